@@ -5,11 +5,16 @@
 at N > 1 every rank works on its own pair (weak scaling, no collective inside forward) and the step ends
 with the RCCL all-gather of the final disparity.  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0: `metric`, `value` (pairs/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of
+one timed step) and the per-step event statistics.  A plain run does only that: set up, warm up, time the K steps, write the
+outputs if asked, print.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; see
+write_outputs): the inputs are a pure function of the arguments, so two builds can be compared output for output.
+`--full` adds what the headline figure does not need, each measured after the timed region:
+  "exact_fp32_path": the same pair through the exact fp32-MFMA path, timed in the same run (split arithmetics, N=1);
   "roofline":     dominant kernel (the implicit-GEMM conv of encoder.convc2 in the selected arithmetic) measured live
                   with hipEvents on the launch stream: `achieved` = algorithmic TFLOP/s from its duration INSIDE the
                   fused loop (nnd_profile_loop_conv), `peak` = dense 16-bit MFMA peak (2500 TFLOP/s) / MFMA products per fp32
@@ -54,6 +59,11 @@ ARITH_NOTE["fp16x2"] = (
 SPLIT_PRODUCTS = {"fp32": 1, "bf16x3": 6, "fp16x2": 3}
 # algorithmic work of one pair: 32 x 43.15 GFLOP loop + 0.5 GFLOP pyramid + 155.2 GFLOP encoder + cnet_proj
 E2E_TFLOP = (32 * 43.15 + 0.5 + 155.2) / 1e3
+# --dump-outputs: 64 MB in all; raft544 writes the final map whole (2 MB per pair) and every iteration's at 2^17 sampled pixels
+# (16 MB), kitti64 / cre8 a sample of 2^23 values (32 MB) of their batch's disparities
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PIXELS = 1 << 17
+DUMP_BATCH_VALUES = 1 << 23
 
 
 def usable_cores() -> int:
@@ -77,9 +87,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-hbm-group", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the exact fp32 path, the roofline block (per-conv timings, in-loop dominant "
+                         "launch, sustained-MFMA probe, HBM-bound kernel group) and the CPU oracle baseline with its parity; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline block")
+    ap.add_argument("--no-hbm-group", action="store_true", help="with --full: skip the HBM-bound kernel group of the roofline block")
     ap.add_argument("--arithmetic", default="fp16x2", choices=["fp16x2", "bf16x3", "fp32"],
                     help="MFMA arithmetic of the update-block / encoder convolutions (the model classes' default is the same): fp16x2 = "
                          "fp32 operands carried as 2 range-scaled fp16 pieces, 3 products on v_mfma_f32_32x32x16_f16; bf16x3 = 3 bf16 "
@@ -176,6 +191,21 @@ def main():
                    "pairs_per_step": world, "parallelism": f"batch-parallel x{world}" if world > 1 else "single", "launch": args.launch,
                    "arithmetic": ARITH_NOTE[args.arithmetic]},
     }
+    if args.dump_outputs and rank == 0:
+        # every iteration's up_disp (what forward() returns; 32 x 2 MB) at fixed sampled pixels, the last one whole (all ranks' pairs)
+        pix = torch.from_numpy(sample_positions(H_IMG * W_IMG, DUMP_PIXELS)).to(dev)
+        write_outputs(args.dump_outputs, {
+            "up_disp_final": final,
+            "up_disp_per_iter_sampled": torch.stack([o["up_disp"][0].reshape(-1) for o in out]).index_select(1, pix)})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            import torch.distributed as dist
+            parallel.barrier()
+            dist.destroy_process_group()
+        return
+
     if args.arithmetic != "fp32" and rank == 0 and world == 1:
         # the same pair through the exact fp32-MFMA path, same run: what the split arithmetic buys and what it changes
         exact = BaseRAFTStereo(iters=ITERS, context_dim=64, arithmetic="fp32")
@@ -435,6 +465,10 @@ def sharded_config(args):
     torch.cuda.synchronize(dev)
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, dev)
     assert out.shape[0] == n_pairs and tuple(out.shape[2:]) == hw
+    if args.dump_outputs and rank == 0:  # the gathered disparities of the whole batch (> 64 MB): a fixed sample of them
+        flat = out.reshape(-1)
+        write_outputs(args.dump_outputs, {
+            "up_disp_final_sampled": flat.index_select(0, torch.from_numpy(sample_positions(flat.numel(), DUMP_BATCH_VALUES)).to(dev))})
     if rank == 0:
         print(json.dumps({
             "metric": metric, "value": n_pairs * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
@@ -446,6 +480,24 @@ def sharded_config(args):
         import torch.distributed as dist
         parallel.barrier()
         dist.destroy_process_group()
+
+
+def sample_positions(n, k, seed=0):
+    """A fixed sample of k positions in range(n) (fewer after removing repeats), in increasing order: a pure function of (n, k, seed)."""
+    import numpy as np
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=min(k, n), dtype=np.int64))
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: each {name: tensor} as dirname/<name>.npy in float32, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs written to {dirname}: " + ", ".join(f"{n} {tuple(a.shape)}" for n, a in host.items()))
 
 
 def _traffic(arithmetic="fp32"):

@@ -287,37 +287,69 @@ def test_models_are_inference_only_and_name_their_fallbacks(raft_sd):
         reg.eval()(torch.zeros(1, 8, 8, 8, 8), [torch.zeros(1, 40, 4, 4), torch.zeros(1, 80, 2, 2), torch.zeros(1, 160, 1, 1)])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/nndepth"), reason="needs the reference checkout (build container only)")
+class _ModuleTree(torch.nn.Module):
+    """Bare nn.Module tree holding the given (state_dict key, tensor) entries: parameters, BatchNorm statistics as buffers."""
+
+    def __init__(self, entries):
+        super().__init__()
+        children = {}
+        for key, val in entries:
+            head, _, rest = key.partition(".")
+            if rest:
+                children.setdefault(head, []).append((rest, val))
+            elif head in ("running_mean", "running_var", "num_batches_tracked"):
+                self.register_buffer(head, val.clone())
+            else:
+                self.register_parameter(head, torch.nn.Parameter(val.clone()))
+        for name, sub in children.items():
+            self.add_module(name, _ModuleTree(sub))
+
+
+class _ReferenceLayoutRAFTStereo(_ModuleTree):
+    """Stand-in for an unmodified reference BaseRAFTStereo(context_dim=64): plain-PyTorch modules with the reference's
+    state_dict keys, order and shapes (oracle/torch_ref.raft_stereo_spec, checked against the imported reference by
+    oracle/make_golden.py), the three seams as plain attributes, and a forward that reaches them in the reference's order
+    (corr_fn(fmap1, fmap2, levels, radius), corr(coords), update_block(net, inp, corr, disp), convex_upsample(disp, mask, rate)).
+    The encoder is replaced by an 8x average pool: only the seams are under test."""
+
+    def __init__(self, sd):
+        super().__init__(sd.items())
+        self.hidden_dim, self.context_dim = 128, 64
+        self.corr_fn = lambda fmap1, fmap2, levels, radius: None
+        self.convex_upsample = lambda flow, mask, rate=8: None
+
+    def forward(self, frame1, frame2):
+        fmap1, fmap2 = (torch.nn.functional.avg_pool2d(f, 8).repeat(1, 86, 1, 1)[:, :256] for f in (frame1, frame2))
+        net, inp = torch.split(fmap1[:, :self.hidden_dim + self.context_dim], [self.hidden_dim, self.context_dim], dim=1)
+        corr = self.corr_fn(fmap1, fmap2, 4, 4)
+        coords = torch.arange(fmap1.shape[-1], dtype=torch.float32).expand(fmap1.shape[0], 1, *fmap1.shape[-2:])
+        net, mask, delta = self.update_block(torch.tanh(net), torch.relu(inp), corr(coords), coords - coords)
+        return [{"up_disp": self.convex_upsample(delta, mask, rate=8)}]
+
+
 def test_patch_swaps_the_seams_of_the_imported_reference_model(raft_sd):
-    """`patch()` on an UNMODIFIED instance of the reference's BaseRAFTStereo — the three seams are replaced, the
-    update block keeps the reference's state_dict keys (strict load both ways), and the patched seams refuse CPU tensors
-    (nothing computes without the HIP device).  Build container only: the reference never travels to the GPU box."""
-    import sys
-    from oracle.make_golden import _install_standins
-    saved = dict(sys.modules), list(sys.path)
-    try:
-        _install_standins()
-        from nndepth.models.raft_stereo.model import BaseRAFTStereo as RefModel
-        from nndepth_amd._lib import NndError
-        from nndepth_amd.blocks import BasicUpdateBlock
-        from nndepth_amd.cost_volume import CorrBlock1D
-        from nndepth_amd.raft_stereo import patch
-        ref = RefModel(iters=2, context_dim=64).eval()
-        ref.load_state_dict(raft_sd, strict=True)
-        keys = list(ref.state_dict().keys())
-        patch(ref)
-        assert isinstance(ref.update_block, BasicUpdateBlock) and ref.corr_fn is CorrBlock1D
-        assert list(ref.state_dict().keys()) == keys                      # same keys, same order
-        ref.load_state_dict(raft_sd, strict=True)                         # the reference's load_weights path still works
-        assert all(torch.equal(ref.state_dict()[k], raft_sd[k]) for k in keys)
-        with pytest.raises(NndError):                                     # the reference's own forward now reaches our seams
-            ref(torch.zeros(1, 3, 32, 64), torch.zeros(1, 3, 32, 64))
-        with pytest.raises(NndError):
-            ref.convex_upsample(torch.zeros(1, 1, 4, 8), torch.zeros(1, 576, 4, 8), 8)
-    finally:
-        for k in set(sys.modules) - set(saved[0]):
-            del sys.modules[k]
-        sys.path[:] = saved[1]
+    """`patch()` on a model laid out like an UNMODIFIED instance of the reference's BaseRAFTStereo (same state_dict
+    keys, order and shapes; plain-PyTorch modules under the seams) — the three seams are replaced, the update block keeps the
+    reference's state_dict keys (strict load both ways), and the patched seams refuse CPU tensors (nothing computes without
+    the HIP device)."""
+    from nndepth_amd._lib import NndError
+    from nndepth_amd.blocks import BasicUpdateBlock
+    from nndepth_amd.cost_volume import CorrBlock1D
+    from nndepth_amd.raft_stereo import patch
+    ref = _ReferenceLayoutRAFTStereo(raft_sd).eval()
+    ref.load_state_dict(raft_sd, strict=True)
+    keys = list(ref.state_dict().keys())
+    assert keys == list(raft_sd.keys())                               # the reference's layout, key for key
+    assert not isinstance(ref.update_block, BasicUpdateBlock)
+    patch(ref)
+    assert isinstance(ref.update_block, BasicUpdateBlock) and ref.corr_fn is CorrBlock1D
+    assert list(ref.state_dict().keys()) == keys                      # same keys, same order
+    ref.load_state_dict(raft_sd, strict=True)                         # the reference's load_weights path still works
+    assert all(torch.equal(ref.state_dict()[k], raft_sd[k]) for k in keys)
+    with pytest.raises(NndError):                                     # the reference-shaped forward now reaches our seams
+        ref(torch.zeros(1, 3, 32, 64), torch.zeros(1, 3, 32, 64))
+    with pytest.raises(NndError):
+        ref.convex_upsample(torch.zeros(1, 1, 4, 8), torch.zeros(1, 576, 4, 8), 8)
 
 
 def test_no_packed_fp32_fma_in_the_update_blocks_valu_convolutions(tmp_path):

@@ -60,6 +60,12 @@ def test_igev_config3_136x240_vs_oracle(R, B, iters):
         gvol = R.cost_volume_filter(reg_sd, "igev.cv_regularizer", fvol.permute(0, 1, 4, 2, 3), guides)
         fp, gp = R.igev_pyramids(fvol, gvol, 4)
         init = R.igev_init_disparity(torch.nn.functional.conv3d(gvol, sq_w, sq_b, padding=1).squeeze(1))
+        # the oracle's own noise on this init: its soft-argmin on the same logits evaluated in float64 and rounded once (what
+        # another rounding of the squeezer's Conv3d gets — another host CPU's, the kernel's); x500 logits make it 4.1e-4 .. 4.3e-4
+        # here, the order of the oracle's 1-thread vs 8-thread shift through the regularised volume (2.7e-4 at B = 2)
+        logits64 = torch.nn.functional.conv3d(gvol.double(), sq_w.double(), sq_b.double(), padding=1).squeeze(1)
+        init_noise = (R.igev_init_disparity(logits64.float()) - init).abs().max().item()
+        del logits64
         # the soft-argmin of a randomly-weighted regulariser is spread over the whole candidate axis (-239 .. 0), which would
         # put half of the coordinates off the map; the loop stage starts from a plausible disparity field instead (-10 .. -4 px
         # around the true shift of 7), the soft-argmin stage above keeps its own output
@@ -96,10 +102,12 @@ def test_igev_config3_136x240_vs_oracle(R, B, iters):
     e_init = (got_init - init).abs().max().item()
     e_init_e2e = (ops.igev_init_disparity(cv.geo_aware_cv[0], sq_w, sq_b, B, G, H, W, W).cpu() - init).abs().max().item()
     print(f"[config3 B={B}] init disparity {e_init:.2e} on the oracle's volume, {e_init_e2e:.2e} end to end "
-          f"(range {init.min().item():.1f} .. {init.max().item():.1f})")
+          f"(range {init.min().item():.1f} .. {init.max().item():.1f}; oracle self-noise {init_noise:.2e})")
     # (round 4: the kernel evaluates the soft-argmin in ATen's order, csrc/corr1d.hip; measured 4.7e-4 .. 5.4e-4 and 5.8e-4 .. 5.9e-4 on
-    #  disparities up to 127 whose x500 logits make exp() amplify one ulp of a logit to 3e-5 relative; bars = 1.5 x the measurement)
-    assert e_init <= 8e-4 and e_init_e2e <= 9e-4
+    #  disparities up to 127 whose x500 logits make exp() amplify one ulp of a logit to 3e-5 relative; bars = 1.5 x the measurement.
+    #  That measurement is against one host's fp32 oracle; another host's moves by up to the self-noise above (6.8e-4 / 9.0e-4 seen),
+    #  so, as for config 4, the bars are those plus the oracle's self-noise: staying inside the oracle's own envelope)
+    assert e_init <= 8e-4 + init_noise and e_init_e2e <= 9e-4 + init_noise
     # a14 at full size: combined 576-channel lookup, bit-exact on identical pyramids
     coords = torch.arange(W).float()[None, None, None].repeat(B, 1, H, 1) + init
     got_lk = ops.igev_lookup(torch.cat([p.reshape(-1) for p in fp]).to(DEV), torch.cat([p.reshape(-1) for p in gp]).to(DEV),
