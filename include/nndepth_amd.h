@@ -53,6 +53,14 @@ extern "C" {
                                 (`packed_dev` is WRITTEN by such a call; the extra kernels run on `stream` like everything
                                 else).  nnd_*_calibration_finish then fixes the layers' activation scales.  See "fp16x2
                                 activation range" below.                                                                    */
+#define NND_FLAG_LAST_UPSAMPLE_ONLY 2 /* update block, the four nnd_*_refine entry points only (every other entry point that computes
+                                refuses it; sizing and packing accept it, the blob layout does not depend on it): the loop computes
+                                the upsampled map of the LAST iteration alone — every other iteration runs flow_head.conv1 (without
+                                mask.0), flow_head.conv2 and the advance, no mask head and no convex upsample.  up_out receives that
+                                one map and up_iter_stride must be 0 (else NND_ERR_INVALID).  up_out, low_out and net_out are
+                                bit-identical to those of the call without the flag.  Ignored by a call that also carries
+                                NND_FLAG_CALIBRATE (the mask head records its range over every iteration: the whole schedule runs).
+                                A library without the flag refuses it as unknown (nnd_update_block_packed_floats < 0).        */
 
 typedef enum {
     NND_OK = 0,
@@ -427,7 +435,9 @@ int nnd_mask_upsample_forward(const float* packed_dev, const float* x, const flo
  * nnd_corr1d_build.  coords start at arange(W) (+ disp_init if non-NULL).  Every iteration:
  * lookup -> update block -> coords += delta -> convex upsample of (coords - arange).
  * up_out: iteration i writes (B,1,rate*H,rate*W) at up_out + i*up_iter_stride floats
- *         (stride 0 keeps only the last); low_out (optional) receives the final 1/rate-res
+ *         (stride 0 keeps only the last, but still computes every iteration's map; desc->flags with
+ *         NND_FLAG_LAST_UPSAMPLE_ONLY and stride 0 computes the last map alone — for all four
+ *         nnd_*_refine entry points); low_out (optional) receives the final 1/rate-res
  *         disparity (B,1,H,W); net_out (optional) the final hidden state.
  * Only flow_channels == 1 (RAFT-Stereo / IGEV-style 1-D disparity).                       */
 int nnd_raft_stereo_refine(const nnd_update_block_desc* desc, const float* packed_dev,

@@ -15,6 +15,7 @@ class NndError(RuntimeError):
 
 
 NND_FLAG_CALIBRATE = 1
+NND_FLAG_LAST_UPSAMPLE_ONLY = 2  # the refine entry points: only the last iteration's upsampled map
 
 
 class _SizedDesc(C.Structure):

@@ -27,7 +27,7 @@ from ._lib import NndError
 from .blocks import BasicUpdateBlock
 from .cost_volume import AGCL
 from .encoder import BasicEncoder
-from .raft_stereo import AutoCalibrate, hip_encoder_blocker, load_weights, require_eval
+from .raft_stereo import AutoCalibrate, check_outputs, hip_encoder_blocker, last_only, load_weights, require_eval
 from .upsample import convex_upsample
 
 
@@ -111,9 +111,12 @@ class CREStereoBase(AutoCalibrate, nn.Module):
                  max_disp: int = 192, num_fnet_channels: int = 256, hidden_dim: int = 128, context_dim: int = 128,
                  search_num: int = 9, mixed_precision: bool = False, test_mode: bool = False, tracing: bool = False,
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
-                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", **kwargs):
+                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
         super().__init__()
         self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        # "all": every iteration's up_disp; "last": [{"up_disp": final}] (raft_stereo.check_outputs).  test_mode (the reference's switch,
+        # returns the final flow tensor) runs last-only as well
+        self.outputs = check_outputs(outputs)
         if fnet_cls != "basic_encoder" or update_cls != "basic_update_block":
             raise ValueError("CREStereoBase: only basic_encoder / basic_update_block exist (as in the reference)")
         if context_dim != hidden_dim:
@@ -172,22 +175,27 @@ class CREStereoBase(AutoCalibrate, nn.Module):
             self._off_version = v
         return self._off_engines
 
-    def _stage(self, corr_fn, net, inp, flow, offset, n_iters: int, iter_mode: bool, outs: List[Dict[str, torch.Tensor]]):
+    def _stage(self, corr_fn, net, inp, flow, offset, n_iters: int, iter_mode: bool, outs: List[Dict[str, torch.Tensor]],
+               last: bool = False):
+        """last: only the stage's final upsampled flow is computed (and nothing is appended to `outs`)."""
         if self.fused_loop and isinstance(corr_fn, AGCL) and n_iters > 0:
             # ONE C-ABI call for the whole stage (nnd_cre_stereo_refine): AGCL + update block + advance + upsample
             eng = self.update_block.sync_engine(net.device)
             f1, f2 = corr_fn.attended()
             up, flow, net = eng.refine_cre(f1, f2, net.float(), inp.float(), self.fnet_ds, n_iters, flow_init=flow,
-                                           extra_offset=None if iter_mode else offset.float())
-            outs.extend({"up_disp": up[i]} for i in range(n_iters))
-            return net, flow, up[n_iters - 1]
+                                           extra_offset=None if iter_mode else offset.float(), keep_all=not last, last_only=last)
+            if not last:
+                outs.extend({"up_disp": up[i]} for i in range(n_iters))
+            return net, flow, up[-1]
         up = None
         for itr in range(n_iters):
             corr = corr_fn(flow, offset, small_patch=(itr % 2 == 1), iter_mode=iter_mode)
             net, mask, delta = self.update_block(net, inp, corr, flow)
             flow = flow + delta
-            up = self.convex_upsample(flow, mask, rate=self.fnet_ds)
-            outs.append({"up_disp": up})
+            if not last or itr == n_iters - 1:
+                up = self.convex_upsample(flow, mask, rate=self.fnet_ds)
+            if not last:
+                outs.append({"up_disp": up})
         return net, flow, up
 
     def forward(self, frame1: torch.Tensor, frame2: torch.Tensor, flow_init: Optional[torch.Tensor] = None,
@@ -202,6 +210,7 @@ class CREStereoBase(AutoCalibrate, nn.Module):
         fmap1, fmap2 = self.forward_fnet(frame1, frame2)
         fmap1, fmap2 = fmap1.float(), fmap2.float()
         net, inp = ops.split_tanh_relu(fmap1, hd)  # split + tanh + relu in one kernel (model.py:148-151)
+        last = self.test_mode or last_only(self)  # every stage last-only: stages 16 and 8 hand on their last upsampled flow alone
         outs: List[Dict[str, torch.Tensor]] = []
         if flow_init is not None:
             scale = fmap1.shape[2] / flow_init.shape[2]
@@ -221,19 +230,19 @@ class CREStereoBase(AutoCalibrate, nn.Module):
             f1_16, f2_16 = self.self_att_fn.forward_maps(f1_pe, f2_pe)
             flow16 = torch.zeros(n, 2, h16, w16, dtype=torch.float32, device=fmap1.device)
             _, _, up = self._stage(self.corr_cls(f1_16, f2_16, att=self.cross_att_fn), net16, inp16, flow16, off16,
-                                   self.iters // 2, False, outs)
+                                   self.iters // 2, False, outs, last)
             # 1/(2*ds): learned offsets, no attention
             off8 = ops.conv2d_offset(conv8, f1_8, self.range_8)
             scale = f1_8.shape[2] / up.shape[2]
             flow8 = ops.resize_bilinear_ac(up, f1_8.shape[2:], scale)  # scale * interpolate(bilinear, align_corners=True)
-            _, _, up = self._stage(self.corr_cls(f1_8, f2_8), net8, inp8, flow8, off8, self.iters // 2, False, outs)
+            _, _, up = self._stage(self.corr_cls(f1_8, f2_8), net8, inp8, flow8, off8, self.iters // 2, False, outs, last)
             scale = fmap1.shape[2] / up.shape[2]
             flow = ops.resize_bilinear_ac(up, fmap1.shape[2:], scale)
         # 1/ds: plain warped window correlation
-        _, _, up = self._stage(self.corr_cls(fmap1, fmap2), net, inp, flow, None, self.iters, True, outs)
+        _, _, up = self._stage(self.corr_cls(fmap1, fmap2), net, inp, flow, None, self.iters, True, outs, last)
         if self.test_mode:
             return up
-        return outs
+        return [{"up_disp": up}] if last else outs
 
 
 def two_stage_forward(model: CREStereoBase, frame1: torch.Tensor, frame2: torch.Tensor) -> List[Dict[str, torch.Tensor]]:

@@ -163,6 +163,11 @@ struct ConvIO {
     bool dst_tiled = false;  // ... out0/out1/aux0/aux1/bmap
     bool src_c4 = false;     // tile-major with 4 channels interleaved (layout.h); channel counts / slice starts % 4 == 0
     bool dst_c4 = false;
+    // > 0: only output channels [0, cout_need) are wanted.  The launch keeps the tile configuration picked for the whole layer
+    // (P, split-K, per-wave K order: the same bits in those channels) and drops the waves of the other output-channel blocks
+    // (fewer per workgroup, same grid rows) where the kernel's staging plan allows it, else the rows that hold none of the wanted
+    // blocks; with one row and no such staging plan it runs the whole layer.
+    int cout_need = 0;
 };
 
 // input channels per K-chunk for a layer shape (host packer and kernels must agree)

@@ -599,11 +599,36 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
         NND_LAUNCH_CHECK();
         return NND_OK;
     }
-    dim3 grid(cfg.tiles_x * cfg.tiles_y, cdiv(L.ncb, cfg.wco), B), block(64 * cfg.wco * cfg.ks);
+    int ny = cdiv(L.ncb, cfg.wco);
+    // ConvIO::cout_need: only output-channel blocks [0, nb) are wanted.  The picked shape stays (P, ks, CI_T: the same K chunks and
+    // partial-tile sums for every wave that remains); as in conv_split.hip (restrict_split), each row keeps wco = ceil(nb / ny) of
+    // its output-channel waves if the fewer threads still cover the patch (npos <= threads, at most 16 channels per staging thread),
+    // else the rows without a wanted block are dropped; with one row and no such staging plan the whole layer runs.
+    bool restricted = false;
+    if (io.cout_need > 0 && cdiv(io.cout_need, 32) < L.ncb) {
+        const int nb = cdiv(io.cout_need, 32), wco = cdiv(nb, ny);
+        const int nthreads = 64 * wco * cfg.ks;
+        const int ngroups = nthreads / cfg.npos;
+        const int ne = ngroups > 0 ? cdiv(cfg.ks * L.CI_T, ngroups) : 1 << 20;
+        if (wco < cfg.wco && ne <= 16) {
+            cfg.wco = wco;
+            cfg.ngroups = ngroups;
+            cfg.ne = ne;
+            a.wco = wco;
+            a.ngroups = ngroups;
+            ny = cdiv(nb, wco);
+            restricted = true;
+        } else if (cdiv(nb, cfg.wco) < ny) {
+            ny = cdiv(nb, cfg.wco);
+            restricted = true;
+        }
+    }
+    dim3 grid(cfg.tiles_x * cfg.tiles_y, ny, B), block(64 * cfg.wco * cfg.ks);
     const bool verbose = switches().conv_verbose;
     if (verbose)
-        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B\n",
-                L.KH, L.KW, L.Cin, L.Cout, L.CI_T, cfg.P, cfg.wco, cfg.ks, cfg.ne, grid.x, grid.y, grid.z, cfg.lds);
+        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B%s\n",
+                L.KH, L.KW, L.Cin, L.Cout, L.CI_T, cfg.P, cfg.wco, cfg.ks, cfg.ne, grid.x, grid.y, grid.z, cfg.lds,
+                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "");
     int rc = NND_ERR_UNSUPPORTED;
     if (L.stride == 2) {
         if (L.KH == 3 && L.KW == 3 && L.CI_T == 16) rc = launch_one<3, 3, 16, 1, 16, 2>(a, grid, block, cfg.lds, stream);

@@ -165,6 +165,33 @@ bool pick_split(const ConvLayer& L, int c0, int c1, int B, int H, int W, bool fa
     if (search(force_ny, force_ks, force_p)) return true;
     return rule && search(-1, -1, -1);  // the regime rule's shape does not exist for this layer: the cost model decides
 }
+
+// ConvIO::cout_need: only output-channel blocks [0, nb) are wanted.  The shape picked for the whole layer stays (P, ks, the K chunks
+// of wave (cbi, kj) and the order the ks partial tiles are summed in), so those channels get the same bits.  The workgroups keep
+// their pixels and the grid its rows where it can: each row keeps wco = ceil(nb / ny) of its output-channel waves (one row: the
+// waves of the unwanted blocks are dropped), if the fewer threads still stage the patch with an instantiated number of staging
+// units (nu <= 4).  Otherwise the rows without a wanted block are dropped; with one row and no such variant the whole layer runs
+// (returns false).  (Dropping rows alone does not make the launch shorter where the whole layer is one workgroup per CU or fewer:
+// each workgroup takes as long as before — RAFT-Stereo at 544x960, flow_head.conv1+mask.0: 2 rows of 128 workgroups of 12 waves,
+// one row 23.7 us against 23.5 for both.)
+bool restrict_split(const ConvLayer& L, int cout_need, SplitCfg* cfg) {
+    const int nb = cdiv(cout_need, 32);
+    if (cout_need <= 0 || nb >= L.ncb) return false;
+    const int wco = cdiv(nb, cfg->ny);
+    const int STR = L.stride, PRI = 3 * STR + L.KH, PCI = 7 * STR + L.KW;
+    const int npos = (STR == 2 && L.KH * L.KW == 1) ? 32 : PRI * PCI;
+    const int nu = cdiv(cfg->P * npos * 2 * cfg->ks, 64 * wco * cfg->ks);
+    if (cfg->P == 2 && nu <= 4 && wco < cfg->wco) {
+        cfg->wco = wco;
+        cfg->ny = cdiv(nb, wco);
+        cfg->nu = nu <= 2 ? 2 : 4;
+        return true;
+    }
+    const int ny = cdiv(nb, cfg->wco);
+    if (ny >= cfg->ny) return false;
+    cfg->ny = ny;
+    return true;
+}
 }  // namespace
 
 // the kernel instantiations live in conv_split_ns2.hip / conv_split_ns3.hip
@@ -200,6 +227,7 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
     const bool fast_ok = !switches().split_no_fast || L.stride == 2;
     NND_REQUIRE(pick_split(L, io.src0.C, io.src1.C, B, H, W, fast_ok, &cfg), "conv_split: no configuration for %dx%d Cin=%d (%d+%d)", L.KH,
                 L.KW, L.Cin, io.src0.C, io.src1.C);
+    const bool restricted = restrict_split(L, io.cout_need, &cfg);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = io.src0.ptr; a.bs0 = io.src0.bstride; a.c0 = io.src0.C;
@@ -238,8 +266,9 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
     dim3 grid(cdiv(cfg.ntiles, cfg.P), cfg.ny, B), block(64 * cfg.wco * cfg.ks);
     const bool verbose = switches().conv_verbose;
     if (verbose)
-        fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B\n", L.KH,
-                L.KW, L.Cin, L.Cout, L.arith, cfg.ny, cfg.wco, cfg.ks, cfg.P, cfg.nu, cfg.fast ? ", fast" : "", grid.x, grid.y, grid.z, cfg.lds);
+        fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B%s\n", L.KH,
+                L.KW, L.Cin, L.Cout, L.arith, cfg.ny, cfg.wco, cfg.ks, cfg.P, cfg.nu, cfg.fast ? ", fast" : "", grid.x, grid.y, grid.z, cfg.lds,
+                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "");
     int rc = L.arith == 3 ? launch_split_ns<3>(a, cfg, L.KH, L.KW, grid, block, stream)
                           : launch_split_ns<2>(a, cfg, L.KH, L.KW, grid, block, stream);
     NND_REQUIRE(rc != NND_ERR_UNSUPPORTED, "conv_split: shape %dx%d P=%d nu=%d %s is not instantiated", L.KH, L.KW, cfg.P, cfg.nu,

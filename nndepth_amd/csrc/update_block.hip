@@ -62,7 +62,7 @@ static int make_plan(const nnd_update_block_desc* d, Plan* p) {
     NND_REQUIRE(d, "update_block: null descriptor");
     NND_REQUIRE(d->struct_size == (int32_t)sizeof(nnd_update_block_desc), "update_block: descriptor of %d bytes, this library expects %d (struct_size)",
                 d->struct_size, (int)sizeof(nnd_update_block_desc));
-    NND_REQUIRE((d->flags & ~NND_FLAG_CALIBRATE) == 0, "update_block: unknown flags 0x%x", d->flags);
+    NND_REQUIRE((d->flags & ~(NND_FLAG_CALIBRATE | NND_FLAG_LAST_UPSAMPLE_ONLY)) == 0, "update_block: unknown flags 0x%x", d->flags);
     const int hid = d->hidden_dim, ctx = d->context_dim, cp = d->cor_planes, fc = d->flow_channels, mc = d->mask_channels;
     NND_REQUIRE(hid > 0 && hid % 32 == 0, "update_block: hidden_dim %d must be a positive multiple of 32", hid);
     NND_REQUIRE(ctx > 0 && ctx % 8 == 0, "update_block: context_dim %d must be a positive multiple of 8", ctx);
@@ -110,6 +110,13 @@ static int make_plan(const nnd_update_block_desc* d, Plan* p) {
     p->fc2_b = off; off += 4;  // keep 16-B alignment of what follows
     p->L[C_M2] = mk(1, 1, 2 * hid, mc, &off, ar(C_M2));  // consumed by the fused mask + upsample kernel in the same arithmetic
     p->total = off;
+    return NND_OK;
+}
+
+// NND_FLAG_LAST_UPSAMPLE_ONLY selects a schedule of the fused refinement loops (enqueue_refine); the sizing and packing entry points
+// accept it (the blob layout does not depend on it), the other entry points that compute refuse it
+static int refuse_last_only(const nnd_update_block_desc* d, const char* what) {
+    NND_REQUIRE(!d || !(d->flags & NND_FLAG_LAST_UPSAMPLE_ONLY), "%s: NND_FLAG_LAST_UPSAMPLE_ONLY applies to the refine entry points only", what);
     return NND_OK;
 }
 
@@ -705,6 +712,7 @@ int nnd_update_block_forward(const nnd_update_block_desc* desc, const float* pac
     Plan p;
     int rc = make_plan(desc, &p);
     if (rc != NND_OK) return rc;
+    if ((rc = refuse_last_only(desc, "update_block_forward")) != NND_OK) return rc;
     NND_REQUIRE(packed && net && inp && corr && flow && net_out && delta_out && workspace, "update_block_forward: null pointer");
     NND_REQUIRE(B > 0 && H > 0 && W > 0, "update_block_forward: bad shape");
     CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && p.d.arithmetic == 2);
@@ -773,6 +781,12 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
     Plan p;
     int rc = make_plan(desc, &p);
     if (rc != NND_OK) return rc;
+    // NND_FLAG_LAST_UPSAMPLE_ONLY: up_out receives one map, the last iteration's.  A calibrating call ignores the flag and runs the
+    // whole schedule (mask.0 and mask.2 record their largest activation over every iteration), each map into that one buffer.
+    const bool last_flag = (p.d.flags & NND_FLAG_LAST_UPSAMPLE_ONLY) != 0;
+    NND_REQUIRE(!last_flag || up_iter_stride == 0,
+                "refine: NND_FLAG_LAST_UPSAMPLE_ONLY writes one upsampled map, so up_iter_stride must be 0 (got %lld)", (long long)up_iter_stride);
+    const bool last_only = last_flag && !(p.d.flags & NND_FLAG_CALIBRATE);
     NND_REQUIRE(packed && (pyramid || cre) && net && inp && up_out && workspace, "refine: null pointer");
     const bool igev = geo_pyramid != nullptr;
     const int fc = p.d.flow_channels;
@@ -843,6 +857,11 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
     // Per-iteration schedule, all on the caller's stream:
     //   convf1 + convf2 (flow branch of the motion encoder: one launch in split arithmetic), lookup (+convc1), convc2, conv, zr1, q1, zr2, q2,
     //   flow_head.conv1+mask.0, flow_head.conv2+advance, mask.2 + convex upsample (fused)
+    // NND_FLAG_LAST_UPSAMPLE_ONLY: every iteration but the last ends with flow_head.conv1 alone (output channels [0, hid) of the merged
+    // launch: ConvIO::cout_need) and flow_head.conv2 + advance (the separate kernel, bit-identical to the folded one); the last
+    // iteration runs the full schedule.  Bit-identity needs the merged layer's tile configuration (same split-K, P and K order) for
+    // the flow-head channels; launch_conv keeps it and drops only the mask.0 waves / rows (or runs the whole layer where its staging
+    // plan cannot shrink: conv_split.hip restrict_split, conv_mfma.hip launch_conv).
     // Rounds 1-2 ran the flow branch on a low-priority side stream beside lookup / convc2 (per-call fork/join events).
     // Measured on MI355X, same box, ms per 544x960 pair: side stream 11.79, in line 11.82 (KITTI batch 8 70.5 / 71.0,
     // CREStereo 39.8 / 39.9, IGEV batch 8 190.1 / 190.5): the overlap it bought (convc2 61 us beside the branch instead
@@ -895,11 +914,14 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
         if (fused_lk && interleaved && igev_lookup_convc1_il_supported(groups, num_levels, radius)) {  // IGEV over the group-interleaved copy of both pyramids
             NND_TRY(igev_lookup_convc1_il_launch(interleaved, groups, w.coords, p.L[C_C1], packed, w.c1, 256 * n, B, H, W, num_levels,
                                                  radius, s, ws_c4()));
+            NND_TRY(debug_sync("lookup+convc1 (interleaved)", s));
         } else if (fused_lk && p.L[C_C1].arith == 0) {  // lookup + convc1 in one kernel, the sampled features never reach HBM
             NND_TRY(lookup_convc1_launch(pyramid, geo_pyramid, groups, w.coords, p.L[C_C1], packed, w.c1, 256 * n, B, H, W,
                                          num_levels, radius, s, ws_c4()));
+            NND_TRY(debug_sync("lookup+convc1", s));
         } else {
             NND_TRY(lookup(s, it));
+            NND_TRY(debug_sync("lookup", s));
             NND_TRY(run_conv(p, packed, w, C_C1, c, nullptr, nullptr, B, H, W, s));
         }
         }
@@ -910,6 +932,16 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
         if (p.sep) {
             NND_TRY(loop_conv(C_ZR2X));
             NND_TRY(loop_conv(C_Q2X));
+        }
+        if (last_only && it + 1 < iters) {
+            // last-upsample-only schedule, every iteration but the last: flow_head.conv1 (output channels [0, hid) of the merged
+            // launch, in the tile configuration of the whole layer: the same bits), flow_head.conv2 + advance; no mask head, no upsample
+            ConvIO io = conv_io(p, w, C_FHM, c, n, nullptr, nullptr);
+            io.cout_need = hid;
+            NND_TRY(launch_conv(p.L[C_FHM], packed, io, conv_epi(C_FHM), B, H, W, s));
+            NND_TRY(debug_sync("flow_head.conv1", s));
+            NND_TRY(run_fc2(p, packed, w, w.delta, cre ? 2 : 1, igev, B, H, W, s));
+            continue;
         }
         NND_TRY(loop_conv(C_FHM));  // flow_head.conv1 and mask.0 in one launch
         float* up_it = up_out + (int64_t)it * up_iter_stride;
@@ -932,9 +964,11 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
         if (fused_up) {  // mask.2 + softmax + upsample in one kernel: the 9*r*r-channel mask never reaches HBM
             NND_TRY(mask_upsample_launch(p.L[C_M2], packed, w.fm + hid * n, (int64_t)3 * hid * n, w.flow, up_it, B, H, W, rate, s,
                                          true, fc, ws_c4()));
+            NND_TRY(debug_sync("mask.2 + upsample", s));
         } else {
             NND_TRY(run_conv(p, packed, w, C_M2, c, w.mask, nullptr, B, H, W, s));
             NND_TRY(convex_upsample_launch(w.flow, w.mask, up_it, B, fc, H, W, rate, s, true));
+            NND_TRY(debug_sync("convex upsample", s));
         }
     }
     if (low_out) NND_TRY(from_tiled(w.flow, fc * n, low_out, B, fc, H, W, s));
@@ -1095,6 +1129,7 @@ int nnd_profile_conv(const nnd_update_block_desc* desc, const float* packed, flo
     Plan p;
     int rc = make_plan(desc, &p);
     if (rc != NND_OK) return rc;
+    if ((rc = refuse_last_only(desc, "profile_conv")) != NND_OK) return rc;
     NND_REQUIRE(packed && workspace && ms_out && flops_out, "profile_conv: null pointer");
     NND_REQUIRE(which >= 0 && which < C_LOOP_COUNT && reps > 0, "profile_conv: bad conv index / reps");
     NND_REQUIRE(p.sep || (which != C_ZR2X && which != C_Q2X), "profile_conv: conv_gru has no second GRU pass");
@@ -1128,6 +1163,7 @@ static int profile_loop(const nnd_update_block_desc* desc, const float* packed, 
                         int which, void* stream, float* ms_out, bool empty) {
     NND_REQUIRE(ms_out && which >= 0 && which < C_LOOP_COUNT && which != C_C1 && which != C_M2 && iters > 0,
                 "profile_loop_conv: conv %d is not a stand-alone launch of the recurrence", which);
+    if (int rc = refuse_last_only(desc, "profile_loop_conv")) return rc;
     LoopProbe probe;
     probe.which = which;
     probe.empty = empty;

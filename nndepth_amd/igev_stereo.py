@@ -28,7 +28,7 @@ from . import ops
 from ._lib import NndError
 from .blocks import BasicUpdateBlock
 from .cost_volume import GeometryAwareCostVolume
-from .raft_stereo import AutoCalibrate, load_weights, require_eval
+from .raft_stereo import AutoCalibrate, check_outputs, last_only, load_weights, require_eval
 from .upsample import convex_upsample
 
 
@@ -160,9 +160,10 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
     def __init__(self, update_cls: str = "basic_update_block", cv_groups: int = 8, iters: int = 12, hidden_dim: int = 128,
                  context_dim: int = 128, corr_levels: int = 4, corr_radius: int = 4, tracing: bool = False,
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
-                 fused_loop: bool = True, arithmetic: str = "fp16x2"):
+                 fused_loop: bool = True, arithmetic: str = "fp16x2", outputs: str = "all"):
         super().__init__()
         self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        self.outputs = check_outputs(outputs)  # "all": every iteration's up_disp; "last": [{"up_disp": final}] (raft_stereo.check_outputs)
         if update_cls != "basic_update_block":
             raise KeyError(update_cls)
         self.fnet = self._init_fnet()
@@ -235,6 +236,7 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
                           RuntimeWarning, stacklevel=2)
             logits = self.cv_squeezer(geo0.reshape(B, self.cv_groups, H1, W1, W2).permute(0, 1, 4, 2, 3)).squeeze(1)
             init = ops.softargmin_disparity(logits.float())
+        last = last_only(self)
         if self.fused_loop and isinstance(corr, GeometryAwareCostVolume):
             eng = self.update_block.sync_engine(frame1.device)
             il = corr.interleaved()
@@ -242,16 +244,17 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
             # the pooled levels of the two pyramids are then never made
             feat, geo = corr.pyramids(pooled=not ops.igev_refine_reads_interleaved(self.cv_groups, self.corr_levels, self.corr_radius))
             up, low, _ = eng.refine_igev(feat, geo, self.cv_groups, self.corr_levels, self.corr_radius,
-                                         net.float(), inp.float(), fnet_ds, self.iters, disp_init=init, keep_all=True,
-                                         interleaved=il)
+                                         net.float(), inp.float(), fnet_ds, self.iters, disp_init=init, keep_all=not last,
+                                         interleaved=il, last_only=last)
             self.last_low_coords = low  # the loop's state after the last iteration: absolute coordinates at 1/4 resolution (Q5)
-            return [{"up_disp": up[i]} for i in range(self.iters)]
+            return [{"up_disp": up[i]} for i in range(up.shape[0])]
         coords1 = self.initialize_coords(fmap1) + init
         outs = []
-        for _ in range(self.iters):
+        for i in range(self.iters):
             net, mask, delta = self.update_block(net, inp, corr(coords1), coords1)
             coords1 = coords1 + delta
-            outs.append({"up_disp": self.convex_upsample(coords1, mask, rate=fnet_ds)})
+            if not last or i == self.iters - 1:
+                outs.append({"up_disp": self.convex_upsample(coords1, mask, rate=fnet_ds)})
         self.last_low_coords = coords1
         return outs
 

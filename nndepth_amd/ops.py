@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import NND_FLAG_CALIBRATE, Conv3dDesc, ConvDesc, EncoderDesc, NndError, UpdateBlockDesc, check, lib
+from ._lib import NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, NndError, UpdateBlockDesc, check, lib
 
 
 def _dev(*tensors: torch.Tensor) -> torch.device:
@@ -357,6 +357,20 @@ class UpdateBlockEngine:
         self.desc.flags = _calib_flags(self) if self.arithmetic == "fp16x2" else 0
         return C.byref(self.desc)
 
+    @staticmethod
+    def _keep_all(keep_all: Optional[bool], last_only: bool) -> bool:
+        """keep_all=None (default): every iteration's map unless last_only."""
+        if last_only and keep_all:
+            raise NndError("refine: last_only=True computes one upsampled map; it cannot be combined with keep_all=True")
+        return (not last_only) if keep_all is None else bool(keep_all)
+
+    def _refine_desc(self, last_only: bool) -> UpdateBlockDesc:
+        """The descriptor of one refine call: a copy of `self.desc` with this call's flags, so NND_FLAG_LAST_UPSAMPLE_ONLY never
+        reaches a later call (update_block_forward refuses it)."""
+        d = UpdateBlockDesc.from_buffer_copy(self.desc)
+        d.flags = (_calib_flags(self) if self.arithmetic == "fp16x2" else 0) | (NND_FLAG_LAST_UPSAMPLE_ONLY if last_only else 0)
+        return d
+
     def _calibration_finish(self, status: Optional[torch.Tensor]) -> None:
         self.desc.flags = 0
         check(lib.nnd_update_block_calibration_finish(C.byref(self.desc), _p(self.packed), _p(status), _stream(self.packed.device)),
@@ -420,10 +434,14 @@ class UpdateBlockEngine:
         return net_out, mask, delta
 
     def refine(self, pyr, num_levels: int, radius: int, net, inp, rate: int, iters: int,
-               disp_init=None, keep_all: bool = True):
-        """Fused loop -> (up (iters or 1, B,1,rate*H,rate*W), low (B,1,H,W), net (B,hid,H,W))."""
+               disp_init=None, keep_all: Optional[bool] = None, last_only: bool = False):
+        """Fused loop -> (up (iters or 1, B,1,rate*H,rate*W), low (B,1,H,W), net (B,hid,H,W)).
+        keep_all (default unless last_only): every iteration's upsampled map; False: the last one, all of them computed.
+        last_only: the last iteration's map alone is computed (NND_FLAG_LAST_UPSAMPLE_ONLY), the same bits as keep_all's up[-1]."""
         if self.packed is None:
             raise NndError("UpdateBlockEngine: parameters not loaded")
+        keep_all = self._keep_all(keep_all, last_only)
+        desc = self._refine_desc(last_only)
         d = _dev(pyr, net, inp, self.packed)
         net, inp = net.contiguous(), inp.contiguous()
         B, _, H, W = net.shape
@@ -442,17 +460,19 @@ class UpdateBlockEngine:
         if disp_init is not None:
             disp_init = disp_init.contiguous()
         with torch.cuda.device(d):
-            check(lib.nnd_raft_stereo_refine(self._desc(), _p(self.packed), _p(pyr), num_levels, radius,
+            check(lib.nnd_raft_stereo_refine(C.byref(desc), _p(self.packed), _p(pyr), num_levels, radius,
                                              _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low), _p(net_out),
                                              _p(ws), B, H, W, rate, iters, _stream(d)), "raft_stereo_refine")
         return up, low, net_out
 
     def refine_group(self, group_pyr, num_groups: int, num_levels: int, radius: int, net, inp, rate: int, iters: int,
-                     disp_init=None, keep_all: bool = True):
+                     disp_init=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """One cascade stage of Coarse2FineGroupRepViTRAFTStereo (raft_stereo/model.py:297-311): refine() with GroupCorrBlock1D's
         lookup over the pyramid of raft_group_corr_build -> (up, low, net)."""
         if self.packed is None:
             raise NndError("UpdateBlockEngine: parameters not loaded")
+        keep_all = self._keep_all(keep_all, last_only)
+        desc = self._refine_desc(last_only)
         d = _dev(group_pyr, net, inp, self.packed)
         net, inp = net.contiguous(), inp.contiguous()
         B, _, H, W = net.shape
@@ -471,17 +491,19 @@ class UpdateBlockEngine:
             _dev(disp_init)
             disp_init = disp_init.contiguous()
         with torch.cuda.device(d):
-            check(lib.nnd_raft_stereo_group_refine(self._desc(), _p(self.packed), _p(group_pyr), num_groups, num_levels, radius,
+            check(lib.nnd_raft_stereo_group_refine(C.byref(desc), _p(self.packed), _p(group_pyr), num_groups, num_levels, radius,
                                                    _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low), _p(net_out),
                                                    _p(ws), B, H, W, rate, iters, _stream(d)), "raft_stereo_group_refine")
         return up, low, net_out
 
     def refine_igev(self, feat_pyr, geo_pyr, num_groups: int, num_levels: int, radius: int, net, inp, rate: int,
-                    iters: int, disp_init=None, keep_all: bool = True, interleaved=None):
+                    iters: int, disp_init=None, keep_all: Optional[bool] = None, interleaved=None, last_only: bool = False):
         """IGEV loop (absolute coordinates, combined lookup) -> (up, low, net) like refine().
         interleaved: optional igev_interleave_pyramids(feat_pyr, geo_pyr, ...) — the loop then gathers from it."""
         if self.packed is None:
             raise NndError("UpdateBlockEngine: parameters not loaded")
+        keep_all = self._keep_all(keep_all, last_only)
+        desc = self._refine_desc(last_only)
         d = _dev(feat_pyr, geo_pyr, net, inp, self.packed)
         net, inp = net.contiguous(), inp.contiguous()
         B, _, H, W = net.shape
@@ -506,17 +528,19 @@ class UpdateBlockEngine:
         if disp_init is not None:
             disp_init = disp_init.contiguous()
         with torch.cuda.device(d):
-            check(lib.nnd_igev_stereo_refine(self._desc(), _p(self.packed), _p(feat_pyr), _p(geo_pyr), _p(interleaved), num_groups,
+            check(lib.nnd_igev_stereo_refine(C.byref(desc), _p(self.packed), _p(feat_pyr), _p(geo_pyr), _p(interleaved), num_groups,
                                              num_levels, radius, _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low),
                                              _p(net_out), _p(ws), B, H, W, rate, iters, _stream(d)), "igev_stereo_refine")
         return up, low, net_out
 
     def refine_cre(self, fmap1, fmap2, net, inp, rate: int, iters: int, flow_init=None, extra_offset=None,
-                   scratch=None, keep_all: bool = True):
+                   scratch=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """One CREStereo cascade stage (AGCL -> update block -> flow += delta -> 2-channel upsample, `iters` times)
         -> (up (iters or 1, B,2,rate*H,rate*W), flow (B,2,H,W), net).  extra_offset=None: iter mode."""
         if self.packed is None:
             raise NndError("UpdateBlockEngine: parameters not loaded")
+        keep_all = self._keep_all(keep_all, last_only)
+        desc = self._refine_desc(last_only)
         d = _dev(fmap1, fmap2, net, inp, self.packed)
         fmap1, fmap2, net, inp = (t.contiguous() for t in (fmap1, fmap2, net, inp))
         B, Cf, H, W = fmap1.shape
@@ -541,7 +565,7 @@ class UpdateBlockEngine:
         if scratch is None or scratch.numel() < need:
             scratch = torch.empty(need, dtype=torch.float32, device=d)
         with torch.cuda.device(d):
-            check(lib.nnd_cre_stereo_refine(self._desc(), _p(self.packed), _p(fmap1), _p(fmap2), Cf, _p(extra_offset),
+            check(lib.nnd_cre_stereo_refine(C.byref(desc), _p(self.packed), _p(fmap1), _p(fmap2), Cf, _p(extra_offset),
                                             _p(scratch), scratch.numel(), _p(net), _p(inp), _p(flow_init), _p(up), stride, _p(low),
                                             _p(net_out), _p(ws), B, H, W, rate, iters, _stream(d)), "cre_stereo_refine")
         return up, low, net_out

@@ -52,6 +52,22 @@ def require_eval(model: nn.Module) -> None:
                        "(training-mode BatchNorm / autograd are not built)")
 
 
+OUTPUTS = ("all", "last")
+
+
+def check_outputs(outputs: str) -> str:
+    """The `outputs` switch of the model classes: "all" = every iteration's up_disp (the reference's list), "last" = the final one
+    alone, as a list of one dict (`outs[-1]["up_disp"]` of the reference's inference / evaluate scripts is unchanged); the fused loops
+    then compute no mask head and no upsample on the other iterations (NND_FLAG_LAST_UPSAMPLE_ONLY)."""
+    if outputs not in OUTPUTS:
+        raise NndError(f"outputs={outputs!r}: must be 'all' (every iteration's up_disp) or 'last' (the final one only)")
+    return outputs
+
+
+def last_only(model: nn.Module) -> bool:
+    return check_outputs(getattr(model, "outputs", "all")) == "last"
+
+
 class AutoCalibrate:
     """fp16x2 activation range (include/nndepth_amd.h "fp16x2 activation range", csrc/calib.hip), shared by the model classes.
 
@@ -67,16 +83,22 @@ class AutoCalibrate:
 
     def calibrate(self, *args, max_passes: int = 4, **kwargs):
         require_eval(self)
-        for _ in range(max_passes):
-            with ops.calibration() as c, torch.no_grad():
-                self._forward(*args, **kwargs)
-            if not (c.status & 1):  # bit 0: a layer saw inf / NaN at the scale it had (lowered by 2^12 since): go again
-                return self
+        outputs = getattr(self, "outputs", "all")
+        self.outputs = "all"  # the mask head records its range over every iteration, whatever the model returns
+        try:
+            for _ in range(max_passes):
+                with ops.calibration() as c, torch.no_grad():
+                    self._forward(*args, **kwargs)
+                if not (c.status & 1):  # bit 0: a layer saw inf / NaN at the scale it had (lowered by 2^12 since): go again
+                    return self
+        finally:
+            self.outputs = outputs
         raise NndError(f"{type(self).__name__}.calibrate: activations still overflow fp16 after {max_passes} passes "
                        "(non-finite inputs or weights?)")
 
     def _forward_calibrated(self, *args, **kwargs):
         """`_forward`, calibrating first if an fp16x2 engine on its path still has the default activation scales."""
+        check_outputs(getattr(self, "outputs", "all"))  # (an attribute: it may have been set after construction)
         if self.arithmetic != "fp16x2" or not self.auto_calibrate:
             return self._forward(*args, **kwargs)
         try:
@@ -104,9 +126,10 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
     def __init__(self, iters: int = 12, fnet_dim: int = 256, hidden_dim: int = 128, context_dim: int = 128,
                  corr_levels: int = 4, corr_radius: int = 4, tracing: bool = False,
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
-                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", **kwargs):
+                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
         super().__init__()
         self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        self.outputs = check_outputs(outputs)  # "all": every iteration's up_disp; "last": [{"up_disp": final}] (check_outputs)
         self.iters, self.fnet_dim, self.hidden_dim, self.context_dim = iters, fnet_dim, hidden_dim, context_dim
         self.corr_levels, self.corr_radius = corr_levels, corr_radius
         self.tracing, self.include_preprocessing = tracing, include_preprocessing
@@ -167,20 +190,22 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
         fmap1, fmap2 = fmap1.float(), fmap2.float()
         net, inp = ops.split_tanh_relu(cnet.float(), self.hidden_dim)  # split + tanh + relu in one kernel (model.py:119-122)
         corr = self.corr_fn(fmap1, fmap2, self.corr_levels, self.corr_radius)
+        last = last_only(self)
         if self.fused_loop and isinstance(corr, CorrBlock1D):
             eng = self.update_block.sync_engine(frame1.device)
             up, _, _ = eng.refine(corr._pyr, self.corr_levels, self.corr_radius, net.float(), inp.float(),
-                                  rate, self.iters, keep_all=True)
-            return [{"up_disp": up[i]} for i in range(self.iters)]
+                                  rate, self.iters, keep_all=not last, last_only=last)
+            return [{"up_disp": up[i]} for i in range(up.shape[0])]
         # seam-by-seam loop (same shape as the reference's), every step still a HIP kernel
         coords1 = self.initialize_coords(fmap1)
         org = self.initialize_coords(fmap1)
         outs = []
-        for _ in range(self.iters):
+        for i in range(self.iters):
             sampled = corr(coords1)
             net, mask, delta = self.update_block(net, inp, sampled, coords1 - org)
             coords1 = coords1 + delta
-            outs.append({"up_disp": self.convex_upsample(coords1 - org, mask, rate=rate)})
+            if not last or i == self.iters - 1:
+                outs.append({"up_disp": self.convex_upsample(coords1 - org, mask, rate=rate)})
         return outs
 
 
@@ -198,10 +223,11 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
 
     def __init__(self, iters: int = 12, hidden_dim: int = 128, context_dim: int = 128, corr_levels: int = 1, corr_radius: int = 4,
                  num_groups: int = 4, weights: Optional[str] = None, strict_load: bool = True, fused_loop: bool = True,
-                 arithmetic: str = "fp16x2", **kwargs):
+                 arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
         super().__init__()
         assert corr_levels == 1, "Corr level must be 1 in Coarse2FineGroupRepViTRaftStereo"  # model.py:214
         self.arithmetic = arithmetic
+        self.outputs = check_outputs(outputs)  # "last": every stage last-only, the final stage's map alone returned
         self.iters, self.hidden_dim, self.context_dim = iters, hidden_dim, context_dim
         self.corr_levels, self.corr_radius, self.num_groups = corr_levels, corr_radius, num_groups
         self.fused_loop = fused_loop
@@ -256,8 +282,10 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
         return self.refine_stages(feats, cnets, tuple(frame1.shape[-2:]))
 
     def refine_stages(self, feats, cnets, frame_hw) -> List[Dict[str, torch.Tensor]]:
-        """The cascade behind the encoder side (model.py:280-320): HIP kernels only."""
+        """The cascade behind the encoder side (model.py:280-320): HIP kernels only.  outputs="last": every stage computes its last
+        upsampled map alone (it seeds the next stage) and only the final stage's is returned."""
         B = feats[0].shape[0] // 2
+        last = last_only(self)
         outs: List[Dict[str, torch.Tensor]] = []
         up_last = None
         for idx, feat in enumerate(feats):
@@ -271,28 +299,31 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
             if self.fused_loop and isinstance(corr, GroupCorrBlock1D):
                 eng = self.update_block.sync_engine(fmap1.device)
                 up, _, _ = eng.refine_group(corr._pyr, self.num_groups, self.corr_levels, self.corr_radius, net, inp, 4, self.iters,
-                                            disp_init=up_last, keep_all=True)
-                ups = [up[i] for i in range(self.iters)]
+                                            disp_init=up_last, keep_all=not last, last_only=last)
+                ups = [up[i] for i in range(up.shape[0])]
             else:  # seam-by-seam loop (same shape as the reference's), every step still a HIP kernel
                 org = self.initialize_coords(fmap1)
                 coords1 = org if up_last is None else org + up_last
                 ups = []
-                for _ in range(self.iters):
+                for i in range(self.iters):
                     sampled = corr(coords1)
                     net, mask, delta = self.update_block(net, inp, sampled, coords1 - org)
                     coords1 = coords1 + delta
-                    ups.append(self.convex_upsample(coords1 - org, mask, rate=(4, 4)))
-            for u in ups:
-                rate = frame_hw[1] / u.shape[-1]
-                outs.append({"up_disp": u if rate == 1 else nn.functional.interpolate(u, size=tuple(frame_hw)) * rate})
+                    if not last or i == self.iters - 1:
+                        ups.append(self.convex_upsample(coords1 - org, mask, rate=(4, 4)))
+            if not last or idx == len(feats) - 1:
+                for u in ups:
+                    rate = frame_hw[1] / u.shape[-1]
+                    outs.append({"up_disp": u if rate == 1 else nn.functional.interpolate(u, size=tuple(frame_hw)) * rate})
             up_last = ups[-1]
         return outs
 
 
-def patch_coarse2fine(model: nn.Module, arithmetic: str = "fp16x2", fused_loop: bool = True) -> nn.Module:
+def patch_coarse2fine(model: nn.Module, arithmetic: str = "fp16x2", fused_loop: bool = True, outputs: str = "all") -> nn.Module:
     """Swap the HIP hot path into a reference `Coarse2FineGroupRepViTRAFTStereo` instance in place: `patch()` for `update_block` and
     `convex_upsample`, `corr_fn` = GroupCorrBlock1D, and `forward` = the reference's encoder side (its own fnet / fusion_blocks /
-    cnet_proj modules) followed by Coarse2FineRAFTStereoBase.refine_stages."""
+    cnet_proj modules) followed by Coarse2FineRAFTStereoBase.refine_stages.  `outputs`: as on Coarse2FineRAFTStereoBase."""
+    model.outputs = check_outputs(outputs)
     patch(model, arithmetic)
     model.corr_fn = GroupCorrBlock1D
     model.convex_upsample = lambda flow, mask, rate=(4, 4): convex_upsample(flow, mask, rate if isinstance(rate, int) else rate[0])
