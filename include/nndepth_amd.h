@@ -355,6 +355,66 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed_dev, 
 /* fp16x2 calibration of the encoder's layers after forwards with NND_FLAG_CALIBRATE (as nnd_update_block_calibration_finish) */
 int nnd_encoder_calibration_finish(const nnd_encoder_desc* desc, float* packed_dev, int32_t* status_dev, void* stream);
 
+/* ------------------------------------------------------------------------- RepViT encoder side (Coarse2Fine)
+ * Replaces the encoder side of Coarse2FineGroupRepViTRAFTStereo.forward  nndepth/models/raft_stereo/model.py:275-288: RepViT.forward
+ * (nndepth/encoders/rep_vit.py:736-744; stem rep_vit.py:429-479, ConvPatchEmbed 309-360, RepFormerBlock 227-306, RepTokenMixer
+ * 117-224, AttentionBlock 363-426, ChannelMixer 69-114), LinearSelfAttention (nndepth/blocks/attn_block.py:151-169), MobileOneBlock
+ * (nndepth/blocks/conv.py:130-371), RepLargeKernelConv (conv.py:374-442; no activation, conv.py:454) and FeatureFusionBlock
+ * (conv.py:549-567), plus the three MobileOne cnet_proj blocks (model.py:216-222).  Exact fp32 (no split arithmetic, no calibration).
+ * The descriptor carries the configuration; strides are 1 or 2 (the reference's (1, 1) / (2, 2)), patch_size 3, 5 or 7.
+ * nnd_repvit_pack (HOST): `tensors` = nnd_repvit_num_tensors(desc) pointers, 3 per layer {weight, bias, scale or NULL}, every
+ * branch / BatchNorm already folded (ops.RepViTEngine, float64 on the host), in the layer order:
+ *   stem.0 (16,3,3,3) | stem.1 (16,1,3,3) | stem.2 (16,16,1,1) | per stage i: patch embed depthwise (C_in,1,k,k), patch embed 1x1
+ *   (C_i,C_in,1,1), per block: [repmixer: token mixer depthwise (C_i,1,3,3)] or [attention: qkv (1+2C_i,C_i,1,1), out_proj (C_i,C_i,1,1)
+ *   with scale = layer_scale_1], [FFN: fc1 (hid,C_i,1,1), fc2 (C_i,hid,1,1) with scale = layer_scale(_2)] |
+ *   cnet_proj.0 (cnet_dim,C_3), cnet_proj.1 (cnet_dim,fusion_dim[0]), cnet_proj.2 (cnet_dim,fusion_dim[0]) |
+ *   fusion 0 coarse (fusion_dim[0],C_3), fine (fusion_dim[0],C_1) | fusion 1 coarse (fusion_dim[1],fusion_dim[0]), fine (fusion_dim[1],16)
+ * (a fusion block's halves: conv3 composed with conv1 / conv2; the coarse half is applied before the bilinear upsample).
+ * A layer with a scale computes residual + scale * (conv + bias) (the caller passes bias already multiplied by the scale).
+ * nnd_repvit_forward: frames (nsplit,3,H,W) and frames_b (N - nsplit,3,H,W) where they lie (frames_b NULL: all N from frames) ->
+ *   feat0 (N,C_3,H/64,W/64), feat1 (N,fusion_dim[0],H/16,W/16), feat2 (N,fusion_dim[1],H/4,W/4) (at the default strides; each
+ *   stride-2 step maps n to (n - 1) / 2 + 1) and cnet0..2 (B,cnet_dim,...) of the first B = nsplit samples (frames_b given) or
+ *   all N.  workspace: nnd_repvit_workspace_floats(desc, N, H, W) floats, caller-owned.  All launches on `stream`.            */
+typedef struct nnd_repvit_desc {
+    int32_t struct_size;     /* sizeof(nnd_repvit_desc) */
+    int32_t stem_strides[3]; /* 1 or 2 */
+    int32_t patch_size;      /* 3, 5, 7 */
+    int32_t down_strides[4]; /* 1 or 2 */
+    int32_t channels[4];     /* stage widths (32, 64, 128, 256) */
+    int32_t num_blocks[4];
+    int32_t mixer[4];        /* 0 = repmixer, 1 = attention */
+    int32_t ffn_hidden[4];   /* 0 = no FFN (use_ffn false; attention stages always have one) */
+    int32_t cnet_dim;        /* 2 * context_dim */
+    int32_t fusion_dim[2];   /* output channels of the two FeatureFusionBlocks (64, 64) */
+    int32_t flags;           /* 0 */
+} nnd_repvit_desc;
+int nnd_repvit_num_tensors(const nnd_repvit_desc* desc);
+int64_t nnd_repvit_packed_floats(const nnd_repvit_desc* desc);
+int64_t nnd_repvit_workspace_floats(const nnd_repvit_desc* desc, int N, int H, int W);
+int nnd_repvit_pack(const nnd_repvit_desc* desc, const float* const* tensors_host, float* packed_host);
+int nnd_repvit_forward(const nnd_repvit_desc* desc, const float* packed_dev, const float* frames, const float* frames_b, int nsplit,
+                       float* feat0, float* feat1, float* feat2, float* cnet0, float* cnet1, float* cnet2, float* workspace, int N,
+                       int H, int W, void* stream);
+
+/* The encoder side's kernels one at a time, as nnd_repvit_forward launches them (NCHW, fp32, all on `stream`):
+ *   nnd_repvit_depthwise   y (N,C,Ho,Wo) = [GELU](depthwise k x k conv(x; w (C,1,k,k), bias, stride, padding k/2)), k 3 / 5 / 7,
+ *                          stride 1 / 2, Ho = (H - 1) / stride + 1 (PyTorch's output size for padding k/2)
+ *   nnd_repvit_stem        y (N,16,Ho,Wo) = GELU(conv 3x3 (3 -> 16, padding 1)(x; w (16,3,3,3), bias)); samples n >= nsplit read x1
+ *   nnd_repvit_pointwise*  1x1 conv on conv_mfma: y = GELU(conv + bias) (gelu), residual + scale * conv + bias (residual; pack the
+ *                          bias already multiplied by the scale; scale NULL = 1) or conv + bias; pack on the HOST
+ *   nnd_repvit_linear_attention   qkv (N,1+2C,H,W) -> out (N,C,H,W): LinearSelfAttention's core per (sample, row), W <= 4096
+ *   nnd_repvit_upsample_add_relu  y (N,C,H,W) = relu(y + F.interpolate(a (N,C,h,w), (H,W), "bilinear", align_corners=False)) */
+int nnd_repvit_depthwise(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int k, int stride,
+                         int gelu, void* stream);
+int nnd_repvit_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W,
+                    int stride, void* stream);
+int64_t nnd_repvit_pointwise_packed_floats(int Cout, int Cin, int stride);
+int nnd_repvit_pointwise_pack(int Cout, int Cin, int stride, const float* w, const float* bias, const float* scale, float* packed_host);
+int nnd_repvit_pointwise(int Cout, int Cin, int stride, const float* packed_dev, const float* x, const float* residual, float* y, int N,
+                         int H, int W, int gelu, void* stream);
+int nnd_repvit_linear_attention(const float* qkv, float* out, int N, int C, int H, int W, void* stream);
+int nnd_repvit_upsample_add_relu(const float* a, float* y, int N, int C, int h, int w, int H, int W, void* stream);
+
 /* ------------------------------------------------------------- pre- / post-processing on the device
  * nnd_resize_normalize : preprocess_frame  nndepth/models/raft_stereo/scripts/inference.py:55-60
  *     dst (B,C,H,W) = (bilinear_resize(src) - sub) / div, bilinear as F.interpolate(mode="bilinear") (align_corners=False);

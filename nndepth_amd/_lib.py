@@ -46,6 +46,12 @@ class EncoderDesc(_SizedDesc):
                 ("arithmetic", C.c_int32), ("flags", C.c_int32)]
 
 
+class RepViTDesc(_SizedDesc):
+    _fields_ = [("struct_size", C.c_int32), ("stem_strides", C.c_int32 * 3), ("patch_size", C.c_int32),
+                ("down_strides", C.c_int32 * 4), ("channels", C.c_int32 * 4), ("num_blocks", C.c_int32 * 4), ("mixer", C.c_int32 * 4),
+                ("ffn_hidden", C.c_int32 * 4), ("cnet_dim", C.c_int32), ("fusion_dim", C.c_int32 * 2), ("flags", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/nndepth_amd.h one to one
 _P = C.c_void_p
 _I = C.c_int
@@ -113,6 +119,18 @@ SIGNATURES = {
     "nnd_encoder_workspace_floats": (C.c_int64, [C.POINTER(EncoderDesc), _I, _I, _I]),
     "nnd_encoder_pack": (_I, [C.POINTER(EncoderDesc), C.POINTER(_P), C.c_float, _P]),
     "nnd_encoder_forward": (_I, [C.POINTER(EncoderDesc), _P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "nnd_repvit_num_tensors": (_I, [C.POINTER(RepViTDesc)]),
+    "nnd_repvit_packed_floats": (C.c_int64, [C.POINTER(RepViTDesc)]),
+    "nnd_repvit_workspace_floats": (C.c_int64, [C.POINTER(RepViTDesc), _I, _I, _I]),
+    "nnd_repvit_pack": (_I, [C.POINTER(RepViTDesc), C.POINTER(_P), _P]),
+    "nnd_repvit_forward": (_I, [C.POINTER(RepViTDesc), _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_repvit_depthwise": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "nnd_repvit_stem": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nnd_repvit_pointwise_packed_floats": (C.c_int64, [_I, _I, _I]),
+    "nnd_repvit_pointwise_pack": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "nnd_repvit_pointwise": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nnd_repvit_linear_attention": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "nnd_repvit_upsample_add_relu": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_resize_normalize": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_replicate_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_epe_metrics_workspace_bytes": (C.c_int64, []),

@@ -120,7 +120,9 @@ enum ConvEpilogue {
     EPI_SCALE = 4,   // out0 = scale * v
     EPI_AFFINE = 5,  // y = acc * cscale[co] + shift[co] (folded norm; shift in the bias slot); flags bit 0: ReLU;
                      // aux0 (optional): y = aux0 + y; flags bit 1: ReLU          (encoder / residual blocks)
-    EPI_SIGMOID_RANGE = 6  // out0 = scale * (sigmoid(v) - 0.5) * 2    (CREStereo's learned search offsets, cre_stereo/model.py:158-159)
+    EPI_SIGMOID_RANGE = 6,  // out0 = scale * (sigmoid(v) - 0.5) * 2    (CREStereo's learned search offsets, cre_stereo/model.py:158-159)
+    EPI_GELU = 7            // out0 = v * 0.5 * (1 + erf(v / sqrt(2)))   (exact GELU of the RepViT encoder side, repvit.hip); exact fp32
+                            // kernel (arith 0) with a planar destination only: launch_conv refuses it elsewhere
 };
 
 // One convolution layer inside a packed parameter blob.
@@ -168,6 +170,9 @@ struct ConvIO {
     // (fewer per workgroup, same grid rows) where the kernel's staging plan allows it, else the rows that hold none of the wanted
     // blocks; with one row and no such staging plan it runs the whole layer.
     int cout_need = 0;
+    // > 0: split-K factor forced for this launch (the picker then chooses among the shapes with this ks).  ks = 1 keeps every output
+    // the same K order whatever the batch / map size (repvit.hip: a pair's outputs do not depend on the batch it runs in).
+    int force_ks = 0;
 };
 
 // input channels per K-chunk for a layer shape (host packer and kernels must agree)

@@ -460,8 +460,8 @@ struct TileCfg {
 // Cost model: every wave issues unit = ceil(nchunks/ks) * P MFMA streams; waves spread evenly over the 1024
 // SIMDs of the chip, so the busiest SIMD runs ceil(waves/1024) * unit (quantisation is what matters at
 // batch 1: 68x120 = 255 tiles of 4x8 pixels).
-static bool pick_tile(const ConvLayer& L, int c0, int c1, int B, int H, int W, TileCfg* out) {
-    const int force_p = switches().conv_p, force_ks = switches().conv_ks, force_wco = switches().conv_wco;
+static bool pick_tile(const ConvLayer& L, int c0, int c1, int B, int H, int W, TileCfg* out, int io_ks = 0) {
+    const int force_p = switches().conv_p, force_ks = io_ks > 0 ? io_ks : switches().conv_ks, force_wco = switches().conv_wco;
     double best = 1e30;
     bool found = false;
     for (int ks : {1, 2})  // ks = 4 measured slower on every layer (scripts/sweep_conv.py)
@@ -538,7 +538,10 @@ static int launch_shape(const ConvArgs& a, const TileCfg& cfg, dim3 grid, dim3 b
 
 int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W,
                 hipStream_t stream) {
-    if (L.arith != 0) return launch_conv_split(L, blob, io, epi, B, H, W, stream);
+    if (L.arith != 0) {
+        NND_REQUIRE(epi != EPI_GELU, "conv: EPI_GELU is built on the exact fp32 kernel only");
+        return launch_conv_split(L, blob, io, epi, B, H, W, stream);
+    }
     NND_REQUIRE(io.src0.C + io.src1.C == L.Cin, "conv: source channels %d+%d != Cin %d", io.src0.C, io.src1.C, L.Cin);
     NND_REQUIRE(io.src1.C == 0 || io.src0.C % L.CI_T == 0, "conv: first source (%d ch) must be a multiple of %d", io.src0.C, L.CI_T);
     const int Hin = io.Hin > 0 ? io.Hin : H, Win = io.Win > 0 ? io.Win : W;
@@ -547,7 +550,8 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
                 "conv: output %dx%d does not match input %dx%d at stride %d", H, W, Hin, Win, L.stride);
     NND_REQUIRE((long)(L.Cin + 2 * L.CI_T) * tiled_plane(Hin, Win) < (1L << 31), "conv: plane offsets exceed 32 bits");
     TileCfg cfg;
-    NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg), "conv: no tile configuration for %dx%d Cin=%d", L.KH, L.KW, L.Cin);
+    NND_REQUIRE(epi != EPI_GELU || (!io.dst_c4 && !io.out1.ptr && !io.bmap.ptr), "conv: EPI_GELU is built for a planar out0 only");
+    NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg, io.force_ks), "conv: no tile configuration for %dx%d Cin=%d", L.KH, L.KW, L.Cin);
     {   // LDS sizing rule, re-derived independently of pick_tile (DESIGN.md §4 "staging bounds"): two patch buffers of
         // ks*CI_T channels + the spare word that swallows the stores of non-staging threads, and — aliasing them after the
         // last barrier — one 32x32 partial tile per wave for the split-K exchange; every staging thread needs a slot.

@@ -11,19 +11,9 @@
 // All HBM-bound element-wise / reduction kernels.  Compiled with -ffp-contract=off (the bilinear weights follow
 // ATen's compute_source_index_and_lambda step by step).
 #include "common.h"
+#include "bilinear.h"
 
 namespace nnd {
-
-// ATen: area_pixel_compute_source_index (align_corners = false, not cubic) + guard_index_and_lambda
-__device__ __forceinline__ void src_index(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    float real = fmaf(scale, (float)dst + 0.5f, -0.5f);  // ATen's x86 build contracts scale*(dst+0.5)-0.5 into one fma; the
-                                                         // weight is sensitive to that rounding (measured against torch CPU)
-    real = real < 0.f ? 0.f : real;
-    i0 = min((int)floorf(real), in_size - 1);
-    l1 = fminf(fmaxf(real - (float)i0, 0.f), 1.f);
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l0 = 1.f - l1;
-}
 
 // one thread per output pixel, loops the C channels; u8hwc: src is (B,h,w,C) uint8, else (B,C,h,w) float
 __global__ void __launch_bounds__(256) resize_normalize_kernel(const void* __restrict__ src, float* __restrict__ dst, int C, int h,

@@ -12,7 +12,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, NndError, UpdateBlockDesc, check, lib
+from ._lib import (NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, NndError, RepViTDesc, UpdateBlockDesc,
+                   check, lib)
 
 
 def _dev(*tensors: torch.Tensor) -> torch.device:
@@ -921,6 +922,307 @@ class EncoderEngine:
             check(lib.nnd_encoder_forward2(C.byref(self.desc), _p(self.packed), _p(frames), _p(frames_b), nsplit, _p(fmap), _p(cnet), n_cnet,
                                            _p(self._ws), N, H, W, _stream(d)), "encoder_forward")
         return fmap, cnet
+
+
+# ------------------------------------------------------------------------------------------ RepViT encoder side (Coarse2Fine)
+def _d(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to("cpu", torch.float64)
+
+
+def _bn_affine(bn) -> Tuple[torch.Tensor, torch.Tensor]:
+    """eval-mode BatchNorm as y = s * x + t (float64)."""
+    s = _d(bn.weight) / torch.sqrt(_d(bn.running_var) + bn.eps)
+    return s, _d(bn.bias) - _d(bn.running_mean) * s
+
+
+def _fold_conv_bn(branch, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """conv (no bias) + BN -> (weight padded to k x k, bias) (conv.py:298-323, 503-522)."""
+    s, t = _bn_affine(branch.bn)
+    w = _d(branch.conv.weight) * s.reshape(-1, 1, 1, 1)
+    p = (k - w.shape[-1]) // 2
+    return torch.nn.functional.pad(w, [p, p, p, p]), t
+
+
+def _identity_kernel(cin: int, groups: int, k: int) -> torch.Tensor:
+    w = torch.zeros(cin, cin // groups, k, k, dtype=torch.float64)
+    for i in range(cin):
+        w[i, i % (cin // groups), k // 2, k // 2] = 1.0
+    return w
+
+
+def _fold_mobileone(m) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MobileOneBlock's branches (skip BN, 1x1 scale branch, conv branches) -> one conv + bias (conv.py:245-296)."""
+    k, cout = m.kernel_size, m.out_channels
+    w = torch.zeros(cout, m.in_channels // m.groups, k, k, dtype=torch.float64)
+    b = torch.zeros(cout, dtype=torch.float64)
+    if m.rbr_scale is not None:
+        ws, bs = _fold_conv_bn(m.rbr_scale, k)
+        w, b = w + ws, b + bs
+    if m.rbr_skip is not None:
+        s, t = _bn_affine(m.rbr_skip)
+        w, b = w + _identity_kernel(m.in_channels, m.groups, k) * s.reshape(-1, 1, 1, 1), b + t
+    if m.rbr_conv is not None:
+        for br in m.rbr_conv:
+            wc, bc = _fold_conv_bn(br, k)
+            w, b = w + wc, b + bc
+    return w, b
+
+
+def _conv_wb(conv) -> Tuple[torch.Tensor, torch.Tensor]:
+    b = _d(conv.bias) if conv.bias is not None else torch.zeros(conv.out_channels, dtype=torch.float64)
+    return _d(conv.weight), b
+
+
+def _stride1(s, what: str) -> int:
+    """The reference's stride as given — an int or an (sy, sx) pair — as the one stride the HIP path builds (1 or 2), or NndError."""
+    pair = tuple(s) if isinstance(s, (tuple, list)) else (s, s)
+    if len(pair) != 2 or pair[0] != pair[1] or pair[0] not in (1, 2):
+        raise NndError(f"RepViTEngine: {what} stride {s!r} is not built (only (1, 1) and (2, 2))")
+    return int(pair[0])
+
+
+class RepViTEngine:
+    """The encoder side of Coarse2FineGroupRepViTRAFTStereo on the HIP path (csrc/repvit.hip, ONE call: nnd_repvit_forward), packed
+    from the train-time modules of nndepth_amd.rep_vit (or of a reference instance: the same layout).  `fold(...)` turns every block
+    into the plain layer chain the kernels run, in float64 on the host:
+      MobileOneBlock        branches + BatchNorms -> one conv + bias (the skip BN as an identity kernel, the 1x1 scale branch padded)
+      RepLargeKernelConv    the small 3x3 (conv + BN) padded into the large kernel (conv.py:456-469)
+      RepTokenMixer         x + ls * (mixer(x) - norm(x)) -> ONE depthwise 3x3: id + ls * (W_mixer - W_norm), ls * (b_mixer - b_norm)
+                            (rep_vit.py:187-224)
+      AttentionBlock.norm   BatchNorm before the 1x1 qkv_proj: W diag(s), W t + b (exact: no padding between them)
+      layer_scale*          the layer's `scale` (residual + ls * (conv + bias) in the conv epilogue; bias pre-multiplied here)
+      FeatureFusionBlock    the 1x1 conv3 split in its two input halves and composed with conv1 / conv2
+    then casts once to fp32.  Each layer is a dict {kind: stem|dw|pw, w, b, s (scale or None), stride, act: none|gelu|resid}."""
+
+    def __init__(self, desc: RepViTDesc, layers: List[dict], device):
+        self.desc, self.layers = desc, layers
+        n = int(lib.nnd_repvit_num_tensors(C.byref(desc)))
+        if n < 0:
+            check(n, "repvit_num_tensors")
+        if n != 3 * len(layers):
+            raise NndError(f"RepViTEngine: {len(layers)} layers folded, the library expects {n // 3}")
+        host = []
+        for l in layers:
+            host += [l["w"].contiguous(), l["b"].contiguous(), None if l["s"] is None else l["s"].contiguous()]
+        arr = (C.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in host])
+        total = int(lib.nnd_repvit_packed_floats(C.byref(desc)))
+        if total <= 0:
+            check(total, "repvit_packed_floats")
+        blob = torch.empty(total, dtype=torch.float32)
+        check(lib.nnd_repvit_pack(C.byref(desc), arr, _p(blob)), "repvit_pack")
+        self.packed = blob.to(device)
+        self._ws = None
+
+    # ---------------------------------------------------------------- checks
+    @staticmethod
+    def blocker(owner, fnet, cnet_proj, fusion_blocks) -> Optional[str]:
+        """Why the HIP encoder side cannot run these modules, or None."""
+        from .rep_vit import reparam_blocker
+        if owner.training or fnet.training:
+            return "training mode (call model.eval(): BatchNorm is folded with its running statistics)"
+        why = reparam_blocker(fnet, cnet_proj, fusion_blocks)
+        if why:
+            return why + "; reparameterised (inference_mode) checkpoints are not supported"
+        try:
+            RepViTEngine.descriptor(fnet, cnet_proj, fusion_blocks)
+        except NndError as e:
+            return str(e)
+        return None
+
+    @staticmethod
+    def descriptor(fnet, cnet_proj, fusion_blocks) -> RepViTDesc:
+        d = RepViTDesc()
+        for i, m in enumerate(fnet.stem):
+            d.stem_strides[i] = _stride1(m.stride, f"stem.{i}")
+            if getattr(m, "se", None) is not None and not isinstance(m.se, torch.nn.Identity):
+                raise NndError(f"RepViTEngine: stem.{i} has squeeze-excitation (not built)")
+        if fnet.stem[0].in_channels != 3 or fnet.stem[0].out_channels != 16:
+            raise NndError("RepViTEngine: the stem must be 3 -> 16 channels")
+        for i in range(4):
+            stage = getattr(fnet, f"stage_{i}")
+            lk = stage[0].proj[0]
+            if lk.kernel_size % 2 == 0 or lk.kernel_size not in (3, 5, 7):
+                raise NndError(f"RepViTEngine: patch_size {lk.kernel_size} is not built (odd 3, 5 or 7)")
+            if getattr(lk, "small_kernel", None) is not None and (lk.small_kernel % 2 == 0 or lk.small_kernel > lk.kernel_size):
+                raise NndError(f"RepViTEngine: small kernel {lk.small_kernel} is not built")
+            d.patch_size = lk.kernel_size
+            d.down_strides[i] = _stride1(lk.stride, f"stage_{i} patch embed")
+            d.channels[i] = stage[0].proj[1].out_channels
+            blocks = list(stage[1])
+            d.num_blocks[i] = len(blocks)
+            kinds = {type(b).__name__ for b in blocks}
+            if len(kinds) > 1:
+                raise NndError(f"RepViTEngine: stage_{i} mixes block types {sorted(kinds)}")
+            if blocks:
+                b0 = blocks[0]
+                d.mixer[i] = 1 if type(b0).__name__ == "AttentionBlock" else 0
+                ffn = b0.convffn if (d.mixer[i] == 1 or b0.use_ffn) else None
+                d.ffn_hidden[i] = ffn.fc1.out_channels if ffn is not None else 0
+                for b in blocks:
+                    if d.mixer[i] == 0 and (b.use_ffn != bool(d.ffn_hidden[i]) or b.token_mixer.kernel_size != 3):
+                        raise NndError(f"RepViTEngine: stage_{i}'s blocks differ in their FFN / kernel")
+        d.cnet_dim = cnet_proj[0].out_channels
+        d.fusion_dim[0], d.fusion_dim[1] = fusion_blocks[0].conv3.out_channels, fusion_blocks[1].conv3.out_channels
+        want = [(d.channels[3], d.channels[1]), (d.fusion_dim[0], 16)]
+        for j, fb in enumerate(fusion_blocks):
+            if fb.conv3.kernel_size != (1, 1) or fb.conv1.kernel_size != (1, 1) or fb.conv2.kernel_size != (1, 1):
+                raise NndError(f"RepViTEngine: fusion_blocks[{j}] has {fb.conv3.kernel_size} convs (built: kernel_size=1, padding=0)")
+            if (fb.conv1.in_channels, fb.conv2.in_channels) != want[j]:
+                raise NndError(f"RepViTEngine: fusion_blocks[{j}] takes {(fb.conv1.in_channels, fb.conv2.in_channels)} channels, "
+                               f"the backbone gives {want[j]}")
+        for j, (m, cin) in enumerate(zip(cnet_proj, (d.channels[3], d.fusion_dim[0], d.fusion_dim[1]))):
+            if m.kernel_size != 1 or m.in_channels != cin or m.out_channels != d.cnet_dim or not isinstance(m.activation, torch.nn.GELU):
+                raise NndError(f"RepViTEngine: cnet_proj[{j}] is not a 1x1 GELU MobileOneBlock {cin} -> {d.cnet_dim}")
+        if d.fusion_dim[1] != d.fusion_dim[0]:
+            raise NndError("RepViTEngine: cnet_proj[1] and [2] read maps of different widths")
+        n = int(lib.nnd_repvit_num_tensors(C.byref(d)))
+        if n < 0:
+            check(n, "repvit descriptor")
+        return d
+
+    # ---------------------------------------------------------------- host fold
+    @staticmethod
+    def fold(fnet, cnet_proj, fusion_blocks) -> List[dict]:
+        def lay(kind, w, b, stride=1, act="none", s=None):
+            return {"kind": kind, "w": w.float(), "b": b.float(), "s": None if s is None else s.float(), "stride": stride, "act": act}
+
+        def ls_of(t):
+            return _d(t).reshape(-1) if t is not None else None
+
+        def resid(conv, ls):
+            w, b = _conv_wb(conv)
+            if ls is None:
+                ls = torch.ones(w.shape[0], dtype=torch.float64)
+            return lay("pw", w, ls * b, act="resid", s=ls)
+
+        L = []
+        for i, m in enumerate(fnet.stem):
+            w, b = _fold_mobileone(m)
+            L.append(lay("stem" if i == 0 else ("dw" if m.groups > 1 else "pw"), w, b, _stride1(m.stride, "stem"), "gelu"))
+        for i in range(4):
+            stage = getattr(fnet, f"stage_{i}")
+            lk, pw = stage[0].proj
+            w, b = _fold_conv_bn(lk.lkb_origin, lk.kernel_size)
+            if hasattr(lk, "small_conv"):
+                ws, bs = _fold_conv_bn(lk.small_conv, lk.kernel_size)
+                w, b = w + ws, b + bs
+            L.append(lay("dw", w, b, _stride1(lk.stride, "patch embed"), "none"))  # no activation: conv.py:454
+            w, b = _fold_mobileone(pw)
+            L.append(lay("pw", w, b, 1, "gelu"))
+            for blk in stage[1]:
+                if type(blk).__name__ == "AttentionBlock":
+                    s, t = _bn_affine(blk.norm)
+                    wq, bq = _conv_wb(blk.token_mixer.qkv_proj)
+                    L.append(lay("pw", wq * s.reshape(1, -1, 1, 1), bq + wq[:, :, 0, 0] @ t, 1, "none"))
+                    L.append(resid(blk.token_mixer.out_proj, ls_of(getattr(blk, "layer_scale_1", None))))
+                    ffn, ls = blk.convffn, ls_of(getattr(blk, "layer_scale_2", None))
+                else:
+                    tm = blk.token_mixer
+                    wm, bm = _fold_mobileone(tm.mixer)
+                    wn, bn = _fold_mobileone(tm.norm)
+                    lsm = _d(tm.layer_scale).reshape(-1, 1, 1, 1) if tm.use_layer_scale else torch.ones(tm.dim, 1, 1, 1, dtype=torch.float64)
+                    L.append(lay("dw", _identity_kernel(tm.dim, tm.dim, tm.kernel_size) + lsm * (wm - wn), lsm.reshape(-1) * (bm - bn), 1,
+                                 "none"))
+                    ffn = blk.convffn if blk.use_ffn else None
+                    ls = ls_of(getattr(blk, "layer_scale", None)) if ffn is not None and blk.use_layer_scale else None
+                if ffn is not None:
+                    w, b = _conv_wb(ffn.fc1)
+                    L.append(lay("pw", w, b, 1, "gelu"))
+                    L.append(resid(ffn.fc2, ls))
+        for m in cnet_proj:
+            w, b = _fold_mobileone(m)
+            L.append(lay("pw", w, b, 1, "gelu"))
+        for fb in fusion_blocks:
+            w1, b1 = _conv_wb(fb.conv1)
+            w2, b2 = _conv_wb(fb.conv2)
+            w3, b3 = _conv_wb(fb.conv3)
+            c1 = w1.shape[0]
+            w3a, w3b = w3[:, :c1, 0, 0], w3[:, c1:, 0, 0]
+            L.append(lay("pw", (w3a @ w1[:, :, 0, 0])[:, :, None, None], w3a @ b1, 1, "none"))        # coarse half (before the upsample)
+            L.append(lay("pw", (w3b @ w2[:, :, 0, 0])[:, :, None, None], w3b @ b2 + b3, 1, "none"))   # fine half
+        return L
+
+    @staticmethod
+    def fold_forward(layers: List[dict], desc: RepViTDesc, frame1: torch.Tensor, frame2: torch.Tensor):
+        """The folded chain as plain fp32 F.conv2d calls, in the kernels' layer order: the host fold checked without a GPU."""
+        F = torch.nn.functional
+        it = iter(layers)
+
+        def conv(x, l, res=None):
+            w = l["w"].to(x.device)
+            groups = x.shape[1] if l["kind"] == "dw" else 1
+            y = F.conv2d(x, w, l["b"].to(x.device), stride=l["stride"], padding=w.shape[-1] // 2, groups=groups)
+            if l["act"] == "gelu":
+                return F.gelu(y)
+            if l["act"] == "resid":  # residual + ls * (conv + bias): bias was pre-multiplied by ls
+                y = F.conv2d(x, w, None) * l["s"].to(x.device).reshape(1, -1, 1, 1) + l["b"].to(x.device).reshape(1, -1, 1, 1)
+                return res + y
+            return y
+
+        B = frame1.shape[0]
+        x = torch.cat([frame1, frame2], 0)
+        for _ in range(3):
+            x = conv(x, next(it))
+        feats = [x]
+        for i in range(4):
+            x = conv(conv(x, next(it)), next(it))
+            for _ in range(desc.num_blocks[i]):
+                if desc.mixer[i] == 0:
+                    x = conv(x, next(it))
+                else:
+                    qkv = conv(x, next(it))
+                    q, k, v = torch.split(qkv, [1, desc.channels[i], desc.channels[i]], dim=1)
+                    ctx = (k * F.softmax(q, dim=-1)).sum(-1, keepdim=True)
+                    x = conv(F.relu(v) * ctx, next(it), res=x)
+                if desc.ffn_hidden[i] > 0:
+                    x = conv(conv(x, next(it)), next(it), res=x)
+            feats.append(x)
+        cp = [next(it) for _ in range(3)]
+        out = [feats[4]]
+        for coarse_l, fine_l, fine in ((next(it), next(it), feats[2]), (next(it), next(it), feats[0])):
+            a = conv(out[-1], coarse_l)
+            up = F.interpolate(a, size=fine.shape[-2:], mode="bilinear", align_corners=False)
+            out.append(F.relu(conv(fine, fine_l) + up))
+        cnets = [conv(f[:B], l) for f, l in zip(out, cp)]
+        return out, cnets, feats
+
+    @classmethod
+    def from_modules(cls, fnet, cnet_proj, fusion_blocks, device) -> "RepViTEngine":
+        desc = cls.descriptor(fnet, cnet_proj, fusion_blocks)
+        return cls(desc, cls.fold(fnet, cnet_proj, fusion_blocks), device)
+
+    # ---------------------------------------------------------------- forward
+    def forward(self, frame1: torch.Tensor, frame2: torch.Tensor):
+        """(B,3,H,W) x 2 -> (feats, cnets) as Coarse2FineRAFTStereoBase.forward_features: feats[j] (2B, C, h, w) of both frames
+        (left first), cnets[j] (B, cnet_dim, h, w) of the left frames; stage order coarse -> fine."""
+        d = _dev(frame1, frame2, self.packed)
+        frame1, frame2 = frame1.contiguous(), frame2.contiguous()
+        if tuple(frame1.shape) != tuple(frame2.shape) or frame1.dim() != 4 or frame1.shape[1] != 3:
+            raise NndError(f"repvit: frames {tuple(frame1.shape)} / {tuple(frame2.shape)}: expected two (B, 3, H, W) tensors")
+        B, _, H, W = frame1.shape
+        N, ds = 2 * B, self.desc
+
+        def down(n, s):
+            return (n - 1) // s + 1
+
+        h, w = H, W
+        sizes = []
+        for s in list(ds.stem_strides) + list(ds.down_strides):
+            h, w = down(h, s), down(w, s)
+            sizes.append((h, w))
+        stem_hw, s1_hw, s3_hw = sizes[2], sizes[4], sizes[6]
+        f = lambda n, c, hw: torch.empty((n, c) + tuple(hw), dtype=torch.float32, device=d)  # noqa: E731
+        feats = [f(N, ds.channels[3], s3_hw), f(N, ds.fusion_dim[0], s1_hw), f(N, ds.fusion_dim[1], stem_hw)]
+        cnets = [f(B, ds.cnet_dim, s3_hw), f(B, ds.cnet_dim, s1_hw), f(B, ds.cnet_dim, stem_hw)]
+        need = int(lib.nnd_repvit_workspace_floats(C.byref(ds), N, H, W))
+        if need < 0:
+            check(need, "repvit_workspace_floats")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
+            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_repvit_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), B, *[_p(t) for t in feats + cnets],
+                                         _p(self._ws), N, H, W, _stream(d)), "repvit_forward")
+        return feats, cnets
 
 
 def softargmin_disparity(logits: torch.Tensor) -> torch.Tensor:

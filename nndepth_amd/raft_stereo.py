@@ -20,6 +20,7 @@ The classes are inference-only (eval-mode BatchNorm is folded into the convoluti
 `patch(model)` installs the same kernels behind the three duck-typed seams of an *unmodified*
 reference model instance: `corr_fn`, `update_block`, `convex_upsample`.
 """
+import itertools
 from typing import Dict, List, Optional
 
 import torch
@@ -319,28 +320,115 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
         return outs
 
 
-def patch_coarse2fine(model: nn.Module, arithmetic: str = "fp16x2", fused_loop: bool = True, outputs: str = "all") -> nn.Module:
+class RepViTEncoderSide:
+    """The encoder side of Coarse2FineGroupRepViTRAFTStereo — RepViT `fnet`, the three MobileOne `cnet_proj` blocks and the two
+    FeatureFusionBlocks — on HIP: ONE C-ABI call per forward (csrc/repvit.hip: nnd_repvit_forward, exact fp32 whatever the
+    cascade's `arithmetic`), packed by ops.RepViTEngine from the modules' train-time parameters (branches, BatchNorms and layer
+    scales folded on the host in float64) and repacked when a parameter's data_ptr / _version changes."""
+
+    def __init__(self):
+        self.engine, self.version = None, None
+
+    def run(self, owner: nn.Module, fnet, cnet_proj, fusion_blocks, frame1: torch.Tensor, frame2: torch.Tensor):
+        """-> (feats, cnets) exactly as Coarse2FineRAFTStereoBase.forward_features returns them."""
+        if owner.training or fnet.training:
+            raise NndError(f"{type(owner).__name__}: the HIP encoder side is inference-only (BatchNorm is folded with its running "
+                           "statistics): call model.eval() first")
+        # the module walk, the descriptor and the fold run only when a parameter / buffer changed (data_ptr, _version) or one was
+        # added / removed (a reparameterised module registers new ones); otherwise this tuple is the whole per-call check
+        v = (tuple((t.data_ptr(), t._version) for m in (fnet, cnet_proj, fusion_blocks)
+                   for t in itertools.chain(m.parameters(), m.buffers())), str(frame1.device))
+        if v != self.version:
+            why = ops.RepViTEngine.blocker(owner, fnet, cnet_proj, fusion_blocks)
+            if why:
+                raise NndError(f"{type(owner).__name__}: the HIP encoder side cannot run this model ({why}); pass hip_encoder=False "
+                               "to run the encoder side's PyTorch-ROCm modules explicitly")
+            self.engine = ops.RepViTEngine.from_modules(fnet, cnet_proj, fusion_blocks, frame1.device)
+            self.version = v
+        # the two frame tensors are read where they lie: no torch.cat copy (model.py:275)
+        return self.engine.forward(frame1.float(), frame2.float())
+
+
+class Coarse2FineGroupRepViTRAFTStereo(Coarse2FineRAFTStereoBase):
+    """Drop-in for the reference's `Coarse2FineGroupRepViTRAFTStereo` (nndepth/models/raft_stereo/model.py:166-320): its
+    constructor kwargs (= `RepViTRAFTStereoModelConfig`, with corr_levels=1 as the reference asserts), its state_dict keys in its
+    order (fnet, cnet_proj, update_block, fusion_blocks) and `forward(frame1, frame2) -> List[{"up_disp"}]`.
+
+    hip_encoder=True (default): the whole encoder side is ONE HIP call (RepViTEncoderSide), followed by the HIP cascade of
+    Coarse2FineRAFTStereoBase.refine_stages.  A configuration the HIP encoder side does not build raises NndError naming it;
+    hip_encoder=False is the explicit opt-in to the containers' PyTorch-ROCm forward (nndepth_amd.rep_vit)."""
+
+    def __init__(self, num_groups: int = 4, downsample_ratios=((2, 2), (2, 2), (2, 2), (2, 2)), ffn_exp_ratios=(1.0, 3.0, 3.0, 4.0),
+                 num_blocks_per_stage=(4, 4, 6, 2), patch_size: int = 7, stem_strides=((2, 2), (2, 2), (1, 1)),
+                 token_mixer_types=("repmixer", "repmixer", "repmixer", "attention"), use_ffn_per_stage=(False, True, True, True),
+                 width_multipliers=(1, 1, 1, 1), weights: Optional[str] = None, strict_load: bool = True, iters: int = 12,
+                 fnet_dim: int = 256, hidden_dim: int = 128, context_dim: int = 128, corr_levels: int = 1, corr_radius: int = 4,
+                 tracing: bool = False, include_preprocessing: bool = False, hip_encoder: bool = True, arithmetic: str = "fp16x2",
+                 outputs: str = "all", fused_loop: bool = True, **kwargs):
+        self.downsample_ratios, self.ffn_exp_ratios = downsample_ratios, ffn_exp_ratios
+        self.num_blocks_per_stage, self.patch_size, self.stem_strides = num_blocks_per_stage, patch_size, stem_strides
+        self.token_mixer_types, self.use_ffn_per_stage, self.width_multipliers = token_mixer_types, use_ffn_per_stage, width_multipliers
+        self.fnet_dim, self.tracing, self.include_preprocessing = fnet_dim, tracing, include_preprocessing
+        super().__init__(iters=iters, hidden_dim=hidden_dim, context_dim=context_dim, corr_levels=corr_levels, corr_radius=corr_radius,
+                         num_groups=num_groups, weights=None, fused_loop=fused_loop, arithmetic=arithmetic, outputs=outputs)
+        # the reference registers fusion_blocks after update_block (model.py:216-228 run after RAFTStereo.__init__): same order here
+        self._modules["fusion_blocks"] = self._modules.pop("fusion_blocks")
+        self.hip_encoder = hip_encoder
+        self._encoder_side = RepViTEncoderSide()
+        self.weights, self.strict_load = weights, strict_load
+        if weights is not None:
+            load_weights(self, weights, strict_load)
+
+    def _init_fnet(self) -> nn.Module:
+        from .rep_vit import RepViT
+        return RepViT(downsample_ratios=self.downsample_ratios, ffn_exp_ratios=self.ffn_exp_ratios,
+                      num_blocks_per_stage=self.num_blocks_per_stage, patch_size=self.patch_size, stem_strides=self.stem_strides,
+                      token_mixer_types=self.token_mixer_types, use_ffn_per_stage=self.use_ffn_per_stage,
+                      width_multipliers=self.width_multipliers)
+
+    def _init_cnet_proj(self) -> nn.ModuleList:
+        from .rep_vit import MobileOneBlock
+        return nn.ModuleList([MobileOneBlock(c, self.context_dim * 2, kernel_size=1, stride=1, padding=0) for c in (256, 64, 64)])
+
+    def _init_fusion_blocks(self) -> nn.ModuleList:
+        from .rep_vit import FeatureFusionBlock
+        return nn.ModuleList([FeatureFusionBlock(256, 64, 64, 1, 0), FeatureFusionBlock(64, 16, 64, 1, 0)])
+
+    def forward_features(self, frame1: torch.Tensor, frame2: torch.Tensor):
+        if self.hip_encoder:
+            return self._encoder_side.run(self, self.fnet, self.cnet_proj, self.fusion_blocks, frame1, frame2)
+        return super().forward_features(frame1, frame2)  # explicit opt-in (hip_encoder=False): PyTorch-ROCm modules
+
+
+def patch_coarse2fine(model: nn.Module, arithmetic: str = "fp16x2", fused_loop: bool = True, outputs: str = "all",
+                      hip_encoder: bool = False) -> nn.Module:
     """Swap the HIP hot path into a reference `Coarse2FineGroupRepViTRAFTStereo` instance in place: `patch()` for `update_block` and
     `convex_upsample`, `corr_fn` = GroupCorrBlock1D, and `forward` = the reference's encoder side (its own fnet / fusion_blocks /
-    cnet_proj modules) followed by Coarse2FineRAFTStereoBase.refine_stages.  `outputs`: as on Coarse2FineRAFTStereoBase."""
+    cnet_proj modules) followed by Coarse2FineRAFTStereoBase.refine_stages.  `outputs`: as on Coarse2FineRAFTStereoBase.
+    hip_encoder=True: the instance's own fnet / cnet_proj / fusion_blocks are packed and run as the ONE HIP call of the drop-in
+    class (RepViTEncoderSide) instead of their PyTorch modules."""
     model.outputs = check_outputs(outputs)
     patch(model, arithmetic)
     model.corr_fn = GroupCorrBlock1D
     model.convex_upsample = lambda flow, mask, rate=(4, 4): convex_upsample(flow, mask, rate if isinstance(rate, int) else rate[0])
     model.arithmetic, model.fused_loop = arithmetic, fused_loop
     cls = Coarse2FineRAFTStereoBase
+    side = RepViTEncoderSide() if hip_encoder else None
 
     def forward(frame1, frame2, **kwargs):
         require_eval(model)
         with torch.no_grad():
-            feats, cnets = cls.forward_features(model, frame1, frame2)
+            if side is not None:
+                feats, cnets = side.run(model, model.fnet, model.cnet_proj, model.fusion_blocks, frame1, frame2)
+            else:
+                feats, cnets = cls.forward_features(model, frame1, frame2)
             return cls.refine_stages(model, feats, cnets, tuple(frame1.shape[-2:]))
 
     model.forward = forward
     return model
 
 
-STEREO_MODELS = {"base-raft-stereo": BaseRAFTStereo}
+STEREO_MODELS = {"base-raft-stereo": BaseRAFTStereo, "coarse2fine": Coarse2FineGroupRepViTRAFTStereo}
 
 
 def patch(model: nn.Module, arithmetic: str = "fp16x2") -> nn.Module:

@@ -86,3 +86,11 @@ def synthetic_frames(seed: int, batch: int, height: int, width: int) -> Tuple[to
     noise = (uniform01(f"noise{seed}", n).reshape(left.shape) - 0.5) * 0.05
     right = np.clip(right + noise, -1, 1).astype(np.float32)
     return torch.from_numpy(left), torch.from_numpy(right)
+
+
+def sample_index(tag: str, numel: int, n: int) -> np.ndarray:
+    """n distinct flat indices into a tensor of `numel` elements (all of them, sorted, if numel <= n): a pure function of
+    (tag, numel, n), so a fixture can store a large map's values at these indices only and a test can regenerate them."""
+    if numel <= n:
+        return np.arange(numel, dtype=np.int64)
+    return np.sort(np.argsort(uniform01(f"{tag}/{numel}", numel), kind="stable")[:n]).astype(np.int64)
