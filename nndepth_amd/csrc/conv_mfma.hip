@@ -551,7 +551,9 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
     NND_REQUIRE((long)(L.Cin + 2 * L.CI_T) * tiled_plane(Hin, Win) < (1L << 31), "conv: plane offsets exceed 32 bits");
     TileCfg cfg;
     NND_REQUIRE(epi != EPI_GELU || (!io.dst_c4 && !io.out1.ptr && !io.bmap.ptr), "conv: EPI_GELU is built for a planar out0 only");
-    NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg, io.force_ks), "conv: no tile configuration for %dx%d Cin=%d", L.KH, L.KW, L.Cin);
+    NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg, io.force_ks),
+                "conv: no tile configuration for %dx%d Cin=%d Cout=%d stride %d (NND_CONV_CFG p=%d ks=%d wco=%d, layer ks=%d)", L.KH, L.KW,
+                L.Cin, L.Cout, L.stride, switches().conv_p, switches().conv_ks, switches().conv_wco, io.force_ks);
     {   // LDS sizing rule, re-derived independently of pick_tile (DESIGN.md §4 "staging bounds"): two patch buffers of
         // ks*CI_T channels + the spare word that swallows the stores of non-staging threads, and — aliasing them after the
         // last barrier — one 32x32 partial tile per wave for the split-K exchange; every staging thread needs a slot.
@@ -597,6 +599,9 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
         (L.Cin == 64 || L.Cin == 96 || L.Cin == 128) &&
         (epi == EPI_LINEAR || epi == EPI_RELU || epi == EPI_SCALE || epi == EPI_AFFINE)) {
         const int ntiles = cfg.tiles_x * cfg.tiles_y, KQ = L.nchunks * L.CI_T / 8;
+        if (switches().conv_verbose)
+            fprintf(stderr, "[nnd] conv1x1_stream Cin=%d Cout=%d CI_T=%d: grid %ux1x%d%s\n", L.Cin, L.Cout, L.CI_T,
+                    (unsigned)cdiv64((long)L.ncb * ntiles, 4), B, io.dst_c4 ? ", c4 destination" : "");
         if (L.Cin == 64) launch_conv1x1_stream<8>(a, ntiles, L.ncb, KQ, B, stream);
         else if (L.Cin == 96) launch_conv1x1_stream<12>(a, ntiles, L.ncb, KQ, B, stream);
         else launch_conv1x1_stream<16>(a, ntiles, L.ncb, KQ, B, stream);
@@ -630,9 +635,10 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
     dim3 grid(cfg.tiles_x * cfg.tiles_y, ny, B), block(64 * cfg.wco * cfg.ks);
     const bool verbose = switches().conv_verbose;
     if (verbose)
-        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B%s\n",
+        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B%s%s\n",
                 L.KH, L.KW, L.Cin, L.Cout, L.CI_T, cfg.P, cfg.wco, cfg.ks, cfg.ne, grid.x, grid.y, grid.z, cfg.lds,
-                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "");
+                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
+                L.stride == 2 ? ", stride 2" : "");
     int rc = NND_ERR_UNSUPPORTED;
     if (L.stride == 2) {
         if (L.KH == 3 && L.KW == 3 && L.CI_T == 16) rc = launch_one<3, 3, 16, 1, 16, 2>(a, grid, block, cfg.lds, stream);

@@ -225,8 +225,10 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
     // sources.  NND_SPLIT_NO_FAST (diagnostic) keeps the generic kernel.
     // (the stride-2 kernels exist in the FAST regime only: the diagnostic switch does not apply to them)
     const bool fast_ok = !switches().split_no_fast || L.stride == 2;
-    NND_REQUIRE(pick_split(L, io.src0.C, io.src1.C, B, H, W, fast_ok, &cfg), "conv_split: no configuration for %dx%d Cin=%d (%d+%d)", L.KH,
-                L.KW, L.Cin, io.src0.C, io.src1.C);
+    NND_REQUIRE(pick_split(L, io.src0.C, io.src1.C, B, H, W, fast_ok, &cfg),
+                "conv_split: no configuration for %dx%d Cin=%d (%d+%d) Cout=%d stride %d (NND_SPLIT_CFG ny=%d ks=%d P=%d%s)", L.KH, L.KW,
+                L.Cin, io.src0.C, io.src1.C, L.Cout, L.stride, switches().split_ny, switches().split_ks, switches().split_p,
+                fast_ok ? "" : ", NND_SPLIT_NO_FAST");
     const bool restricted = restrict_split(L, io.cout_need, &cfg);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -266,9 +268,10 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
     dim3 grid(cdiv(cfg.ntiles, cfg.P), cfg.ny, B), block(64 * cfg.wco * cfg.ks);
     const bool verbose = switches().conv_verbose;
     if (verbose)
-        fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B%s\n", L.KH,
+        fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B%s%s\n", L.KH,
                 L.KW, L.Cin, L.Cout, L.arith, cfg.ny, cfg.wco, cfg.ks, cfg.P, cfg.nu, cfg.fast ? ", fast" : "", grid.x, grid.y, grid.z, cfg.lds,
-                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "");
+                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
+                L.stride == 2 ? ", stride 2" : "");
     int rc = L.arith == 3 ? launch_split_ns<3>(a, cfg, L.KH, L.KW, grid, block, stream)
                           : launch_split_ns<2>(a, cfg, L.KH, L.KW, grid, block, stream);
     NND_REQUIRE(rc != NND_ERR_UNSUPPORTED, "conv_split: shape %dx%d P=%d nu=%d %s is not instantiated", L.KH, L.KW, cfg.P, cfg.nu,

@@ -8,16 +8,33 @@ from conftest import t
 from oracle import torch_ref as R
 
 
+def _last_bits(got, exp, rel):
+    """|got - exp| <= rel * max(1, |exp| max), with the worst element and the count of non-identical ones in the message.
+    The oracle's fp32 GEMMs and convolutions run on the CPU's BLAS / oneDNN kernels, whose summation order (hence last bits) follows
+    the thread count and the instruction set: the goldens are bit-identical in the container that made them (8 or more threads,
+    AVX-512), not on every machine.  rel is a few times the drift those kernels show across thread counts and instruction sets;
+    an error of semantics (a scale, a tap, a pooling step, an iteration) is orders of magnitude above it."""
+    got, exp = np.asarray(got, dtype=np.float64), np.asarray(exp, dtype=np.float64)
+    assert got.shape == exp.shape, (got.shape, exp.shape)
+    d = np.abs(got - exp)
+    bar = rel * max(1.0, float(np.abs(exp).max()))
+    assert d.max() <= bar, f"max-abs {d.max():.3e} > {bar:.3e} ({int((d > 0).sum())} of {d.size} elements differ)"
+
+
 @pytest.mark.parametrize("name", ["c16_w21", "c256_w40", "c32_w39"])
 def test_corr1d_build_and_lookup(gold, name):
     g = gold("corr1d.npz")
     f1, f2, coords = (t(g[f"{name}_{k}"]) for k in ("f1", "f2", "coords"))
     pyr = R.corr1d_build(f1, f2, 4)
     assert len(pyr) == 5  # one level more than is ever read (SURVEY Q1)
+    # (the level-0 matmul's last bits follow the BLAS kernel: up to 7.7e-7 measured with MKL's AVX2 path, |corr| <= 1.4)
     for i, p in enumerate(pyr):
-        assert np.array_equal(p[:, 0].numpy(), g[f"{name}_pyr{i}"]), f"level {i}"
+        _last_bits(p[:, 0].numpy(), g[f"{name}_pyr{i}"], 4e-6)
     out = R.corr1d_lookup(pyr, coords, 4, 4)
-    assert np.array_equal(out.numpy(), g[f"{name}_out"])
+    _last_bits(out.numpy(), g[f"{name}_out"], 4e-6)
+    # the lookup itself is elementwise: on the golden pyramid it reproduces the golden output bit for bit on any machine
+    gpyr = [t(g[f"{name}_pyr{i}"])[:, None] for i in range(5)]
+    assert np.array_equal(R.corr1d_lookup(gpyr, coords, 4, 4).numpy(), g[f"{name}_out"])
 
 
 def test_linear_sampler_border_clamp():
@@ -225,5 +242,7 @@ def test_coarse2fine_cascade(gold, name):
     cnets = [t(g[f"{name}_cnet{i}"]) for i in range(3)]
     ups = R.coarse2fine_refine(sd, feats, cnets, (Hf, Wf), iters)
     assert len(ups) == 3 * iters
+    # bit-identical with 8 or more CPU threads on AVX-512; with fewer threads oneDNN's convolutions round differently and the
+    # cascade carries that on (x 4 per stage): up to 6.8e-6 measured on the last output (1 - 7 threads, AVX2 kernels)
     for i, u in enumerate(ups):
-        assert np.array_equal(u.numpy(), g[name + "_ups"][i]), i
+        _last_bits(u.numpy(), g[name + "_ups"][i], 3e-5)
