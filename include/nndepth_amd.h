@@ -415,6 +415,59 @@ int nnd_repvit_pointwise(int Cout, int Cin, int stride, const float* packed_dev,
 int nnd_repvit_linear_attention(const float* qkv, float* out, int N, int C, int H, int W, void* stream);
 int nnd_repvit_upsample_add_relu(const float* a, float* y, int N, int C, int h, int w, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------- MobileNetV3 encoder side (IGEVStereoMBNet)
+ * Replaces IGEVStereoMBNet.forward_fnet  nndepth/models/igev_stereo/model.py:163-203: MobilenetV3LargeEncoder
+ * (nndepth/encoders/mobilenetv3_encoder.py) over timm's tf_mobilenetv3_large_100(features_only=True) (stages 0..5; TF "same"
+ * padding, BatchNorm eps 1e-3), fnet_proj / cnet_proj (Conv2d(24 -> fnet_dim / cnet_dim, 3, padding 1) + ReLU) and the guide split.
+ * Exact fp32 (no split arithmetic, no calibration).  The backbone's layout is fixed; the descriptor carries the projections' widths.
+ * nnd_mbv3_pack (HOST): `tensors` = nnd_mbv3_num_tensors(desc) pointers, 2 per layer {weight, bias}, every BatchNorm already folded
+ * (ops.MobileNetV3Engine, float64 on the host), in the layer order:
+ *   conv_stem (16,3,3,3) | per block of stages 0..5: [InvertedResidual: conv_pw (mid,cin,1,1)] conv_dw (mid,1,k,k)
+ *   [SE: conv_reduce (rd,mid,1,1), conv_expand (mid,rd,1,1)] conv_pwl / conv_pw (cout,mid,1,1) | fnet_proj (fnet_dim,24,3,3) |
+ *   cnet_proj (cnet_dim,24,3,3)
+ * nnd_mbv3_forward: frame1, frame2 (B,3,H,W) where they lie -> fmap1, fmap2 (B,fnet_dim,H/4,W/4), cnet1 (B,cnet_dim,H/4,W/4) and
+ *   the left frames' guides guide0 (B,40,H/8,W/8), guide1 (B,80,H/16,W/16), guide2 (B,160,H/32,W/32); every stride-2 step maps n to
+ *   ceil(n / 2).  workspace: nnd_mbv3_workspace_floats(desc, B, H, W) floats, caller-owned.  All launches on `stream`.        */
+typedef struct nnd_mbv3_desc {
+    int32_t struct_size; /* sizeof(nnd_mbv3_desc) */
+    int32_t fnet_dim;    /* fnet_proj output channels (2 * hidden_dim) */
+    int32_t cnet_dim;    /* cnet_proj output channels (2 * context_dim) */
+    int32_t flags;       /* 0 */
+} nnd_mbv3_desc;
+int nnd_mbv3_num_tensors(const nnd_mbv3_desc* desc);
+int64_t nnd_mbv3_packed_floats(const nnd_mbv3_desc* desc);
+int64_t nnd_mbv3_workspace_floats(const nnd_mbv3_desc* desc, int B, int H, int W);
+int nnd_mbv3_pack(const nnd_mbv3_desc* desc, const float* const* tensors_host, float* packed_host);
+int nnd_mbv3_forward(const nnd_mbv3_desc* desc, const float* packed_dev, const float* frame1, const float* frame2, float* fmap1,
+                     float* fmap2, float* cnet1, float* guide0, float* guide1, float* guide2, float* workspace, int B, int H, int W,
+                     void* stream);
+
+/* The encoder side's kernels one at a time, as nnd_mbv3_forward launches them (NCHW, fp32, all on `stream`); act: 0 none, 1 ReLU,
+ * 2 hard-swish:
+ *   nnd_mbv3_depthwise   y (N,C,Ho,Wo) = act(depthwise k x k conv(x; w (C,1,k,k), bias, stride, TF same padding)), k 3 / 5,
+ *                        stride 1 / 2, Ho = ceil(H / stride); partial (optional, nnd_mbv3_se_partials(N,C,Ho,Wo) doubles): the
+ *                        per-workgroup sums of y that nnd_mbv3_se reads
+ *   nnd_mbv3_se          gate (N,C) = hardsigmoid(conv_expand(relu(conv_reduce(mean_hw(y))))) from the partials; y *= gate in place
+ *                        (wr (rd,C), br (rd), we (C,rd), be (C); C <= 1024, rd <= 256)
+ *   nnd_mbv3_stem        y (N,16,ceil(H/2),ceil(W/2)) = hardswish(conv 3x3 stride 2, TF same padding (3 -> 16)(x; w, bias));
+ *                        samples n >= nsplit read x1
+ *   nnd_mbv3_pointwise*  k x k (1 or 3, padding k / 2) stride-1 conv on conv_mfma: y = act(conv + bias), or residual + conv + bias;
+ *                        pack on the HOST
+ *   nnd_mbv3_proj        fnet_proj / cnet_proj: y (N,Cout,H,W) = relu(conv 3x3, padding 1 (x (N,Cin,H,W); w (Cout,Cin,3,3), bias)),
+ *                        Cin <= 64 (VALU, per input channel one fp32 9-tap chain, the channels summed in float64)           */
+int nnd_mbv3_depthwise(const float* x, const float* w, const float* bias, float* y, double* partial, int N, int C, int H, int W, int k,
+                       int stride, int act, void* stream);
+int64_t nnd_mbv3_se_partials(int N, int C, int H, int W);
+int nnd_mbv3_se(float* y, const double* partial, const float* wr, const float* br, const float* we, const float* be, float* gate, int N,
+                int C, int rd, int H, int W, void* stream);
+int nnd_mbv3_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W,
+                  void* stream);
+int64_t nnd_mbv3_pointwise_packed_floats(int Cout, int Cin, int k);
+int nnd_mbv3_pointwise_pack(int Cout, int Cin, int k, const float* w, const float* bias, float* packed_host);
+int nnd_mbv3_proj(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int H, int W, void* stream);
+int nnd_mbv3_pointwise(int Cout, int Cin, int k, const float* packed_dev, const float* x, const float* residual, float* y, int N, int H,
+                       int W, int act, void* stream);
+
 /* ------------------------------------------------------------- pre- / post-processing on the device
  * nnd_resize_normalize : preprocess_frame  nndepth/models/raft_stereo/scripts/inference.py:55-60
  *     dst (B,C,H,W) = (bilinear_resize(src) - sub) / div, bilinear as F.interpolate(mode="bilinear") (align_corners=False);

@@ -52,6 +52,10 @@ class RepViTDesc(_SizedDesc):
                 ("ffn_hidden", C.c_int32 * 4), ("cnet_dim", C.c_int32), ("fusion_dim", C.c_int32 * 2), ("flags", C.c_int32)]
 
 
+class MobileNetV3Desc(_SizedDesc):
+    _fields_ = [("struct_size", C.c_int32), ("fnet_dim", C.c_int32), ("cnet_dim", C.c_int32), ("flags", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/nndepth_amd.h one to one
 _P = C.c_void_p
 _I = C.c_int
@@ -131,6 +135,19 @@ SIGNATURES = {
     "nnd_repvit_pointwise": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nnd_repvit_linear_attention": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "nnd_repvit_upsample_add_relu": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "nnd_mbv3_num_tensors": (_I, [C.POINTER(MobileNetV3Desc)]),
+    "nnd_mbv3_packed_floats": (C.c_int64, [C.POINTER(MobileNetV3Desc)]),
+    "nnd_mbv3_workspace_floats": (C.c_int64, [C.POINTER(MobileNetV3Desc), _I, _I, _I]),
+    "nnd_mbv3_pack": (_I, [C.POINTER(MobileNetV3Desc), C.POINTER(_P), _P]),
+    "nnd_mbv3_forward": (_I, [C.POINTER(MobileNetV3Desc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_mbv3_depthwise": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "nnd_mbv3_se_partials": (C.c_int64, [_I, _I, _I, _I]),
+    "nnd_mbv3_se": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "nnd_mbv3_stem": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_mbv3_proj": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "nnd_mbv3_pointwise_packed_floats": (C.c_int64, [_I, _I, _I]),
+    "nnd_mbv3_pointwise_pack": (_I, [_I, _I, _I, _P, _P, _P]),
+    "nnd_mbv3_pointwise": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nnd_resize_normalize": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_replicate_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_epe_metrics_workspace_bytes": (C.c_int64, []),

@@ -121,8 +121,10 @@ enum ConvEpilogue {
     EPI_AFFINE = 5,  // y = acc * cscale[co] + shift[co] (folded norm; shift in the bias slot); flags bit 0: ReLU;
                      // aux0 (optional): y = aux0 + y; flags bit 1: ReLU          (encoder / residual blocks)
     EPI_SIGMOID_RANGE = 6,  // out0 = scale * (sigmoid(v) - 0.5) * 2    (CREStereo's learned search offsets, cre_stereo/model.py:158-159)
-    EPI_GELU = 7            // out0 = v * 0.5 * (1 + erf(v / sqrt(2)))   (exact GELU of the RepViT encoder side, repvit.hip); exact fp32
+    EPI_GELU = 7,           // out0 = v * 0.5 * (1 + erf(v / sqrt(2)))   (exact GELU of the RepViT encoder side, repvit.hip); exact fp32
                             // kernel (arith 0) with a planar destination only: launch_conv refuses it elsewhere
+    EPI_HSWISH = 8          // out0 = v * min(max(v + 3, 0), 6) / 6   (torch's hardswish, MobileNetV3 encoder side, mbv3.hip); exact fp32
+                            // kernel with a planar destination only, as EPI_GELU
 };
 
 // One convolution layer inside a packed parameter blob.

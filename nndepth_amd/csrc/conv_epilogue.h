@@ -135,6 +135,8 @@ __device__ __forceinline__ void conv_epilogue_planar(const ConvArgs& a, const f3
                 a.out0[b * a.obs0 + co * DP + pix] = a.scale * (sigmoidf_(v) - 0.5f) * 2.0f;
             } else if (epi == EPI_GELU) {  // torch's exact GELU: x * 0.5 * (1 + erf(x * M_SQRT1_2))
                 a.out0[b * a.obs0 + co * DP + pix] = v * 0.5f * (1.0f + erff(v * 0.707106781186547524f));
+            } else if (epi == EPI_HSWISH) {  // torch's hardswish: x * min(max(x + 3, 0), 6) / 6
+                a.out0[b * a.obs0 + co * DP + pix] = v * fminf(fmaxf(v + 3.0f, 0.0f), 6.0f) / 6.0f;
             } else if (epi == EPI_AFFINE) {  // folded norm: y = acc*scale + shift; optional ReLU, residual add, ReLU
                 float y2 = fmaf(acc[pp][reg], z_r[reg], bias_r[reg]);
                 if (a.flags & 4) y2 = y2 > 0.f ? y2 : a.scale * y2;  // LeakyReLU (slope in `scale`), Conv3d path

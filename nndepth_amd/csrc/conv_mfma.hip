@@ -539,7 +539,7 @@ static int launch_shape(const ConvArgs& a, const TileCfg& cfg, dim3 grid, dim3 b
 int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W,
                 hipStream_t stream) {
     if (L.arith != 0) {
-        NND_REQUIRE(epi != EPI_GELU, "conv: EPI_GELU is built on the exact fp32 kernel only");
+        NND_REQUIRE(epi != EPI_GELU && epi != EPI_HSWISH, "conv: EPI_GELU / EPI_HSWISH are built on the exact fp32 kernel only");
         return launch_conv_split(L, blob, io, epi, B, H, W, stream);
     }
     NND_REQUIRE(io.src0.C + io.src1.C == L.Cin, "conv: source channels %d+%d != Cin %d", io.src0.C, io.src1.C, L.Cin);
@@ -550,7 +550,8 @@ int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi
                 "conv: output %dx%d does not match input %dx%d at stride %d", H, W, Hin, Win, L.stride);
     NND_REQUIRE((long)(L.Cin + 2 * L.CI_T) * tiled_plane(Hin, Win) < (1L << 31), "conv: plane offsets exceed 32 bits");
     TileCfg cfg;
-    NND_REQUIRE(epi != EPI_GELU || (!io.dst_c4 && !io.out1.ptr && !io.bmap.ptr), "conv: EPI_GELU is built for a planar out0 only");
+    NND_REQUIRE((epi != EPI_GELU && epi != EPI_HSWISH) || (!io.dst_c4 && !io.out1.ptr && !io.bmap.ptr),
+                "conv: EPI_GELU / EPI_HSWISH are built for a planar out0 only");
     NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg, io.force_ks),
                 "conv: no tile configuration for %dx%d Cin=%d Cout=%d stride %d (NND_CONV_CFG p=%d ks=%d wco=%d, layer ks=%d)", L.KH, L.KW,
                 L.Cin, L.Cout, L.stride, switches().conv_p, switches().conv_ks, switches().conv_wco, io.force_ks);

@@ -4,7 +4,8 @@
 `forward(frame1, frame2) -> List[{"up_disp": (B,1,H,W)}]` of nndepth/models/igev_stereo/model.py:15-158, including its
 two hooks for subclasses (`_init_fnet`, `_init_cost_volume_filter`, `forward_fnet`).  Inside `forward()`:
 
-    backbone (`forward_fnet`)                       whatever the subclass provides (PyTorch)
+    backbone (`forward_fnet`)                       IGEVStereoMBNet: HIP, ONE C-ABI call nnd_mbv3_forward (csrc/mbv3.hip:
+                                                    MobileNetV3 + fnet_proj / cnet_proj); other subclasses: their own
     group-wise correlation volume + pyramids        HIP  csrc/corr1d.hip (GeometryAwareCostVolume)     model.py:133-141
     3-D regulariser (Conv3d hourglass)              HIP  csrc/conv3d.hip: every Conv3d+BN+LeakyReLU one MFMA-conv launch on
                                                     depth-major volumes, trilinear x2 and feature gating kernels
@@ -13,9 +14,10 @@ two hooks for subclasses (`_init_fnet`, `_init_cost_volume_filter`, `forward_fne
     for iters: combined lookup -> update block -> coords += delta -> convex upsample (absolute coords, Q5)
                                                     HIP, ONE C-ABI call: nnd_igev_stereo_refine          model.py:152-158
 
-`IGEVStereoMBNet` (MobileNetV3 backbone from timm) is declared for interface parity; timm is an external dependency of
-the reference that is not part of this repository.
+`IGEVStereoMBNet` is the reference's only concrete model (its STEREO_MODELS["igev_stereo_mbnet"]), built on the timm-free
+MobileNetV3-Large containers of nndepth_amd.mobilenetv3.
 """
+import itertools
 from typing import Dict, List, Optional
 
 import torch
@@ -259,46 +261,74 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
         return outs
 
 
-class IGEVStereoMBNet(IGEVStereoBase):
-    """IGEV-Stereo with the timm MobileNetV3-Large backbone (nndepth/models/igev_stereo/model.py:163-203)."""
+class MobileNetV3EncoderSide:
+    """The encoder side of IGEVStereoMBNet — MobileNetV3 `fnet`, `fnet_proj`, `cnet_proj` and the guide split — on HIP: ONE C-ABI
+    call per forward (csrc/mbv3.hip: nnd_mbv3_forward, exact fp32 whatever the model's `arithmetic`), packed by
+    ops.MobileNetV3Engine from the modules' parameters (BatchNorms folded on the host in float64) and repacked when a parameter's
+    data_ptr / _version changes."""
 
-    def __init__(self, **kwargs):
+    def __init__(self):
+        self.engine, self.version = None, None
+
+    def run(self, owner: nn.Module, fnet, fnet_proj, cnet_proj, frame1: torch.Tensor, frame2: torch.Tensor):
+        """-> (fmap1, fmap2, cnet1, [guide 1/8, guide 1/16, guide 1/32]) exactly as IGEVStereoMBNet.forward_fnet returns them."""
+        if owner.training or fnet.training:
+            raise NndError(f"{type(owner).__name__}: the HIP encoder side is inference-only (BatchNorm is folded with its running "
+                           "statistics): call model.eval() first")
+        # the module walk, the descriptor and the fold run only when a parameter / buffer changed (data_ptr, _version) or one was
+        # added / removed; otherwise this tuple is the whole per-call check
+        v = (tuple((t.data_ptr(), t._version) for m in (fnet, fnet_proj, cnet_proj)
+                   for t in itertools.chain(m.parameters(), m.buffers())), tuple(id(m) for m in fnet.modules()), str(frame1.device))
+        if v != self.version:
+            why = ops.MobileNetV3Engine.blocker(owner, fnet, fnet_proj, cnet_proj)
+            if why:
+                raise NndError(f"{type(owner).__name__}: the HIP encoder side cannot run this model ({why}); pass hip_encoder=False "
+                               "to run the encoder side's PyTorch-ROCm modules explicitly")
+            self.engine = ops.MobileNetV3Engine.from_modules(fnet, fnet_proj, cnet_proj, frame1.device)
+            self.version = v
+        # the two frame tensors are read where they lie: no torch.cat copy (model.py:191)
+        return self.engine.forward(frame1.float(), frame2.float())
+
+
+class IGEVStereoMBNet(IGEVStereoBase):
+    """Drop-in for the reference's `IGEVStereoMBNet` (nndepth/models/igev_stereo/model.py:163-203): its constructor kwargs, its
+    state_dict keys in its order (fnet.backbone.* as timm 1.0.16's tf_mobilenetv3_large_100(features_only=True) names them,
+    update_block, cv_regularizer, cv_squeezer, fnet_proj, cnet_proj) and `forward(frame1, frame2) -> List[{"up_disp"}]`.
+
+    The backbone is nndepth_amd.mobilenetv3's timm-free containers.  Nothing is downloaded: the reference's ImageNet initialisation
+    (`pretrained=True` in its MobilenetV3LargeEncoder) is not reproduced, so trained parameters come only through `weights=` (a
+    reference checkpoint loads with strict=True) or load_state_dict.
+
+    hip_encoder=True (default): the whole encoder side is ONE HIP call (MobileNetV3EncoderSide); a module the HIP encoder side does
+    not build (training mode, a replaced block) raises NndError naming it.  hip_encoder=False is the explicit opt-in to the
+    containers' PyTorch-ROCm forward.  `arithmetic`, `outputs`, `fused_loop`: as on IGEVStereoBase (the encoder side stays exact
+    fp32)."""
+
+    def __init__(self, hip_encoder: bool = True, **kwargs):
         super().__init__(**kwargs)
         self.fnet_proj = nn.Sequential(nn.Conv2d(24, self.hidden_dim * 2, 3, 1, 1), nn.ReLU(False))
         self.cnet_proj = nn.Sequential(nn.Conv2d(24, self.context_dim * 2, 3, 1, 1), nn.ReLU(False))
+        self.hip_encoder = hip_encoder
+        self._encoder_side = MobileNetV3EncoderSide()
         if self.weights is not None:
             load_weights(self, self.weights, self.strict_load)
 
     def _init_fnet(self):
-        try:
-            from timm.models.mobilenetv3 import tf_mobilenetv3_large_100
-        except ImportError as e:  # the reference pins timm==1.0.16 (docker/requirements.txt); not vendored here
-            raise ImportError("IGEVStereoMBNet needs timm's tf_mobilenetv3_large_100 backbone") from e
-
-        class _MobilenetV3LargeEncoder(nn.Module):  # nndepth/encoders/mobilenetv3_encoder.py: stages 1-5 are hooked
-            def __init__(self):
-                super().__init__()
-                self.backbone = tf_mobilenetv3_large_100(pretrained=True, features_only=True)
-
-            def forward(self, x):
-                bb = self.backbone
-                x = bb.act1(bb.bn1(bb.conv_stem(x)))
-                feats = []
-                for i, blk in enumerate(bb.blocks):
-                    x = blk(x)
-                    if i in (1, 2, 3, 4, 5):
-                        feats.append(x)
-                return feats
-
-        return _MobilenetV3LargeEncoder()
+        from .mobilenetv3 import MobilenetV3LargeEncoder
+        return MobilenetV3LargeEncoder(feature_hooks=[1, 2, 3, 4, 5])
 
     def _init_cost_volume_filter(self):
         return CostVolumeFilterNetwork(self.cv_groups, [40, 80, 160])
 
     def forward_fnet(self, frame1: torch.Tensor, frame2: torch.Tensor):
-        B = frame1.shape[0]
+        if self.hip_encoder:
+            return self._encoder_side.run(self, self.fnet, self.fnet_proj, self.cnet_proj, frame1, frame2)
+        B = frame1.shape[0]  # explicit opt-in (hip_encoder=False): the containers' PyTorch-ROCm forward
         feats = self.fnet(torch.cat([frame1, frame2], dim=0))
         fmaps = feats[0]
         cnet1 = self.cnet_proj(fmaps[:B].clone())
         fmap1, fmap2 = torch.split(self.fnet_proj(fmaps), B, dim=0)
         return fmap1, fmap2, cnet1, [feats[i][:B] for i in (1, 2, 4)]
+
+
+STEREO_MODELS = {"igev_stereo_mbnet": IGEVStereoMBNet}

@@ -12,7 +12,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import (NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, NndError, RepViTDesc, UpdateBlockDesc,
+from ._lib import (NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, MobileNetV3Desc, NndError, RepViTDesc,
+                   UpdateBlockDesc,
                    check, lib)
 
 
@@ -1223,6 +1224,202 @@ class RepViTEngine:
             check(lib.nnd_repvit_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), B, *[_p(t) for t in feats + cnets],
                                          _p(self._ws), N, H, W, _stream(d)), "repvit_forward")
         return feats, cnets
+
+
+# ------------------------------------------------------------------------------------------ MobileNetV3 encoder side (IGEVStereoMBNet)
+_MBV3_LAYOUT = None
+
+
+def _mbv3_layout() -> List[Tuple[str, Tuple[int, ...]]]:
+    """(key, shape) of MobilenetV3LargeEncoder's state_dict, built once on the meta device."""
+    global _MBV3_LAYOUT
+    if _MBV3_LAYOUT is None:
+        from .mobilenetv3 import MobilenetV3LargeEncoder
+        with torch.device("meta"):
+            ref = MobilenetV3LargeEncoder()
+        _MBV3_LAYOUT = [(k, tuple(v.shape)) for k, v in ref.state_dict().items()]
+    return _MBV3_LAYOUT
+
+
+class MobileNetV3Engine:
+    """The encoder side of IGEVStereoMBNet on the HIP path (csrc/mbv3.hip, ONE call: nnd_mbv3_forward), packed from the modules of
+    nndepth_amd.mobilenetv3 plus fnet_proj / cnet_proj.  `fold(...)` folds every eval-mode BatchNorm into its conv in float64 on the
+    host (W * s, t with s = gamma / sqrt(var + eps), t = beta - mean * s); the SE convs and the projections keep their own biases.
+    The layers are cast once to fp32 when packed.  Each layer is a dict {kind: stem|dw|pw|se_r|se_e|proj, w, b (float64), k,
+    stride, act: none|relu|hswish, skip}."""
+
+    def __init__(self, desc: MobileNetV3Desc, layers: List[dict], device):
+        self.desc, self.layers = desc, layers
+        n = int(lib.nnd_mbv3_num_tensors(C.byref(desc)))
+        if n < 0:
+            check(n, "mbv3_num_tensors")
+        if n != 2 * len(layers):
+            raise NndError(f"MobileNetV3Engine: {len(layers)} layers folded, the library expects {n // 2}")
+        host = []
+        for l in layers:
+            host += [l["w"].float().contiguous(), l["b"].float().contiguous()]
+        arr = (C.c_void_p * n)(*[t.data_ptr() for t in host])
+        total = int(lib.nnd_mbv3_packed_floats(C.byref(desc)))
+        if total <= 0:
+            check(total, "mbv3_packed_floats")
+        blob = torch.empty(total, dtype=torch.float32)
+        check(lib.nnd_mbv3_pack(C.byref(desc), arr, _p(blob)), "mbv3_pack")
+        self.packed = blob.to(device)
+        self._ws = None
+
+    # ---------------------------------------------------------------- checks
+    @staticmethod
+    def blocker(owner, fnet, fnet_proj, cnet_proj) -> Optional[str]:
+        """Why the HIP encoder side cannot run these modules, or None."""
+        if owner.training or fnet.training:
+            return "training mode (call model.eval(): BatchNorm is folded with its running statistics)"
+        try:
+            MobileNetV3Engine.descriptor(fnet, fnet_proj, cnet_proj)
+        except NndError as e:
+            return str(e)
+        return None
+
+    @staticmethod
+    def descriptor(fnet, fnet_proj, cnet_proj) -> MobileNetV3Desc:
+        from . import mobilenetv3 as mb
+        if not isinstance(fnet, mb.MobilenetV3LargeEncoder) or not isinstance(getattr(fnet, "backbone", None), mb.MobileNetV3Features):
+            raise NndError(f"MobileNetV3Engine: fnet is a {type(fnet).__name__}, not nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder")
+        got = [(k, tuple(v.shape)) for k, v in fnet.state_dict().items()]
+        want = _mbv3_layout()
+        if got != want:
+            bad = next((w for g, w in zip(got, want) if g != w), want[len(got)] if len(got) < len(want) else got[len(want)])
+            raise NndError(f"MobileNetV3Engine: fnet's parameters differ from tf_mobilenetv3_large_100's layout (first difference at "
+                           f"{bad[0]}); a replaced or reshaped block is not built")
+        if sorted(fnet.feature_hooks) != list(mb.HOOKS):
+            raise NndError(f"MobileNetV3Engine: feature_hooks {fnet.feature_hooks} (built: {list(mb.HOOKS)})")
+        cls = {"ds": mb.DepthwiseSeparable, "ir": mb.InvertedResidual, "cn": mb.ConvBnAct}
+        for i, (stage, specs) in enumerate(zip(fnet.backbone.blocks, mb.block_table())):
+            for j, (blk, spec) in enumerate(zip(stage, specs)):
+                if type(blk) is not cls[spec["type"]] or blk.spec != spec:
+                    raise NndError(f"MobileNetV3Engine: blocks.{i}.{j} is a {type(blk).__name__} {getattr(blk, 'spec', '')}, "
+                                   f"not the {cls[spec['type']].__name__} {spec} of the backbone")
+                for conv in (m for m in blk.modules() if isinstance(m, torch.nn.Conv2d)):
+                    k = conv.kernel_size[0]
+                    if conv.dilation != (1, 1) or (type(conv) is torch.nn.Conv2d and conv.padding != (0, 0)) or \
+                            (conv.groups != 1 and conv.groups != conv.in_channels):
+                        raise NndError(f"MobileNetV3Engine: blocks.{i}.{j} has a {k}x{k} conv with dilation {conv.dilation}, "
+                                       f"padding {conv.padding}, groups {conv.groups} (not built)")
+        dims = []
+        for name, seq in (("fnet_proj", fnet_proj), ("cnet_proj", cnet_proj)):
+            conv = seq[0] if len(seq) == 2 else None
+            if not (isinstance(conv, torch.nn.Conv2d) and isinstance(seq[1], torch.nn.ReLU) and conv.in_channels == mb.block_table()[1][-1]["cout"]
+                    and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+                    and conv.groups == 1 and conv.bias is not None):
+                raise NndError(f"MobileNetV3Engine: {name} is not Conv2d(24, C, 3, 1, 1) + ReLU")
+            dims.append(conv.out_channels)
+        d = MobileNetV3Desc(fnet_dim=dims[0], cnet_dim=dims[1], flags=0)
+        n = int(lib.nnd_mbv3_num_tensors(C.byref(d)))
+        if n < 0:
+            check(n, "mbv3 descriptor")
+        return d
+
+    # ---------------------------------------------------------------- host fold
+    @staticmethod
+    def fold(fnet, fnet_proj, cnet_proj) -> List[dict]:
+        def lay(kind, w, b, k=1, stride=1, act="none", skip=False):
+            return {"kind": kind, "w": w, "b": b, "k": k, "stride": stride, "act": act, "skip": skip}
+
+        def cbn(conv, bn):
+            s, t = _bn_affine(bn)
+            return _d(conv.weight) * s.reshape(-1, 1, 1, 1), t
+
+        bb = fnet.backbone
+        L = [lay("stem", *cbn(bb.conv_stem, bb.bn1), 3, 2, "hswish")]
+        for stage in list(bb.blocks)[:6]:  # stage 6's output is never used
+            for blk in stage:
+                sp = blk.spec
+                act = "relu" if sp["relu"] else "hswish"
+                if sp["type"] == "ds":
+                    L.append(lay("dw", *cbn(blk.conv_dw, blk.bn1), sp["k"], sp["stride"], act))
+                    L.append(lay("pw", *cbn(blk.conv_pw, blk.bn2), skip=sp["skip"]))
+                    continue
+                L.append(lay("pw", *cbn(blk.conv_pw, blk.bn1), act=act))
+                L.append(lay("dw", *cbn(blk.conv_dw, blk.bn2), sp["k"], sp["stride"], act))
+                if sp["rd"]:
+                    L.append(lay("se_r", *_conv_wb(blk.se.conv_reduce), act="relu"))
+                    L.append(lay("se_e", *_conv_wb(blk.se.conv_expand), act="hsigmoid"))
+                L.append(lay("pw", *cbn(blk.conv_pwl, blk.bn3), skip=sp["skip"]))
+        for seq in (fnet_proj, cnet_proj):
+            L.append(lay("proj", *_conv_wb(seq[0]), 3, 1, "relu"))
+        return L
+
+    @staticmethod
+    def fold_forward(layers: List[dict], frame1: torch.Tensor, frame2: torch.Tensor):
+        """The folded chain as plain F.conv2d calls in the kernels' layer order and in the frames' dtype (float64: the fold checked
+        without a GPU).  -> (fmap1, fmap2, cnet1, [guide0, guide1, guide2], stage outputs of the left frames)."""
+        from .mobilenetv3 import block_table, same_pad
+        F = torch.nn.functional
+        it = iter(layers)
+
+        def conv(x, l, res=None):
+            w, b = l["w"].to(x), l["b"].to(x)
+            groups = x.shape[1] if l["kind"] == "dw" else 1
+            pad_x = same_pad(x, l["k"], l["stride"]) if l["kind"] in ("stem", "dw") else x
+            y = F.conv2d(pad_x, w, b, stride=l["stride"], padding=l["k"] // 2 if l["kind"] == "proj" else 0, groups=groups)
+            if l["act"] == "relu":
+                y = F.relu(y)
+            elif l["act"] == "hswish":
+                y = F.hardswish(y)
+            elif l["act"] == "hsigmoid":
+                y = F.hardsigmoid(y)
+            return res + y if res is not None else y
+
+        B = frame1.shape[0]
+        x = conv(torch.cat([frame1, frame2], 0), next(it))
+        stages = []
+        for si, specs in enumerate(block_table()[:6]):
+            if si == 2:
+                x = x[:B]  # stages 2..5: the left frames only (eval BatchNorm is per sample)
+            for sp in specs:
+                inp = x
+                if sp["type"] == "ir":
+                    x = conv(x, next(it))
+                x = conv(x, next(it))
+                if sp["rd"]:
+                    g = conv(conv(x.mean((2, 3), keepdim=True), next(it)), next(it))
+                    x = x * g
+                x = conv(x, next(it), res=inp if sp["skip"] else None)
+            stages.append(x)
+            if si == 1:
+                fp, cp = layers[-2], layers[-1]
+                fmaps = conv(x, fp)
+                cnet1 = conv(x[:B], cp)
+        return fmaps[:B], fmaps[B:], cnet1, [stages[2], stages[3], stages[5]], [s[:B] for s in stages]
+
+    @classmethod
+    def from_modules(cls, fnet, fnet_proj, cnet_proj, device) -> "MobileNetV3Engine":
+        desc = cls.descriptor(fnet, fnet_proj, cnet_proj)
+        return cls(desc, cls.fold(fnet, fnet_proj, cnet_proj), device)
+
+    # ---------------------------------------------------------------- forward
+    def forward(self, frame1: torch.Tensor, frame2: torch.Tensor):
+        """(B,3,H,W) x 2 -> (fmap1, fmap2, cnet1, [guide0, guide1, guide2]) as IGEVStereoMBNet.forward_fnet returns them."""
+        if tuple(frame1.shape) != tuple(frame2.shape) or frame1.dim() != 4 or frame1.shape[1] != 3:
+            raise NndError(f"mbv3: frames {tuple(frame1.shape)} / {tuple(frame2.shape)}: expected two (B, 3, H, W) tensors")
+        d = _dev(frame1, frame2, self.packed)
+        frame1, frame2 = frame1.contiguous(), frame2.contiguous()
+        B, _, H, W = frame1.shape
+        ds = self.desc
+        hw = [(H, W)]
+        for _ in range(5):
+            hw.append(((hw[-1][0] + 1) // 2, (hw[-1][1] + 1) // 2))
+        f = lambda c, s: torch.empty((B, c) + s, dtype=torch.float32, device=d)  # noqa: E731
+        fmap1, fmap2, cnet1 = f(ds.fnet_dim, hw[2]), f(ds.fnet_dim, hw[2]), f(ds.cnet_dim, hw[2])
+        guides = [f(40, hw[3]), f(80, hw[4]), f(160, hw[5])]
+        need = int(lib.nnd_mbv3_workspace_floats(C.byref(ds), B, H, W))
+        if need < 0:
+            check(need, "mbv3_workspace_floats")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
+            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_mbv3_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), _p(fmap1), _p(fmap2), _p(cnet1),
+                                       *[_p(g) for g in guides], _p(self._ws), B, H, W, _stream(d)), "mbv3_forward")
+        return fmap1, fmap2, cnet1, guides
 
 
 def softargmin_disparity(logits: torch.Tensor) -> torch.Tensor:
