@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define NND_VERSION 104 /* 0.1.4: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak */
+#define NND_VERSION 104 /* 0.1.4: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning) */
 
 /* Descriptors start with `struct_size` = sizeof(the descriptor type) of the header the caller was compiled against; every entry
  * point that takes one refuses another size (NND_ERR_INVALID), so a caller and a library of different versions cannot
@@ -467,6 +467,51 @@ int nnd_mbv3_pointwise_pack(int Cout, int Cin, int k, const float* w, const floa
 int nnd_mbv3_proj(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int H, int W, void* stream);
 int nnd_mbv3_pointwise(int Cout, int Cin, int k, const float* packed_dev, const float* x, const float* residual, float* y, int N, int H,
                        int W, int act, void* stream);
+
+/* ------------------------------------------------------------------------------ MobileNetV3DepthModel (csrc/midas.hip)
+ * The reference's monocular model (nndepth/models/midas/models/mobilenet_v3.py) in one call, exact fp32: the MobileNetV3-Large
+ * backbone above on ONE frame tensor (stages 0..5, taps of stages 1, 2, 4, 5), BaseDecoder (four skip convs, four UpsamplerBlocks)
+ * and the last_conv head.  x (B,3,H,W) -> depth (B,1,H,W); H and W must be multiples of 32 (refused by name otherwise: the
+ * decoder's x2 upsamples would not meet the backbone's ceil(n / 2) maps).  feature_channels: multiples of 16 up to 128.
+ * nnd_midas_pack (HOST): `tensors` = nnd_midas_num_tensors(desc) pointers, 2 per layer {weight, bias}, every BatchNorm already
+ *   folded into its conv, in the order: the backbone's layers as nnd_mbv3_pack takes them (without fnet_proj / cnet_proj) |
+ *   decoder.skip_layers.0..3 | per decoder.upsampler_layers.0..3: [conv1 + bn1 (blocks 0..2 only: block 3 runs without a skip
+ *   input, its conv1 / bn1 are never evaluated)], conv2 + bn2, out_conv | last_conv.0, last_conv.2, last_conv.4.
+ * nnd_midas_forward: all launches on `stream`, no allocation, no synchronisation; workspace = nnd_midas_workspace_floats floats,
+ *   caller-owned.  After the call the workspace still holds the four taps, the decoder's output (B,C,H/2,W/2) and — with
+ *   NND_MIDAS_KEEP_PRE in desc->flags — the map before the final ReLU (B,1,H,W), at nnd_midas_workspace_offset(desc, which, ...)
+ *   floats (which: 0..3 taps, 4 decoder output, 5 pre-ReLU map).                                                             */
+#define NND_MIDAS_KEEP_PRE 1
+typedef struct nnd_midas_desc {
+    int32_t struct_size; /* sizeof(nnd_midas_desc) */
+    int32_t feature_channels;
+    int32_t flags;       /* NND_MIDAS_KEEP_PRE or 0 */
+} nnd_midas_desc;
+int nnd_midas_num_tensors(const nnd_midas_desc* desc);
+int64_t nnd_midas_packed_floats(const nnd_midas_desc* desc);
+int64_t nnd_midas_workspace_floats(const nnd_midas_desc* desc, int B, int H, int W);
+int64_t nnd_midas_workspace_offset(const nnd_midas_desc* desc, int which, int B, int H, int W);
+int nnd_midas_pack(const nnd_midas_desc* desc, const float* const* tensors_host, float* packed_host);
+int nnd_midas_forward(const nnd_midas_desc* desc, const float* packed_dev, const float* x, float* depth, float* workspace, int B, int H,
+                      int W, void* stream);
+/* The model's new kernels one at a time, as nnd_midas_forward launches them (NCHW, fp32, all on `stream`); channel counts:
+ * multiples of 16 up to 128.
+ *   nnd_midas_up2x_pw   y (N,Cout,2h,2w) = relu(conv1x1(up2x(x (N,Cin,h,w))) + bias), up2x = F.interpolate(scale_factor=2,
+ *                       mode="bilinear", align_corners=False) evaluated while the tile is staged: the upsampled map is never
+ *                       written.  packed: nnd_midas_up2x_pw_pack (HOST) of w (Cout,Cin,1,1), bias.
+ *   nnd_midas_head      depth (N,1,2h,2w) = relu(conv1x1_{C->1}(relu(conv3x3_{C->C}(up2x(t (N,C,h,w))) + b2)) + b4) in one kernel;
+ *                       pre_relu (optional, same shape): the value before the last ReLU.  packed: nnd_midas_head_pack (HOST) of
+ *                       w2 (C,C,3,3), b2 (C), w4 (1,C,1,1), b4 (1).
+ *   nnd_midas_conv_add  y = feat + relu(conv k x k (1 or 3, padding k / 2)(x) + bias): the activation BEFORE the addition
+ *                       (nnd_mbv3_pointwise's residual mode adds first); packed: nnd_mbv3_pointwise_pack.                     */
+int64_t nnd_midas_up2x_pw_packed_floats(int Cout, int Cin);
+int nnd_midas_up2x_pw_pack(int Cout, int Cin, const float* w, const float* bias, float* packed_host);
+int nnd_midas_up2x_pw(int Cout, int Cin, const float* packed_dev, const float* x, float* y, int N, int h, int w, void* stream);
+int64_t nnd_midas_head_packed_floats(int C);
+int nnd_midas_head_pack(int C, const float* w2, const float* b2, const float* w4, const float* b4, float* packed_host);
+int nnd_midas_head(int C, const float* packed_dev, const float* t, float* depth, float* pre_relu, int N, int h, int w, void* stream);
+int nnd_midas_conv_add(int Cout, int Cin, int k, const float* packed_dev, const float* x, const float* feat, float* y, int N, int H, int W,
+                       void* stream);
 
 /* ------------------------------------------------------------- pre- / post-processing on the device
  * nnd_resize_normalize : preprocess_frame  nndepth/models/raft_stereo/scripts/inference.py:55-60

@@ -56,6 +56,13 @@ class MobileNetV3Desc(_SizedDesc):
     _fields_ = [("struct_size", C.c_int32), ("fnet_dim", C.c_int32), ("cnet_dim", C.c_int32), ("flags", C.c_int32)]
 
 
+NND_MIDAS_KEEP_PRE = 1
+
+
+class MidasDesc(_SizedDesc):
+    _fields_ = [("struct_size", C.c_int32), ("feature_channels", C.c_int32), ("flags", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/nndepth_amd.h one to one
 _P = C.c_void_p
 _I = C.c_int
@@ -148,6 +155,19 @@ SIGNATURES = {
     "nnd_mbv3_pointwise_packed_floats": (C.c_int64, [_I, _I, _I]),
     "nnd_mbv3_pointwise_pack": (_I, [_I, _I, _I, _P, _P, _P]),
     "nnd_mbv3_pointwise": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nnd_midas_num_tensors": (_I, [C.POINTER(MidasDesc)]),
+    "nnd_midas_packed_floats": (C.c_int64, [C.POINTER(MidasDesc)]),
+    "nnd_midas_workspace_floats": (C.c_int64, [C.POINTER(MidasDesc), _I, _I, _I]),
+    "nnd_midas_workspace_offset": (C.c_int64, [C.POINTER(MidasDesc), _I, _I, _I, _I]),
+    "nnd_midas_pack": (_I, [C.POINTER(MidasDesc), C.POINTER(_P), _P]),
+    "nnd_midas_forward": (_I, [C.POINTER(MidasDesc), _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_midas_up2x_pw_packed_floats": (C.c_int64, [_I, _I]),
+    "nnd_midas_up2x_pw_pack": (_I, [_I, _I, _P, _P, _P]),
+    "nnd_midas_up2x_pw": (_I, [_I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_midas_head_packed_floats": (C.c_int64, [_I]),
+    "nnd_midas_head_pack": (_I, [_I, _P, _P, _P, _P, _P]),
+    "nnd_midas_head": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_midas_conv_add": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "nnd_resize_normalize": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_replicate_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_epe_metrics_workspace_bytes": (C.c_int64, []),

@@ -20,7 +20,7 @@
 // Every conv_mfma launch fixes its split-K factor per layer (2 from two K chunks on, else 1; as repvit.hip), so a pair's maps do not
 // depend on the batch it runs in.  The SE mean is reduced in a fixed order (workgroup tree, then the workgroups in order): no
 // float atomics, bit-reproducible.  Activations are NCHW in the caller's workspace.
-#include "common.h"
+#include "mbv3.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,7 +30,6 @@
 
 namespace nnd {
 
-enum MbAct { MB_NONE = 0, MB_RELU = 1, MB_HSWISH = 2 };
 
 // torch's hardswish / hardsigmoid: x * min(max(x + 3, 0), 6) / 6, min(max(x + 3, 0), 6) / 6
 __device__ __forceinline__ double mb_act(double v, int act) {
@@ -39,9 +38,6 @@ __device__ __forceinline__ double mb_act(double v, int act) {
     return v;
 }
 
-// TF "same" padding before the data along one axis (timm pad_same): total max((ceil(n / s) - 1) * s + k - n, 0), half before
-static inline int same_out(int n, int s) { return (n + s - 1) / s; }
-static inline int same_pad_before(int n, int k, int s) { return std::max((same_out(n, s) - 1) * s + k - n, 0) / 2; }
 
 // ------------------------------------------------------------------------------------------ depthwise k x k
 // One thread per output pixel of one (sample, channel) plane; taps in (dy, dx) order, float64 accumulation rounded once after
@@ -132,7 +128,6 @@ __global__ void __launch_bounds__(256) mbv3_gate_kernel(float* __restrict__ y, c
 // ------------------------------------------------------------------------------------------ conv_stem: 3x3 dense, 3 -> 16, stride 2
 // Samples n < nsplit read `x`, the others `x1` (the two frame tensors where they lie).  One thread per output pixel, all 16
 // output channels; float64 taps, bias and hard-swish, rounded once; the 27 x 16 weights sit in LDS.
-constexpr int MB_STEM_C = 16;
 __global__ void __launch_bounds__(256) mbv3_stem_kernel(const float* __restrict__ x, const float* __restrict__ x1, int nsplit,
                                                         float* __restrict__ y, const float* __restrict__ w, const float* __restrict__ bias,
                                                         int Hin, int Win, int Ho, int Wo, int pt, int pl) {
@@ -216,11 +211,7 @@ __global__ void __launch_bounds__(256) mbv3_proj_kernel(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------ plan
 // The backbone is fixed (tf_mobilenetv3_large_100, stages 0..5 as decoded by timm; nndepth_amd/mobilenetv3.py:block_table)
-struct MbBlock {
-    int ir;  // 0: DepthwiseSeparable, 1: InvertedResidual
-    int cin, mid, cout, k, stride, rd, act, skip, stage;
-};
-static const MbBlock MB_BLOCKS[] = {
+const MbBlock MB_BLOCKS[] = {
     {0, 16, 16, 16, 3, 1, 0, MB_RELU, 1, 0},
     {1, 16, 64, 24, 3, 2, 0, MB_RELU, 0, 1},      {1, 24, 72, 24, 3, 1, 0, MB_RELU, 1, 1},
     {1, 24, 72, 40, 5, 2, 24, MB_RELU, 0, 2},     {1, 40, 120, 40, 5, 1, 32, MB_RELU, 1, 2},   {1, 40, 120, 40, 5, 1, 32, MB_RELU, 1, 2},
@@ -229,23 +220,13 @@ static const MbBlock MB_BLOCKS[] = {
     {1, 80, 480, 112, 3, 1, 120, MB_HSWISH, 0, 4}, {1, 112, 672, 112, 3, 1, 168, MB_HSWISH, 1, 4},
     {1, 112, 672, 160, 5, 2, 168, MB_HSWISH, 0, 5}, {1, 160, 960, 160, 5, 1, 240, MB_HSWISH, 1, 5}, {1, 160, 960, 160, 5, 1, 240, MB_HSWISH, 1, 5},
 };
-constexpr int MB_NBLOCKS = (int)(sizeof(MB_BLOCKS) / sizeof(MB_BLOCKS[0]));
+const int MB_NBLOCKS = (int)(sizeof(MB_BLOCKS) / sizeof(MB_BLOCKS[0]));
 constexpr int MB_S1_C = 24;  // stage 1's width: fnet_proj / cnet_proj input
 
-enum MbKind { MB_STEM = 0, MB_DW = 1, MB_PW = 2, MB_SE_R = 3, MB_SE_E = 4, MB_PROJ = 5 };
 
-struct MbLayer {
-    int kind, cin, cout, k, stride, act;
-    ConvLayer cl;         // MB_PW (1x1 or 3x3, stride 1): conv_mfma layout
-    int64_t off, floats;  // blob offset / size (the others: weights then bias)
-};
 
-struct MbPlan {
-    std::vector<MbLayer> layers;
-    int64_t total = 0;
-};
 
-static void mb_add(MbPlan& p, int kind, int cin, int cout, int k, int stride, int act) {
+void mb_add(MbPlan& p, int kind, int cin, int cout, int k, int stride, int act) {
     MbLayer l{};
     l.kind = kind; l.cin = cin; l.cout = cout; l.k = k; l.stride = stride; l.act = act;
     l.off = p.total;
@@ -285,27 +266,31 @@ static int mb_check(const nnd_mbv3_desc* d) {
 
 // layer order (= the tensor order of nnd_mbv3_pack): stem | per block: [IR: expand 1x1] depthwise [SE reduce, SE expand] project 1x1 |
 // fnet_proj 3x3 | cnet_proj 3x3
+void mb_plan_backbone(MbPlan& p) {
+    mb_add(p, MB_STEM, 3, MB_STEM_C, 3, 2, MB_HSWISH);
+    for (int i = 0; i < MB_NBLOCKS; ++i) {
+        const MbBlock& b = MB_BLOCKS[i];
+        if (b.ir) mb_add(p, MB_PW, b.cin, b.mid, 1, 1, b.act);
+        mb_add(p, MB_DW, b.mid, b.mid, b.k, b.stride, b.act);
+        if (b.rd) {
+            mb_add(p, MB_SE_R, b.mid, b.rd, 1, 1, MB_RELU);
+            mb_add(p, MB_SE_E, b.rd, b.mid, 1, 1, MB_NONE);
+        }
+        mb_add(p, MB_PW, b.mid, b.cout, 1, 1, MB_NONE);
+    }
+}
+
 static int mb_plan(const nnd_mbv3_desc* d, MbPlan* p) {
     if (int rc = mb_check(d)) return rc;
     p->layers.clear();
     p->total = 0;
-    mb_add(*p, MB_STEM, 3, MB_STEM_C, 3, 2, MB_HSWISH);
-    for (int i = 0; i < MB_NBLOCKS; ++i) {
-        const MbBlock& b = MB_BLOCKS[i];
-        if (b.ir) mb_add(*p, MB_PW, b.cin, b.mid, 1, 1, b.act);
-        mb_add(*p, MB_DW, b.mid, b.mid, b.k, b.stride, b.act);
-        if (b.rd) {
-            mb_add(*p, MB_SE_R, b.mid, b.rd, 1, 1, MB_RELU);
-            mb_add(*p, MB_SE_E, b.rd, b.mid, 1, 1, MB_NONE);
-        }
-        mb_add(*p, MB_PW, b.mid, b.cout, 1, 1, MB_NONE);
-    }
+    mb_plan_backbone(*p);
     mb_add(*p, MB_PROJ, MB_S1_C, d->fnet_dim, 3, 1, MB_RELU);
     mb_add(*p, MB_PROJ, MB_S1_C, d->cnet_dim, 3, 1, MB_RELU);
     return NND_OK;
 }
 
-static int64_t mb_align(int64_t n) { return (n + 63) / 64 * 64; }
+int64_t mb_align(int64_t n) { return (n + 63) / 64 * 64; }
 
 // workspace: running activations A, B (ping-pong), expanded E, depthwise D, stage 1's map of both frames, SE gate, SE partials
 struct MbWs {
@@ -333,7 +318,7 @@ static MbWs mb_ws(int B, int H, int W) {
     return r;
 }
 
-static int run_dw(const MbLayer& l, const float* blob, const float* x, float* y, double* partial, int N, int Hin, int Win,
+int run_dw(const MbLayer& l, const float* blob, const float* x, float* y, double* partial, int N, int Hin, int Win,
                   hipStream_t st) {
     const int Ho = same_out(Hin, l.stride), Wo = same_out(Win, l.stride);
     const int pt = l.stride == 1 ? l.k / 2 : same_pad_before(Hin, l.k, 2), pl = l.stride == 1 ? l.k / 2 : same_pad_before(Win, l.k, 2);
@@ -348,7 +333,7 @@ static int run_dw(const MbLayer& l, const float* blob, const float* x, float* y,
     return NND_OK;
 }
 
-static int run_se(const MbLayer& lr, const MbLayer& le, const float* blob, float* y, const double* partial, float* gate, int N, int H,
+int run_se(const MbLayer& lr, const MbLayer& le, const float* blob, float* y, const double* partial, float* gate, int N, int H,
                   int W, hipStream_t st) {
     const int C = lr.cin, rd = lr.cout, P = H * W;
     const float* wr = blob + lr.off;
@@ -362,7 +347,7 @@ static int run_se(const MbLayer& lr, const MbLayer& le, const float* blob, float
 }
 
 // 1x1 / 3x3 stride-1 conv on conv_mfma (NCHW in / out); res: the residual (same shape as y), MB_NONE layers only
-static int run_pw(const MbLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int64_t ybs, const float* res, int N, int H,
+int run_pw(const MbLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int64_t ybs, const float* res, int N, int H,
                   int W, hipStream_t st) {
     ConvIO io{};
     io.src0 = Act{const_cast<float*>(x), xbs, l.cin};
@@ -382,12 +367,88 @@ static int run_proj(const MbLayer& l, const float* blob, const float* x, int64_t
     return NND_OK;
 }
 
-static void pack_pw(const MbLayer& l, const float* w, const float* b, float* base) {
+void pack_pw(const MbLayer& l, const float* w, const float* b, float* base) {
     const float* ws[1] = {w};
     const float* bs[1] = {b};
     int co[1] = {l.cout};
     pack_conv(l.cl, 1, ws, bs, co, base);
     for (int c = 0; c < l.cl.ncb * 32; ++c) base[l.cl.s_off + c] = c < l.cout ? 1.f : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------ one frame tensor (midas.hip)
+// workspace: running activations A, B (ping-pong), expanded E, depthwise D, SE gate, SE partials (doubles)
+struct MbWs1 {
+    int64_t act, e, d, gate, part;
+};
+
+static MbWs1 mb_ws1(int B, int H, int W) {
+    MbWs1 r{};
+    int h = same_out(H, 2), w = same_out(W, 2);
+    r.act = (int64_t)B * MB_STEM_C * h * w;
+    for (int i = 0; i < MB_NBLOCKS; ++i) {
+        const MbBlock& b = MB_BLOCKS[i];
+        const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
+        r.act = std::max(r.act, (int64_t)B * b.cout * ho * wo);
+        r.e = std::max(r.e, (int64_t)B * b.mid * h * w);
+        r.d = std::max(r.d, (int64_t)B * b.mid * ho * wo);
+        if (b.rd) {
+            r.gate = std::max(r.gate, (int64_t)B * b.mid);
+            r.part = std::max(r.part, (int64_t)B * b.mid * cdiv(ho * wo, MB_DW_T));
+        }
+        h = ho; w = wo;
+    }
+    return r;
+}
+
+int64_t mb_single_ws(int B, int H, int W) {
+    const MbWs1 r = mb_ws1(B, H, W);
+    return 2 * mb_align(r.act) + mb_align(r.e) + mb_align(r.d) + mb_align(r.gate) + 2 * mb_align(r.part);
+}
+
+int mb_single_forward(const MbPlan& p, const float* packed, const float* frame, float* const* taps, float* workspace, int B, int H, int W,
+                      hipStream_t st) {
+    const MbWs1 r = mb_ws1(B, H, W);
+    float* q = workspace;
+    float* bufA = q; q += mb_align(r.act);
+    float* bufB = q; q += mb_align(r.act);
+    float* E = q; q += mb_align(r.e);
+    float* D = q; q += mb_align(r.d);
+    float* gate = q; q += mb_align(r.gate);
+    double* part = reinterpret_cast<double*>(q);  // 64-float aligned
+    size_t li = 0;
+    auto L = [&]() -> const MbLayer& { return p.layers[li++]; };
+    int rc;
+    int h = same_out(H, 2), w = same_out(W, 2);
+    {
+        const MbLayer& l0 = L();
+        hipLaunchKernelGGL(mbv3_stem_kernel, dim3((unsigned)cdiv(h * w, 256), 1, (unsigned)B), dim3(256), 0, st, frame, frame, B, bufA,
+                           packed + l0.off, packed + l0.off + MB_STEM_C * 27, H, W, h, w, same_pad_before(H, 3, 2), same_pad_before(W, 3, 2));
+        NND_LAUNCH_CHECK();
+    }
+    const float* x = bufA;
+    for (int i = 0; i < MB_NBLOCKS; ++i) {
+        const MbBlock& b = MB_BLOCKS[i];
+        const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
+        const bool last = i + 1 == MB_NBLOCKS || MB_BLOCKS[i + 1].stage != b.stage;
+        float* keep = !last ? nullptr : b.stage == 1 ? taps[0] : b.stage == 2 ? taps[1] : b.stage == 4 ? taps[2] : b.stage == 5 ? taps[3] : nullptr;
+        float* out = keep ? keep : (x == bufA ? bufB : bufA);
+        const float* dwin = x;
+        if (b.ir) {
+            if ((rc = run_pw(L(), packed, x, (int64_t)b.cin * h * w, E, (int64_t)b.mid * h * w, nullptr, B, h, w, st))) return rc;
+            dwin = E;
+        }
+        if ((rc = run_dw(L(), packed, dwin, D, b.rd ? part : nullptr, B, h, w, st))) return rc;
+        if (b.rd) {
+            const MbLayer& lr = L();
+            const MbLayer& le = L();
+            if ((rc = run_se(lr, le, packed, D, part, gate, B, ho, wo, st))) return rc;
+        }
+        if ((rc = run_pw(L(), packed, D, (int64_t)b.mid * ho * wo, out, (int64_t)b.cout * ho * wo, b.skip ? x : nullptr, B, ho, wo, st)))
+            return rc;
+        x = out;
+        h = ho; w = wo;
+    }
+    return NND_OK;
 }
 
 }  // namespace nnd

@@ -12,7 +12,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import (NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, Conv3dDesc, ConvDesc, EncoderDesc, MobileNetV3Desc, NndError, RepViTDesc,
+from ._lib import (NND_FLAG_CALIBRATE, NND_FLAG_LAST_UPSAMPLE_ONLY, NND_MIDAS_KEEP_PRE, Conv3dDesc, ConvDesc, EncoderDesc, MidasDesc,
+                   MobileNetV3Desc, NndError, RepViTDesc,
                    UpdateBlockDesc,
                    check, lib)
 
@@ -1320,7 +1321,8 @@ class MobileNetV3Engine:
 
     # ---------------------------------------------------------------- host fold
     @staticmethod
-    def fold(fnet, fnet_proj, cnet_proj) -> List[dict]:
+    def fold_backbone(fnet) -> List[dict]:
+        """The backbone's layers alone (stem and stages 0..5), shared with MidasEngine."""
         def lay(kind, w, b, k=1, stride=1, act="none", skip=False):
             return {"kind": kind, "w": w, "b": b, "k": k, "stride": stride, "act": act, "skip": skip}
 
@@ -1344,6 +1346,14 @@ class MobileNetV3Engine:
                     L.append(lay("se_r", *_conv_wb(blk.se.conv_reduce), act="relu"))
                     L.append(lay("se_e", *_conv_wb(blk.se.conv_expand), act="hsigmoid"))
                 L.append(lay("pw", *cbn(blk.conv_pwl, blk.bn3), skip=sp["skip"]))
+        return L
+
+    @staticmethod
+    def fold(fnet, fnet_proj, cnet_proj) -> List[dict]:
+        def lay(kind, w, b, k=1, stride=1, act="none", skip=False):
+            return {"kind": kind, "w": w, "b": b, "k": k, "stride": stride, "act": act, "skip": skip}
+
+        L = MobileNetV3Engine.fold_backbone(fnet)
         for seq in (fnet_proj, cnet_proj):
             L.append(lay("proj", *_conv_wb(seq[0]), 3, 1, "relu"))
         return L
@@ -1420,6 +1430,239 @@ class MobileNetV3Engine:
             check(lib.nnd_mbv3_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), _p(fmap1), _p(fmap2), _p(cnet1),
                                        *[_p(g) for g in guides], _p(self._ws), B, H, W, _stream(d)), "mbv3_forward")
         return fmap1, fmap2, cnet1, guides
+
+
+class MidasEngine:
+    """MobileNetV3DepthModel on the HIP path (csrc/midas.hip, ONE call per forward: nnd_midas_forward), packed from the modules of
+    nndepth_amd.midas.  `fold(model)` folds every eval-mode BatchNorm into its conv in float64 on the host, as
+    MobileNetV3Engine.fold; the layers are cast once to fp32 when packed.  Layer order: the backbone (MobileNetV3Engine.
+    fold_backbone) | skip_layers.0..3 | per UpsamplerBlock 0..3: [conv1 + bn1 (blocks 0..2: block 3 runs without a skip input)],
+    conv2 + bn2, out_conv | last_conv.0, .2, .4."""
+
+    MAPS = ("tap0", "tap1", "tap2", "tap3", "decoder", "pre_relu")
+
+    def __init__(self, desc: MidasDesc, layers: List[dict], device):
+        self.desc, self.layers = desc, layers
+        n = int(lib.nnd_midas_num_tensors(C.byref(desc)))
+        if n < 0:
+            check(n, "midas_num_tensors")
+        if n != 2 * len(layers):
+            raise NndError(f"MidasEngine: {len(layers)} layers folded, the library expects {n // 2}")
+        host = []
+        for l in layers:
+            host += [l["w"].float().contiguous(), l["b"].float().contiguous()]
+        arr = (C.c_void_p * n)(*[t.data_ptr() for t in host])
+        total = int(lib.nnd_midas_packed_floats(C.byref(desc)))
+        if total <= 0:
+            check(total, "midas_packed_floats")
+        blob = torch.empty(total, dtype=torch.float32)
+        check(lib.nnd_midas_pack(C.byref(desc), arr, _p(blob)), "midas_pack")
+        self.packed = blob.to(device)
+        self._ws = None
+
+    @staticmethod
+    def descriptor(model) -> MidasDesc:
+        """The descriptor of a nndepth_amd.midas.MobileNetV3DepthModel, or NndError naming what the HIP path does not build."""
+        from . import midas as md
+        from . import mobilenetv3 as mb
+        enc = getattr(model, "encoder", None)
+        if not isinstance(enc, mb.MobilenetV3LargeEncoder) or not isinstance(getattr(enc, "backbone", None), mb.MobileNetV3Features):
+            raise NndError(f"MidasEngine: encoder is a {type(enc).__name__}, not nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder")
+        got = [(k, tuple(v.shape)) for k, v in enc.state_dict().items()]
+        if got != _mbv3_layout():
+            raise NndError("MidasEngine: the encoder's parameters differ from tf_mobilenetv3_large_100's layout; a replaced or reshaped "
+                           "block is not built")
+        if list(enc.feature_hooks) != list(md.HOOKS):
+            raise NndError(f"MidasEngine: feature_hooks {enc.feature_hooks} (built: {list(md.HOOKS)})")
+        dec = getattr(model, "decoder", None)
+        if not isinstance(dec, md.BaseDecoder) or list(dec.in_channels) != list(md.TAP_CHANNELS) or len(set(dec.out_channels)) != 1:
+            raise NndError("MidasEngine: decoder is not BaseDecoder([24, 40, 112, 160], [C] * 4)")
+        Cc = int(dec.out_channels[0])
+        for blk in dec.upsampler_layers:
+            if not isinstance(blk, md.UpsamplerBlock) or not blk.use_bn or blk.in_channels != Cc or blk.out_channels != Cc:
+                raise NndError(f"MidasEngine: an UpsamplerBlock that is not UpsamplerBlock({Cc}, {Cc}, use_bn=True) is not built")
+        lc = model.last_conv
+        kinds = [torch.nn.Conv2d, torch.nn.Upsample, torch.nn.Conv2d, torch.nn.ReLU, torch.nn.Conv2d, torch.nn.ReLU]
+        if len(lc) != 6 or any(type(m) is not k for m, k in zip(lc, kinds)) or lc[4].out_channels != 1 or lc[0].in_channels != Cc:
+            raise NndError("MidasEngine: last_conv is not Conv3x3, Upsample(x2, bilinear), Conv3x3, ReLU, Conv1x1(C, 1), ReLU")
+        d = MidasDesc(feature_channels=Cc, flags=0)
+        n = int(lib.nnd_midas_num_tensors(C.byref(d)))
+        if n < 0:
+            check(n, "midas descriptor")
+        return d
+
+    @staticmethod
+    def fold(model) -> List[dict]:
+        def lay(kind, w, b, k=1, act="none"):
+            return {"kind": kind, "w": w, "b": b, "k": k, "stride": 1, "act": act, "skip": False}
+
+        def cbn(conv, bn):
+            s, t = _bn_affine(bn)
+            w, b = _conv_wb(conv)
+            return w * s.reshape(-1, 1, 1, 1), b * s + t
+
+        L = MobileNetV3Engine.fold_backbone(model.encoder)
+        dec = model.decoder
+        for seq in dec.skip_layers:
+            L.append(lay("skip", *_conv_wb(seq[0]), 3, "relu"))
+        for i, blk in enumerate(dec.upsampler_layers):
+            if i < len(dec.upsampler_layers) - 1:  # the last block runs with skip_feat=None: conv1 / bn1 are never evaluated
+                L.append(lay("up_conv1", *cbn(blk.conv1, blk.bn1), 3, "relu"))
+            L.append(lay("up_conv2", *cbn(blk.conv2, blk.bn2), 3, "relu"))
+            L.append(lay("up_out", *_conv_wb(blk.out_conv), 1, "relu"))
+        lc = model.last_conv
+        L.append(lay("last0", *_conv_wb(lc[0]), 3))
+        L.append(lay("last2", *_conv_wb(lc[2]), 3, "relu"))
+        L.append(lay("last4", *_conv_wb(lc[4]), 1, "relu"))
+        return L
+
+    @staticmethod
+    def fold_forward(layers: List[dict], x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The folded chain as plain F.conv2d / F.interpolate calls in the kernels' layer order and in x's dtype (float64: the
+        fold checked without a GPU).  -> {tap0..tap3, decoder, pre_relu, depth}."""
+        from .mobilenetv3 import block_table, same_pad
+        F = torch.nn.functional
+        it = iter(layers)
+
+        def conv(x, l, res=None):
+            w, b = l["w"].to(x), l["b"].to(x)
+            if l["kind"] in ("stem", "dw"):
+                y = F.conv2d(same_pad(x, l["k"], l["stride"]), w, b, stride=l["stride"], groups=x.shape[1] if l["kind"] == "dw" else 1)
+            else:
+                y = F.conv2d(x, w, b, padding=l["k"] // 2)
+            if l["act"] == "relu":
+                y = F.relu(y)
+            elif l["act"] == "hswish":
+                y = F.hardswish(y)
+            elif l["act"] == "hsigmoid":
+                y = F.hardsigmoid(y)
+            return res + y if res is not None else y
+
+        up = lambda t: F.interpolate(t, scale_factor=2, mode="bilinear", align_corners=False)  # noqa: E731
+        x = conv(x, next(it))
+        stages = []
+        for specs in block_table()[:6]:
+            for sp in specs:
+                inp = x
+                if sp["type"] == "ir":
+                    x = conv(x, next(it))
+                x = conv(x, next(it))
+                if sp["rd"]:
+                    x = x * conv(conv(x.mean((2, 3), keepdim=True), next(it)), next(it))
+                x = conv(x, next(it), res=inp if sp["skip"] else None)
+            stages.append(x)
+        taps = [stages[i] for i in (1, 2, 4, 5)]
+        skips = [conv(t, next(it)) for t in taps]
+        rest = list(it)
+        ups = [rest[0:3], rest[3:6], rest[6:9], rest[9:11]]
+        out = None
+        for i in (3, 2, 1, 0):
+            ls = ups[i]
+            feat = skips[3] if i == 3 else conv(skips[i], ls[0], res=out)  # feat + relu(bn1(conv1(skip)))
+            out = conv(up(conv(feat, ls[-2])), ls[-1])
+        t = conv(out, rest[11])
+        pre = conv(up(t), rest[12])
+        l4 = rest[13]
+        pre = F.conv2d(pre, l4["w"].to(x), l4["b"].to(x))
+        r = {f"tap{i}": taps[i] for i in range(4)}
+        r.update(decoder=out, pre_relu=pre, depth=F.relu(pre))
+        return r
+
+    @classmethod
+    def from_model(cls, model, device) -> "MidasEngine":
+        return cls(cls.descriptor(model), cls.fold(model), device)
+
+    def forward(self, x: torch.Tensor, keep: bool = False):
+        """x (B,3,H,W) -> depth (B,1,H,W).  keep=True: -> (depth, {tap0..tap3, decoder, pre_relu}), the intermediate maps as views
+        of the workspace (valid until the next call)."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise NndError(f"midas: input {tuple(x.shape)}: expected (B, 3, H, W)")
+        d = _dev(x, self.packed)
+        x = x.contiguous()
+        B, _, H, W = x.shape
+        ds = MidasDesc(feature_channels=self.desc.feature_channels, flags=NND_MIDAS_KEEP_PRE if keep else 0)
+        need = int(lib.nnd_midas_workspace_floats(C.byref(ds), B, H, W))
+        if need < 0:
+            check(need, "midas_workspace_floats")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
+            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_midas_forward(C.byref(ds), _p(self.packed), _p(x), _p(depth), _p(self._ws), B, H, W, _stream(d)), "midas_forward")
+        if not keep:
+            return depth
+        Cc = ds.feature_channels
+        shapes = [(B, c, H >> (i + 2), W >> (i + 2)) for i, c in enumerate((24, 40, 112, 160))] + [(B, Cc, H // 2, W // 2), (B, 1, H, W)]
+        maps = {}
+        for which, (name, shp) in enumerate(zip(self.MAPS, shapes)):
+            off = int(lib.nnd_midas_workspace_offset(C.byref(ds), which, B, H, W))
+            if off < 0:
+                check(off, "midas_workspace_offset")
+            n = shp[0] * shp[1] * shp[2] * shp[3]
+            maps[name] = self._ws[off:off + n].view(shp)
+        return depth, maps
+
+
+# ---- MidasEngine's new kernels one at a time (per-kernel tests and profiles): parameters packed on every call
+def _pack_host(n: int, what: str) -> torch.Tensor:
+    if n <= 0:
+        check(n, what)
+    return torch.empty(n, dtype=torch.float32)
+
+
+def midas_up2x_pw(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """relu(conv1x1(up2x(x)) + bias), up2x = bilinear x2 with align_corners=False, in one kernel: (N,Cin,h,w) -> (N,Cout,2h,2w)."""
+    d = _dev(x)
+    x = x.contiguous()
+    N, Cin, h, w = x.shape
+    Cout = weight.shape[0]
+    blob = _pack_host(int(lib.nnd_midas_up2x_pw_packed_floats(Cout, Cin)), "midas_up2x_pw_packed_floats")
+    wh, bh = _host(weight), _host(bias)  # kept alive across the call
+    check(lib.nnd_midas_up2x_pw_pack(Cout, Cin, _p(wh), _p(bh), _p(blob)), "midas_up2x_pw_pack")
+    blob = blob.to(d)
+    y = torch.empty((N, Cout, 2 * h, 2 * w), dtype=torch.float32, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_midas_up2x_pw(Cout, Cin, _p(blob), _p(x), _p(y), N, h, w, _stream(d)), "midas_up2x_pw")
+    return y
+
+
+def midas_head_pack(w2: torch.Tensor, b2: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, device) -> torch.Tensor:
+    Cc = w2.shape[0]
+    blob = _pack_host(int(lib.nnd_midas_head_packed_floats(Cc)), "midas_head_packed_floats")
+    host = [_host(t) for t in (w2, b2, w4, b4)]  # kept alive across the call
+    check(lib.nnd_midas_head_pack(Cc, *[_p(t) for t in host], _p(blob)), "midas_head_pack")
+    return blob.to(device)
+
+
+def midas_head(t: torch.Tensor, packed: torch.Tensor, want_pre: bool = False):
+    """relu(conv1x1_{C->1}(relu(conv3x3(up2x(t)) + b2)) + b4) in one kernel: (N,C,h,w) -> (N,1,2h,2w) [, the map before the last
+    ReLU]; packed = midas_head_pack(...)."""
+    d = _dev(t, packed)
+    t = t.contiguous()
+    N, Cc, h, w = t.shape
+    depth = torch.empty((N, 1, 2 * h, 2 * w), dtype=torch.float32, device=d)
+    pre = torch.empty_like(depth) if want_pre else None
+    with torch.cuda.device(d):
+        check(lib.nnd_midas_head(Cc, _p(packed), _p(t), _p(depth), _p(pre), N, h, w, _stream(d)), "midas_head")
+    return (depth, pre) if want_pre else depth
+
+
+def midas_conv_add(x: torch.Tensor, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """feat + relu(conv k x k (1 or 3, padding k / 2)(x) + bias): the activation before the addition."""
+    d = _dev(x, feat)
+    x, feat = x.contiguous(), feat.contiguous()
+    N, Cin, H, W = x.shape
+    Cout, k = weight.shape[0], weight.shape[-1]
+    if tuple(feat.shape) != (N, Cout, H, W):
+        raise NndError(f"midas_conv_add: feat {tuple(feat.shape)} must be {(N, Cout, H, W)}")
+    blob = _pack_host(int(lib.nnd_mbv3_pointwise_packed_floats(Cout, Cin, k)), "mbv3_pointwise_packed_floats")
+    wh, bh = _host(weight), _host(bias)  # kept alive across the call
+    check(lib.nnd_mbv3_pointwise_pack(Cout, Cin, k, _p(wh), _p(bh), _p(blob)), "mbv3_pointwise_pack")
+    blob = blob.to(d)
+    y = torch.empty_like(feat)
+    with torch.cuda.device(d):
+        check(lib.nnd_midas_conv_add(Cout, Cin, k, _p(blob), _p(x), _p(feat), _p(y), N, H, W, _stream(d)), "midas_conv_add")
+    return y
 
 
 def softargmin_disparity(logits: torch.Tensor) -> torch.Tensor:
