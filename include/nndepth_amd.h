@@ -532,6 +532,40 @@ int64_t nnd_epe_metrics_workspace_bytes(void);
 int nnd_epe_metrics(const float* disp_gt, const float* disp_pred, const unsigned char* valid_mask, int B, int C, int H, int W,
                     float max_flow, const float* thresholds_host, int num_thresholds, void* workspace, float* out, void* stream);
 
+/* ------------------------------------------------------------- scene types on the device (additions within 104)
+ * Disparity / Depth / Frame of nndepth/scene: get_view (disparity.py:187-233, depth.py:166-216) and resize
+ * (disparity.py:9-75,113-185, depth.py:9-63,85-146, frame.py:47-99).  Masks are bytes (torch.bool or torch.uint8) of the map's shape.
+ * `kind`: 0 = disparity (v = |data|, 0 where mask == 1), 1 = depth (v = data, the minimum over mask == 1 where mask != 1).
+ * nnd_view_range   : range[b] = {min, max} of v over all channels of batch element b (depth: over its valid pixels, which is the
+ *     range of the filled map and, in range[b][0], the fill value).  `workspace` = nnd_view_range_workspace_bytes(B) device bytes,
+ *     `range` = 2 * B device floats.  Deterministic two-pass reduction.
+ * nnd_colorize     : out (B,H,W,3) uint8 = table[idx(channel 0)], the closed form of matplotlib's Normalize(clip=True) + Colormap:
+ *     lo = has_lo ? lo : range[b][0], hi likewise; x = clip((double)v, lo, hi); n = lo == hi ? 0 : (x - lo) / (hi - lo);
+ *     reverse: n = 1 - n; t = n * N; idx = t == N ? N - 1 : (int)t, clamped into the table.  `table` = N * 3 device bytes,
+ *     2 <= N <= 4096.  `range` may be NULL when both bounds are given and no depth mask needs the fill value.  Both bounds given
+ *     with lo > hi is refused.  Non-finite values in the map are outside the contract: they get some colour of the table.
+ * nnd_pool_abs     : dst (B,C,H/kh,W/kw) = max (is_min: min) of |src| over non-overlapping kh x kw windows (the ragged edge is
+ *     dropped), negated if `negate`, then (x * mul) / div if `rescale` (data * W_new / W_old).  `indices` (optional, int64): the
+ *     plane-local offset y * W + x of the first extreme in row-major window order; a NaN wins (max_pool2d).  `mask` / `mask_out`
+ *     (optional, together): mask_out[b,c,i] = mask[indices[b,c,i]] counted from the start of the whole mask — every plane reads
+ *     plane 0, as the reference's flatten()[indices.flatten()] does.  `finite_out` (optional): isfinite(dst) as bytes.
+ * nnd_resize_bilinear : F.interpolate(src (planes,h,w), (H,W), mode="bilinear", align_corners) with the tap arithmetic of
+ *     nnd_resize_normalize; src float, or bytes if src_is_u8.  Optional outputs, at least one: dst (float; (x * mul) / div first
+ *     if `rescale`), u8_out (u8_mode 1: x != 0; 2: the C cast of torch's .type(torch.uint8)), finite_out (isfinite(x)).
+ * nnd_depth_inverse   : dst = clamp(1 / (src + eps)): max first, then min, each only if has_*; a NaN stays.                    */
+int64_t nnd_view_range_workspace_bytes(int B);
+int nnd_view_range(const float* data, const unsigned char* mask, int kind, int B, int C, int H, int W, void* workspace, float* range,
+                   void* stream);
+int nnd_colorize(const float* data, const unsigned char* mask, int kind, int B, int C, int H, int W, const float* range, int has_lo,
+                 double lo, int has_hi, double hi, int reverse, const unsigned char* table, int N, unsigned char* out, void* stream);
+int nnd_pool_abs(const float* src, float* dst, int64_t* indices, const unsigned char* mask, unsigned char* mask_out,
+                 unsigned char* finite_out, int B, int C, int H, int W, int kh, int kw, int is_min, int negate, int rescale, float mul,
+                 float div, void* stream);
+int nnd_resize_bilinear(const void* src, int src_is_u8, float* dst, unsigned char* u8_out, int u8_mode, unsigned char* finite_out,
+                        int planes, int h, int w, int H, int W, int align_corners, int rescale, float mul, float div, void* stream);
+int nnd_depth_inverse(const float* src, float* dst, int64_t n, float eps, int has_max, float clip_max, int has_min, float clip_min,
+                      void* stream);
+
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58
  * (no masks).  The reference's (N, H*W, C) tokens are the (N,C,H,W) maps transposed, so every nn.Linear is a 1x1 conv of

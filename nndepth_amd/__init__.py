@@ -11,7 +11,7 @@ __all__ = ["weightgen"]
 
 def __getattr__(name):
     # lazy: `import nndepth_amd` must not dlopen on tooling that only wants weightgen
-    if name in ("ops", "cost_volume", "blocks", "upsample", "encoder", "raft_stereo", "_lib"):
+    if name in ("ops", "cost_volume", "blocks", "upsample", "encoder", "raft_stereo", "scene", "_lib"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -172,6 +172,12 @@ SIGNATURES = {
     "nnd_replicate_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_epe_metrics_workspace_bytes": (C.c_int64, []),
     "nnd_epe_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_float, C.POINTER(C.c_float), _I, _P, _P, _P]),
+    "nnd_view_range_workspace_bytes": (C.c_int64, [_I]),
+    "nnd_view_range": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "nnd_colorize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, C.c_double, _I, C.c_double, _I, _P, _I, _P, _P]),
+    "nnd_pool_abs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
+    "nnd_resize_bilinear": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
+    "nnd_depth_inverse": (_I, [_P, _P, C.c_int64, C.c_float, _I, C.c_float, _I, C.c_float, _P]),
     "nnd_loftr_packed_floats": (C.c_int64, [_I, _I]),
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),

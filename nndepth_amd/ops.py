@@ -1857,3 +1857,112 @@ def volume_gate_(vol: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(d):
         check(lib.nnd_volume_gate(_p(vol), _p(logits), N, Cc, Dp - 2, H, W, _stream(d)), "volume_gate")
     return vol
+
+
+# ------------------------------------------------------------- scene types (csrc/scene.hip; the drop-in classes are in scene.py)
+def _mask_bytes(mask: Optional[torch.Tensor], like: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """A bool / uint8 mask of `like`'s shape on `like`'s device, as contiguous bytes (None stays None)."""
+    if mask is None:
+        return None
+    if mask.device != like.device:
+        raise NndError(f"{what}: the mask is on {mask.device}, the map on {like.device} (no CPU fallback exists)")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise NndError(f"{what}: masks are torch.bool or torch.uint8; got {mask.dtype}")
+    if mask.numel() != like.numel():
+        raise NndError(f"{what}: the mask has {mask.numel()} elements, the map {like.numel()}")
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def view_range(data: torch.Tensor, mask: Optional[torch.Tensor], kind: int) -> torch.Tensor:
+    """(B,2) device floats: min and max per batch element of the map `get_view` colours (kind 0: |disparity| with occluded
+    pixels at 0; kind 1: depth over its valid pixels)."""
+    d = _dev(data)
+    data = data.contiguous()
+    B, Cc, H, W = data.shape
+    m = _mask_bytes(mask, data, "view_range")
+    ws = torch.empty(max(1, int(lib.nnd_view_range_workspace_bytes(B))), dtype=torch.uint8, device=d)
+    rng = torch.empty((B, 2), dtype=torch.float32, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_view_range(_p(data), _p(m), kind, B, Cc, H, W, _p(ws), _p(rng), _stream(d)), "view_range")
+    return rng
+
+
+def colorize(data: torch.Tensor, mask: Optional[torch.Tensor], kind: int, table: torch.Tensor, lo: Optional[float] = None,
+             hi: Optional[float] = None, reverse: bool = False) -> torch.Tensor:
+    """(B,H,W,3) uint8 on the device: channel 0 of `data` (B,C,H,W) through the (N,3) uint8 device `table`; a bound that is None
+    is the batch element's own (view_range).  No host synchronisation."""
+    d = _dev(data)
+    data = data.contiguous()
+    B, Cc, H, W = data.shape
+    m = _mask_bytes(mask, data, "colorize")
+    if table.device != d or table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 3:
+        raise NndError(f"colorize: the table must be (N,3) torch.uint8 on {d}; got {tuple(table.shape)} {table.dtype} on {table.device}")
+    table = table.contiguous()
+    rng = view_range(data, m, kind) if (lo is None or hi is None or (kind == 1 and m is not None)) else None
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_colorize(_p(data), _p(m), kind, B, Cc, H, W, _p(rng), int(lo is not None), float(lo or 0.0), int(hi is not None),
+                               float(hi or 0.0), int(bool(reverse)), _p(table), table.shape[0], _p(out), _stream(d)), "colorize")
+    return out
+
+
+def pool_abs(x: torch.Tensor, kernel: Tuple[int, int], is_min: bool, negate: bool, rescale: Optional[Tuple[float, float]] = None,
+             mask: Optional[torch.Tensor] = None, indices: bool = False, finite: bool = False):
+    """max / min of |x| over non-overlapping windows -> (values, int64 indices or None, gathered mask bytes or None,
+    isfinite bytes or None); see nnd_pool_abs."""
+    d = _dev(x)
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    kh, kw = int(kernel[0]), int(kernel[1])
+    if kh < 1 or kw < 1:
+        raise NndError(f"pool_abs: a {H}x{W} map cannot be pooled to a larger size (window {kh}x{kw})")
+    m = _mask_bytes(mask, x, "pool_abs")
+    shape = (B, Cc, H // kh, W // kw)
+    y = torch.empty(shape, dtype=torch.float32, device=d)
+    idx = torch.empty(shape, dtype=torch.int64, device=d) if indices else None
+    mo = torch.empty(shape, dtype=torch.uint8, device=d) if m is not None else None
+    fo = torch.empty(shape, dtype=torch.uint8, device=d) if finite else None
+    mul, div = (float(rescale[0]), float(rescale[1])) if rescale else (1.0, 1.0)
+    with torch.cuda.device(d):
+        check(lib.nnd_pool_abs(_p(x), _p(y), _p(idx), _p(m), _p(mo), _p(fo), B, Cc, H, W, kh, kw, int(is_min), int(negate),
+                               int(rescale is not None), mul, div, _stream(d)), "pool_abs")
+    return y, idx, mo, fo
+
+
+def resize_bilinear(x: torch.Tensor, size: Tuple[int, int], align_corners: bool = False,
+                    rescale: Optional[Tuple[float, float]] = None, finite: bool = False, u8_mode: int = 0):
+    """F.interpolate(x, size, mode="bilinear", align_corners=...) of a (B,C,h,w) map.  fp32 x -> (values, isfinite bytes or
+    None), values = (v * rescale[0]) / rescale[1] if given.  A bool / uint8 x (an occlusion mask) -> its bytes after the
+    reference's float round trip: u8_mode 1 = non-zero (bool), 2 = truncated (uint8)."""
+    if x.device.type != "cuda":
+        raise NndError(f"resize_bilinear: the map must be on the HIP device; got {x.device} (no CPU fallback exists)")
+    H, W = int(size[0]), int(size[1])
+    with torch.cuda.device(x.device):
+        if x.dtype in (torch.bool, torch.uint8):
+            src = _mask_bytes(x, x, "resize_bilinear")
+            B, Cc, h, w = src.shape
+            out = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=x.device)
+            check(lib.nnd_resize_bilinear(_p(src), 1, None, _p(out), int(u8_mode), None, B * Cc, h, w, H, W, int(bool(align_corners)), 0,
+                                          1.0, 1.0, _stream(x.device)), "resize_bilinear")
+            return out
+        d = _dev(x)
+        x = x.contiguous()
+        B, Cc, h, w = x.shape
+        y = torch.empty((B, Cc, H, W), dtype=torch.float32, device=d)
+        fo = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=d) if finite else None
+        mul, div = (float(rescale[0]), float(rescale[1])) if rescale else (1.0, 1.0)
+        check(lib.nnd_resize_bilinear(_p(x), 0, _p(y), None, 0, _p(fo), B * Cc, h, w, H, W, int(bool(align_corners)),
+                                      int(rescale is not None), mul, div, _stream(d)), "resize_bilinear")
+    return y, fo
+
+
+def depth_inverse(x: torch.Tensor, clip_max: Optional[float], clip_min: Optional[float], eps: float) -> torch.Tensor:
+    """clamp(1 / (x + eps)): max first, then min (Depth.inverse)."""
+    d = _dev(x)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    with torch.cuda.device(d):
+        check(lib.nnd_depth_inverse(_p(x), _p(y), x.numel(), float(eps), int(clip_max is not None), float(clip_max or 0.0),
+                                    int(clip_min is not None), float(clip_min or 0.0), _stream(d)), "depth_inverse")
+    return y
