@@ -1,12 +1,11 @@
-// MobileNetV3-Large backbone pieces shared by the two models that run it: the encoder side of IGEVStereoMBNet (mbv3.hip,
+// The MobileNetV3-Large backbone shared by the two models that run it: the encoder side of IGEVStereoMBNet (mbv3.hip,
 // nnd_mbv3_forward: two frames, stages 2..5 on the left frames only) and MobileNetV3DepthModel (midas.hip, nnd_midas_forward: one
-// frame tensor, taps of stages 1, 2, 4, 5).  The kernels and launchers live in mbv3.hip; this header only declares them.
+// frame tensor, taps of stages 1, 2, 4, 5).  The block table, the kernels and the walk live in mbv3.hip; the layer plan is
+// enc_plan.h's.
 #pragma once
-#include "common.h"
+#include "enc_plan.h"
 
 #include <algorithm>
-#include <cstdint>
-#include <vector>
 
 namespace nnd {
 
@@ -23,38 +22,22 @@ struct MbBlock {
 extern const MbBlock MB_BLOCKS[];
 extern const int MB_NBLOCKS;
 constexpr int MB_STEM_C = 16;
+constexpr int MB_NSTAGES = 6;  // stages 0..5 (stage 6's output is never used)
 
-enum MbKind { MB_STEM = 0, MB_DW = 1, MB_PW = 2, MB_SE_R = 3, MB_SE_E = 4, MB_PROJ = 5 };
+enum MbKind { MB_SE_R = 3, MB_SE_E = 4, MB_PROJ = 5 };  // after ENC_STEM, ENC_DW, ENC_MFMA
 
-struct MbLayer {
-    int kind, cin, cout, k, stride, act;
-    ConvLayer cl;         // MB_PW (1x1 or 3x3, stride 1): conv_mfma layout
-    int64_t off, floats;  // blob offset / size (the others: weights then bias)
-};
-
-struct MbPlan {
-    std::vector<MbLayer> layers;
-    int64_t total = 0;
-};
-
-int64_t mb_align(int64_t n);
-// appends one layer to the plan (blob offsets 64-float aligned); MB_PW: the conv_mfma layout of a k x k stride-1 conv
-void mb_add(MbPlan& p, int kind, int cin, int cout, int k, int stride, int act);
 // stem | per block: [IR: expand 1x1] depthwise [SE reduce, SE expand] project 1x1 — the backbone's layers in pack order
-void mb_plan_backbone(MbPlan& p);
-void pack_pw(const MbLayer& l, const float* w, const float* b, float* base);
+void mb_plan_backbone(EncPlan& p);
 
-int run_dw(const MbLayer& l, const float* blob, const float* x, float* y, double* partial, int N, int Hin, int Win, hipStream_t st);
-int run_se(const MbLayer& lr, const MbLayer& le, const float* blob, float* y, const double* partial, float* gate, int N, int H, int W,
-           hipStream_t st);
-int run_pw(const MbLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int64_t ybs, const float* res, int N, int H, int W,
-           hipStream_t st);
+// 1x1 / 3x3 stride-1 conv on conv_mfma (NCHW in / out, dense): y = act(conv + bias); res: the residual (same shape as y), MB_NONE
+// layers only
+int mb_run_pw(const EncLayer& l, const float* blob, const float* x, float* y, const float* res, int N, int H, int W, hipStream_t st);
 
-// The backbone on ONE frame tensor x (B,3,H,W), stages 0..5, with the outputs of stages 1, 2, 4, 5 written to taps[0..3]
-// (B, 24 / 40 / 112 / 160, ceil(H / 4) ... ceil(H / 32)).  `layers`: the plan's backbone layers from index 0 on; workspace:
-// mb_single_ws(B, H, W) floats.  The same launchers, kernels and per-layer split-K as nnd_mbv3_forward.
-int64_t mb_single_ws(int B, int H, int W);
-int mb_single_forward(const MbPlan& p, const float* packed, const float* x, float* const* taps, float* workspace, int B, int H, int W,
-                      hipStream_t st);
+// The backbone, stages 0..5.  Samples n < nsplit of the stem read frame1 (B,3,H,W), the others frame2; stages 0..1 run on n01
+// samples, stages 2..5 on the first n25 of them.  keep[s]: where stage s's output goes ((n, C_s, ceil(H / 2^..), ..) dense), or
+// nullptr for the ping-pong buffers.  `p`: a plan whose first layers are mb_plan_backbone's; workspace: mb_walk_ws(...) floats.
+int64_t mb_walk_ws(int n01, int n25, int H, int W);
+int mb_walk(const EncPlan& p, const float* packed, const float* frame1, const float* frame2, int nsplit, int n01, int n25,
+            float* const* keep, float* workspace, int H, int W, hipStream_t st);
 
 }  // namespace nnd

@@ -17,10 +17,13 @@
 //                                                                                         summed in float64)
 // Only the right frames' stage-1 map is needed (fmap2): stages 0-1 run on both frames, stages 2-5 on the left frames only, and
 // stage 6 (whose output the reference discards) never runs.  Eval BatchNorm is per sample, so this changes no output.
-// Every conv_mfma launch fixes its split-K factor per layer (2 from two K chunks on, else 1; as repvit.hip), so a pair's maps do not
-// depend on the batch it runs in.  The SE mean is reduced in a fixed order (workgroup tree, then the workgroups in order): no
+// Every conv_mfma launch fixes its split-K factor per layer (enc_plan.h: enc_run_mfma), so a pair's maps do not depend on the batch it
+// runs in.  The SE mean is reduced in a fixed order (workgroup tree, then the workgroups in order): no
 // float atomics, bit-reproducible.  Activations are NCHW in the caller's workspace.
+// The layer plan, the packer and the conv_mfma launcher are enc_plan.h's, shared with repvit.hip and midas.hip; the backbone walk
+// (mb_walk, declared in mbv3.h) also serves midas.hip; the depthwise tap loop and the stem's patch gather are enc_valu.h's.
 #include "mbv3.h"
+#include "enc_valu.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,7 +32,6 @@
 #include <vector>
 
 namespace nnd {
-
 
 // torch's hardswish / hardsigmoid: x * min(max(x + 3, 0), 6) / 6, min(max(x + 3, 0), 6) / 6
 __device__ __forceinline__ double mb_act(double v, int act) {
@@ -58,18 +60,7 @@ __global__ void __launch_bounds__(MB_DW_T) mbv3_dw_kernel(const float* __restric
         const float* xp = x + ((long)n * C + c) * Hin * Win;
         const float* wp = w + (long)c * K * K;
         const int iy0 = oy * stride - pt, ix0 = ox * stride - pl;
-        double acc = 0.0;
-#pragma unroll
-        for (int dy = 0; dy < K; ++dy) {
-            const int iy = iy0 + dy;
-            if (iy < 0 || iy >= Hin) continue;
-#pragma unroll
-            for (int dx = 0; dx < K; ++dx) {
-                const int ix = ix0 + dx;
-                if (ix < 0 || ix >= Win) continue;
-                acc = fma((double)wp[dy * K + dx], (double)xp[(long)iy * Win + ix], acc);
-            }
-        }
+        const double acc = dw_taps<K>(xp, wp, iy0, ix0, Hin, Win);
         out = (float)mb_act(acc + (double)bias[c], act);
         y[((long)n * C + c) * Ho * Wo + idx] = out;
     }
@@ -140,16 +131,7 @@ __global__ void __launch_bounds__(256) mbv3_stem_kernel(const float* __restrict_
     const int oy = idx / Wo, ox = idx - oy * Wo;
     const float* xp = n < nsplit ? x + (long)n * 3 * Hin * Win : x1 + (long)(n - nsplit) * 3 * Hin * Win;
     float in[27];
-#pragma unroll
-    for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int iy = oy * 2 - pt + dy, ix = ox * 2 - pl + dx;
-                const bool ok = iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
-                in[(ci * 3 + dy) * 3 + dx] = ok ? xp[((long)ci * Hin + iy) * Win + ix] : 0.f;
-            }
+    stem_gather(xp, oy, ox, 2, pt, pl, Hin, Win, in);
     float* yp = y + (long)n * MB_STEM_C * Ho * Wo + idx;
 #pragma unroll 4
     for (int co = 0; co < MB_STEM_C; ++co) {
@@ -223,37 +205,6 @@ const MbBlock MB_BLOCKS[] = {
 const int MB_NBLOCKS = (int)(sizeof(MB_BLOCKS) / sizeof(MB_BLOCKS[0]));
 constexpr int MB_S1_C = 24;  // stage 1's width: fnet_proj / cnet_proj input
 
-
-
-
-void mb_add(MbPlan& p, int kind, int cin, int cout, int k, int stride, int act) {
-    MbLayer l{};
-    l.kind = kind; l.cin = cin; l.cout = cout; l.k = k; l.stride = stride; l.act = act;
-    l.off = p.total;
-    if (kind == MB_PW) {
-        ConvLayer L;
-        L.KH = k; L.KW = k; L.Cin = cin; L.Cout = cout; L.stride = 1; L.arith = 0;
-        // 1x1: 32-channel K chunks (conv_ci_t would take 128 from Cin = 128 on), so that split-K 2 applies from Cin = 64 (as repvit.hip)
-        L.CI_T = k == 1 ? 32 : conv_ci_t(k, k, cin, 1, cout);
-        L.nchunks = cdiv(cin, L.CI_T);
-        L.ncb = cdiv(cout, 32);
-        int64_t off = 0;
-        L.w_off = off; off += L.w_floats();
-        L.b_off = off; off += L.b_floats();
-        L.s_off = off; off += L.b_floats();
-        l.cl = L;
-        l.floats = off;
-    } else if (kind == MB_STEM || kind == MB_PROJ) {
-        l.floats = (int64_t)cout * cin * k * k + cout;
-    } else if (kind == MB_DW) {
-        l.floats = (int64_t)cout * k * k + cout;
-    } else {  // SE reduce (rd, C) / expand (C, rd) 1x1 with bias
-        l.floats = (int64_t)cout * cin + cout;
-    }
-    p.total += (l.floats + 63) / 64 * 64;
-    p.layers.push_back(l);
-}
-
 static int mb_check(const nnd_mbv3_desc* d) {
     NND_REQUIRE(d, "mbv3: null descriptor");
     NND_REQUIRE(d->struct_size == (int)sizeof(nnd_mbv3_desc), "mbv3: struct_size %d != sizeof(nnd_mbv3_desc) %d (header mismatch)",
@@ -264,46 +215,93 @@ static int mb_check(const nnd_mbv3_desc* d) {
     return NND_OK;
 }
 
-// layer order (= the tensor order of nnd_mbv3_pack): stem | per block: [IR: expand 1x1] depthwise [SE reduce, SE expand] project 1x1 |
-// fnet_proj 3x3 | cnet_proj 3x3
-void mb_plan_backbone(MbPlan& p) {
-    mb_add(p, MB_STEM, 3, MB_STEM_C, 3, 2, MB_HSWISH);
+static void mb_add_dense(EncPlan& p, int kind, int cin, int cout, int k, int stride, int act) {  // stem / projection: (cout, cin, k, k) + bias
+    enc_add_raw(p, kind, cin, cout, k, stride, act, (int64_t)cout * cin * k * k + cout);
+}
+
+void mb_plan_backbone(EncPlan& p) {
+    mb_add_dense(p, ENC_STEM, 3, MB_STEM_C, 3, 2, MB_HSWISH);
     for (int i = 0; i < MB_NBLOCKS; ++i) {
         const MbBlock& b = MB_BLOCKS[i];
-        if (b.ir) mb_add(p, MB_PW, b.cin, b.mid, 1, 1, b.act);
-        mb_add(p, MB_DW, b.mid, b.mid, b.k, b.stride, b.act);
-        if (b.rd) {
-            mb_add(p, MB_SE_R, b.mid, b.rd, 1, 1, MB_RELU);
-            mb_add(p, MB_SE_E, b.rd, b.mid, 1, 1, MB_NONE);
+        if (b.ir) enc_add_mfma(p, b.cin, b.mid, 1, 1, b.act);
+        enc_add_raw(p, ENC_DW, b.mid, b.mid, b.k, b.stride, b.act, (int64_t)b.mid * b.k * b.k + b.mid);
+        if (b.rd) {  // SE reduce (rd, C) / expand (C, rd) 1x1 with bias
+            enc_add_raw(p, MB_SE_R, b.mid, b.rd, 1, 1, MB_RELU, (int64_t)b.rd * b.mid + b.rd);
+            enc_add_raw(p, MB_SE_E, b.rd, b.mid, 1, 1, MB_NONE, (int64_t)b.mid * b.rd + b.mid);
         }
-        mb_add(p, MB_PW, b.mid, b.cout, 1, 1, MB_NONE);
+        enc_add_mfma(p, b.mid, b.cout, 1, 1, MB_NONE);
     }
 }
 
-static int mb_plan(const nnd_mbv3_desc* d, MbPlan* p) {
+// layer order (= the tensor order of nnd_mbv3_pack): the backbone (mb_plan_backbone) | fnet_proj 3x3 | cnet_proj 3x3
+static int mb_plan(const nnd_mbv3_desc* d, EncPlan* p) {
     if (int rc = mb_check(d)) return rc;
-    p->layers.clear();
-    p->total = 0;
     mb_plan_backbone(*p);
-    mb_add(*p, MB_PROJ, MB_S1_C, d->fnet_dim, 3, 1, MB_RELU);
-    mb_add(*p, MB_PROJ, MB_S1_C, d->cnet_dim, 3, 1, MB_RELU);
+    mb_add_dense(*p, MB_PROJ, MB_S1_C, d->fnet_dim, 3, 1, MB_RELU);
+    mb_add_dense(*p, MB_PROJ, MB_S1_C, d->cnet_dim, 3, 1, MB_RELU);
     return NND_OK;
 }
 
-int64_t mb_align(int64_t n) { return (n + 63) / 64 * 64; }
+// ------------------------------------------------------------------------------------------ launchers
+static int run_dw(const float* x, const float* w, const float* bias, float* y, double* partial, int N, int C, int Hin, int Win, int k,
+                  int stride, int act, hipStream_t st) {
+    const int Ho = same_out(Hin, stride), Wo = same_out(Win, stride);
+    const int pt = stride == 1 ? k / 2 : same_pad_before(Hin, k, 2), pl = stride == 1 ? k / 2 : same_pad_before(Win, k, 2);
+    dim3 grid((unsigned)cdiv(Ho * Wo, MB_DW_T), (unsigned)C, (unsigned)N);
+    if (k == 3)
+        hipLaunchKernelGGL(mbv3_dw_kernel<3>, grid, dim3(MB_DW_T), 0, st, x, y, w, bias, partial, C, Hin, Win, Ho, Wo, stride, pt, pl, act);
+    else
+        hipLaunchKernelGGL(mbv3_dw_kernel<5>, grid, dim3(MB_DW_T), 0, st, x, y, w, bias, partial, C, Hin, Win, Ho, Wo, stride, pt, pl, act);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
 
-// workspace: running activations A, B (ping-pong), expanded E, depthwise D, stage 1's map of both frames, SE gate, SE partials
+static int run_se(float* y, const double* partial, const float* wr, const float* br, const float* we, const float* be, float* gate, int N,
+                  int C, int rd, int H, int W, hipStream_t st) {
+    const int P = H * W;
+    hipLaunchKernelGGL(mbv3_se_kernel, dim3((unsigned)N), dim3(256), 0, st, partial, cdiv(P, MB_DW_T), P, wr, br, we, be, gate, C, rd);
+    NND_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mbv3_gate_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)C, (unsigned)N), dim3(256), 0, st, y, gate, C, P);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+static int run_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W,
+                    hipStream_t st) {
+    const int Ho = same_out(H, 2), Wo = same_out(W, 2);
+    hipLaunchKernelGGL(mbv3_stem_kernel, dim3((unsigned)cdiv(Ho * Wo, 256), 1, (unsigned)N), dim3(256), 0, st, x, x1, nsplit, y, w, bias, H,
+                       W, Ho, Wo, same_pad_before(H, 3, 2), same_pad_before(W, 3, 2));
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+static int run_proj(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int H, int W, hipStream_t st) {
+    dim3 grid((unsigned)cdiv(H * W, 256), (unsigned)cdiv(Cout, MB_PJ_CO), (unsigned)N);
+    hipLaunchKernelGGL(mbv3_proj_kernel, grid, dim3(256), 0, st, x, (int64_t)Cin * H * W, y, w, bias, Cin, Cout, H, W);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+int mb_run_pw(const EncLayer& l, const float* blob, const float* x, float* y, const float* res, int N, int H, int W, hipStream_t st) {
+    const int epi = l.act == MB_RELU ? EPI_RELU : l.act == MB_HSWISH ? EPI_HSWISH : EPI_AFFINE;
+    return enc_run_mfma(l, blob, x, (int64_t)l.cin * H * W, y, (int64_t)l.cout * H * W, res, epi, 0, N, H, W, H, W, st);
+}
+
+// ------------------------------------------------------------------------------------------ the backbone walk
+// workspace: running activations A, B (ping-pong), expanded E, depthwise D, SE gate, SE partials (doubles); s1: stage 1's map of
+// the n01 samples (the caller's own region where it keeps it: nnd_mbv3_forward)
 struct MbWs {
-    int64_t act, e, d, s1, gate, part;  // floats (part: doubles)
+    int64_t act, e, d, gate, part, s1;  // floats (part: doubles)
+    int64_t walk() const { return 2 * enc_align(act) + enc_align(e) + enc_align(d) + enc_align(gate) + 2 * enc_align(part); }
 };
 
-static MbWs mb_ws(int B, int H, int W) {
+static MbWs mb_ws(int n01, int n25, int H, int W) {
     MbWs r{};
     int h = same_out(H, 2), w = same_out(W, 2);
-    r.act = (int64_t)2 * B * MB_STEM_C * h * w;
+    r.act = (int64_t)n01 * MB_STEM_C * h * w;
     for (int i = 0; i < MB_NBLOCKS; ++i) {
         const MbBlock& b = MB_BLOCKS[i];
-        const int64_t nb = b.stage <= 1 ? 2 * B : B;
+        const int64_t nb = b.stage <= 1 ? n01 : n25;
         const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
         r.act = std::max(r.act, nb * b.cout * ho * wo);
         r.e = std::max(r.e, nb * b.mid * h * w);
@@ -318,133 +316,46 @@ static MbWs mb_ws(int B, int H, int W) {
     return r;
 }
 
-int run_dw(const MbLayer& l, const float* blob, const float* x, float* y, double* partial, int N, int Hin, int Win,
-                  hipStream_t st) {
-    const int Ho = same_out(Hin, l.stride), Wo = same_out(Win, l.stride);
-    const int pt = l.stride == 1 ? l.k / 2 : same_pad_before(Hin, l.k, 2), pl = l.stride == 1 ? l.k / 2 : same_pad_before(Win, l.k, 2);
-    const float* w = blob + l.off;
-    const float* b = w + (int64_t)l.cout * l.k * l.k;
-    dim3 grid((unsigned)cdiv(Ho * Wo, MB_DW_T), (unsigned)l.cout, (unsigned)N);
-    if (l.k == 3)
-        hipLaunchKernelGGL(mbv3_dw_kernel<3>, grid, dim3(MB_DW_T), 0, st, x, y, w, b, partial, l.cout, Hin, Win, Ho, Wo, l.stride, pt, pl, l.act);
-    else
-        hipLaunchKernelGGL(mbv3_dw_kernel<5>, grid, dim3(MB_DW_T), 0, st, x, y, w, b, partial, l.cout, Hin, Win, Ho, Wo, l.stride, pt, pl, l.act);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
-}
+int64_t mb_walk_ws(int n01, int n25, int H, int W) { return mb_ws(n01, n25, H, W).walk(); }
 
-int run_se(const MbLayer& lr, const MbLayer& le, const float* blob, float* y, const double* partial, float* gate, int N, int H,
-                  int W, hipStream_t st) {
-    const int C = lr.cin, rd = lr.cout, P = H * W;
-    const float* wr = blob + lr.off;
-    const float* we = blob + le.off;
-    hipLaunchKernelGGL(mbv3_se_kernel, dim3((unsigned)N), dim3(256), 0, st, partial, cdiv(P, MB_DW_T), P, wr, wr + (int64_t)rd * C, we,
-                       we + (int64_t)C * rd, gate, C, rd);
-    NND_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mbv3_gate_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)C, (unsigned)N), dim3(256), 0, st, y, gate, C, P);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
-}
-
-// 1x1 / 3x3 stride-1 conv on conv_mfma (NCHW in / out); res: the residual (same shape as y), MB_NONE layers only
-int run_pw(const MbLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int64_t ybs, const float* res, int N, int H,
-                  int W, hipStream_t st) {
-    ConvIO io{};
-    io.src0 = Act{const_cast<float*>(x), xbs, l.cin};
-    io.out0 = Act{y, ybs, l.cout};
-    if (res) io.aux0 = Act{const_cast<float*>(res), ybs, l.cout};
-    io.Hin = H; io.Win = W;
-    io.force_ks = l.cl.nchunks >= 2 ? 2 : 1;  // fixed per layer: a pair's outputs do not depend on the batch
-    const int epi = l.act == MB_RELU ? EPI_RELU : l.act == MB_HSWISH ? EPI_HSWISH : EPI_AFFINE;
-    return launch_conv(l.cl, blob + l.off, io, epi, N, H, W, st);
-}
-
-static int run_proj(const MbLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int N, int H, int W, hipStream_t st) {
-    const float* w = blob + l.off;
-    dim3 grid((unsigned)cdiv(H * W, 256), (unsigned)cdiv(l.cout, MB_PJ_CO), (unsigned)N);
-    hipLaunchKernelGGL(mbv3_proj_kernel, grid, dim3(256), 0, st, x, xbs, y, w, w + (int64_t)l.cout * l.cin * 9, l.cin, l.cout, H, W);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
-}
-
-void pack_pw(const MbLayer& l, const float* w, const float* b, float* base) {
-    const float* ws[1] = {w};
-    const float* bs[1] = {b};
-    int co[1] = {l.cout};
-    pack_conv(l.cl, 1, ws, bs, co, base);
-    for (int c = 0; c < l.cl.ncb * 32; ++c) base[l.cl.s_off + c] = c < l.cout ? 1.f : 0.f;
-}
-
-// ------------------------------------------------------------------------------------------ one frame tensor (midas.hip)
-// workspace: running activations A, B (ping-pong), expanded E, depthwise D, SE gate, SE partials (doubles)
-struct MbWs1 {
-    int64_t act, e, d, gate, part;
-};
-
-static MbWs1 mb_ws1(int B, int H, int W) {
-    MbWs1 r{};
-    int h = same_out(H, 2), w = same_out(W, 2);
-    r.act = (int64_t)B * MB_STEM_C * h * w;
-    for (int i = 0; i < MB_NBLOCKS; ++i) {
-        const MbBlock& b = MB_BLOCKS[i];
-        const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
-        r.act = std::max(r.act, (int64_t)B * b.cout * ho * wo);
-        r.e = std::max(r.e, (int64_t)B * b.mid * h * w);
-        r.d = std::max(r.d, (int64_t)B * b.mid * ho * wo);
-        if (b.rd) {
-            r.gate = std::max(r.gate, (int64_t)B * b.mid);
-            r.part = std::max(r.part, (int64_t)B * b.mid * cdiv(ho * wo, MB_DW_T));
-        }
-        h = ho; w = wo;
-    }
-    return r;
-}
-
-int64_t mb_single_ws(int B, int H, int W) {
-    const MbWs1 r = mb_ws1(B, H, W);
-    return 2 * mb_align(r.act) + mb_align(r.e) + mb_align(r.d) + mb_align(r.gate) + 2 * mb_align(r.part);
-}
-
-int mb_single_forward(const MbPlan& p, const float* packed, const float* frame, float* const* taps, float* workspace, int B, int H, int W,
-                      hipStream_t st) {
-    const MbWs1 r = mb_ws1(B, H, W);
+int mb_walk(const EncPlan& p, const float* packed, const float* frame1, const float* frame2, int nsplit, int n01, int n25,
+            float* const* keep, float* workspace, int H, int W, hipStream_t st) {
+    const MbWs r = mb_ws(n01, n25, H, W);
     float* q = workspace;
-    float* bufA = q; q += mb_align(r.act);
-    float* bufB = q; q += mb_align(r.act);
-    float* E = q; q += mb_align(r.e);
-    float* D = q; q += mb_align(r.d);
-    float* gate = q; q += mb_align(r.gate);
+    float* bufA = q; q += enc_align(r.act);
+    float* bufB = q; q += enc_align(r.act);
+    float* E = q; q += enc_align(r.e);
+    float* D = q; q += enc_align(r.d);
+    float* gate = q; q += enc_align(r.gate);
     double* part = reinterpret_cast<double*>(q);  // 64-float aligned
     size_t li = 0;
-    auto L = [&]() -> const MbLayer& { return p.layers[li++]; };
+    auto L = [&]() -> const EncLayer& { return p.layers[li++]; };
+    auto P = [&](const EncLayer& l) { return packed + l.off; };                  // a raw layer's weights
+    auto Pb = [&](const EncLayer& l) { return packed + l.off + l.floats - l.cout; };  // ... its bias
     int rc;
     int h = same_out(H, 2), w = same_out(W, 2);
-    {
-        const MbLayer& l0 = L();
-        hipLaunchKernelGGL(mbv3_stem_kernel, dim3((unsigned)cdiv(h * w, 256), 1, (unsigned)B), dim3(256), 0, st, frame, frame, B, bufA,
-                           packed + l0.off, packed + l0.off + MB_STEM_C * 27, H, W, h, w, same_pad_before(H, 3, 2), same_pad_before(W, 3, 2));
-        NND_LAUNCH_CHECK();
-    }
+    const EncLayer& l0 = L();
+    if ((rc = run_stem(frame1, frame2, nsplit, P(l0), Pb(l0), bufA, n01, H, W, st))) return rc;
     const float* x = bufA;
     for (int i = 0; i < MB_NBLOCKS; ++i) {
         const MbBlock& b = MB_BLOCKS[i];
+        const int nb = b.stage <= 1 ? n01 : n25;  // nnd_mbv3_forward: stages 2..5 on the left frames (the first B samples) only
         const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
         const bool last = i + 1 == MB_NBLOCKS || MB_BLOCKS[i + 1].stage != b.stage;
-        float* keep = !last ? nullptr : b.stage == 1 ? taps[0] : b.stage == 2 ? taps[1] : b.stage == 4 ? taps[2] : b.stage == 5 ? taps[3] : nullptr;
-        float* out = keep ? keep : (x == bufA ? bufB : bufA);
+        float* out = last && keep[b.stage] ? keep[b.stage] : (x == bufA ? bufB : bufA);
         const float* dwin = x;
         if (b.ir) {
-            if ((rc = run_pw(L(), packed, x, (int64_t)b.cin * h * w, E, (int64_t)b.mid * h * w, nullptr, B, h, w, st))) return rc;
+            if ((rc = mb_run_pw(L(), packed, x, E, nullptr, nb, h, w, st))) return rc;
             dwin = E;
         }
-        if ((rc = run_dw(L(), packed, dwin, D, b.rd ? part : nullptr, B, h, w, st))) return rc;
+        const EncLayer& dw = L();
+        if ((rc = run_dw(dwin, P(dw), Pb(dw), D, b.rd ? part : nullptr, nb, dw.cout, h, w, dw.k, dw.stride, dw.act, st))) return rc;
         if (b.rd) {
-            const MbLayer& lr = L();
-            const MbLayer& le = L();
-            if ((rc = run_se(lr, le, packed, D, part, gate, B, ho, wo, st))) return rc;
+            const EncLayer& lr = L();
+            const EncLayer& le = L();
+            if ((rc = run_se(D, part, P(lr), Pb(lr), P(le), Pb(le), gate, nb, b.mid, b.rd, ho, wo, st))) return rc;
         }
-        if ((rc = run_pw(L(), packed, D, (int64_t)b.mid * ho * wo, out, (int64_t)b.cout * ho * wo, b.skip ? x : nullptr, B, ho, wo, st)))
-            return rc;
+        if ((rc = mb_run_pw(L(), packed, D, out, b.skip ? x : nullptr, nb, ho, wo, st))) return rc;
         x = out;
         h = ho; w = wo;
     }
@@ -465,16 +376,7 @@ int nnd_mbv3_depthwise(const float* x, const float* w, const float* bias, float*
     NND_REQUIRE(stride == 1 || stride == 2, "mbv3_depthwise: stride %d not built (1, 2)", stride);
     NND_REQUIRE(act >= MB_NONE && act <= MB_HSWISH, "mbv3_depthwise: activation %d (0 none, 1 ReLU, 2 hard-swish)", act);
     NND_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1 && C <= 65535 && N <= 65535, "mbv3_depthwise: bad size %dx%dx%dx%d", N, C, H, W);
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    const int pt = stride == 1 ? k / 2 : same_pad_before(H, k, 2), pl = stride == 1 ? k / 2 : same_pad_before(W, k, 2);
-    dim3 grid((unsigned)cdiv(Ho * Wo, MB_DW_T), (unsigned)C, (unsigned)N);
-    hipStream_t st = (hipStream_t)stream;
-    if (k == 3)
-        hipLaunchKernelGGL(mbv3_dw_kernel<3>, grid, dim3(MB_DW_T), 0, st, x, y, w, bias, partial, C, H, W, Ho, Wo, stride, pt, pl, act);
-    else
-        hipLaunchKernelGGL(mbv3_dw_kernel<5>, grid, dim3(MB_DW_T), 0, st, x, y, w, bias, partial, C, H, W, Ho, Wo, stride, pt, pl, act);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_dw(x, w, bias, y, partial, N, C, H, W, k, stride, act, (hipStream_t)stream);
 }
 
 int64_t nnd_mbv3_se_partials(int N, int C, int H, int W) {
@@ -487,13 +389,7 @@ int nnd_mbv3_se(float* y, const double* partial, const float* wr, const float* b
     NND_REQUIRE(y && partial && wr && br && we && be && gate, "mbv3_se: null pointer");
     NND_REQUIRE(N >= 1 && N <= 65535 && C >= 1 && C <= MB_SE_MAXC && rd >= 1 && rd <= MB_SE_MAXR && H >= 1 && W >= 1,
                 "mbv3_se: bad size N %d C %d rd %d %dx%d (C <= %d, rd <= %d)", N, C, rd, H, W, MB_SE_MAXC, MB_SE_MAXR);
-    const int P = H * W;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mbv3_se_kernel, dim3((unsigned)N), dim3(256), 0, st, partial, cdiv(P, MB_DW_T), P, wr, br, we, be, gate, C, rd);
-    NND_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mbv3_gate_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)C, (unsigned)N), dim3(256), 0, st, y, gate, C, P);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_se(y, partial, wr, br, we, be, gate, N, C, rd, H, W, (hipStream_t)stream);
 }
 
 int nnd_mbv3_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W,
@@ -502,38 +398,28 @@ int nnd_mbv3_stem(const float* x, const float* x1, int nsplit, const float* w, c
     NND_REQUIRE(N >= 1 && H >= 1 && W >= 1 && N <= 65535, "mbv3_stem: bad size %dx%dx%d", N, H, W);
     if (!x1) nsplit = N;
     NND_REQUIRE(nsplit >= 1 && nsplit <= N, "mbv3_stem: nsplit %d of %d", nsplit, N);
-    const int Ho = same_out(H, 2), Wo = same_out(W, 2);
-    hipLaunchKernelGGL(mbv3_stem_kernel, dim3((unsigned)cdiv(Ho * Wo, 256), 1, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x,
-                       x1 ? x1 : x, nsplit, y, w, bias, H, W, Ho, Wo, same_pad_before(H, 3, 2), same_pad_before(W, 3, 2));
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_stem(x, x1 ? x1 : x, nsplit, w, bias, y, N, H, W, (hipStream_t)stream);
 }
 
 int nnd_mbv3_proj(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int H, int W, void* stream) {
     NND_REQUIRE(x && w && bias && y, "mbv3_proj: null pointer");
     NND_REQUIRE(N >= 1 && N <= 65535 && Cin >= 1 && Cin <= MB_PJ_MAXCI && Cout >= 1 && H >= 1 && W >= 1,
                 "mbv3_proj: bad size N %d Cin %d Cout %d %dx%d (Cin <= %d)", N, Cin, Cout, H, W, MB_PJ_MAXCI);
-    hipLaunchKernelGGL(mbv3_proj_kernel, dim3((unsigned)cdiv(H * W, 256), (unsigned)cdiv(Cout, MB_PJ_CO), (unsigned)N), dim3(256), 0,
-                       (hipStream_t)stream, x, (int64_t)Cin * H * W, y, w, bias, Cin, Cout, H, W);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_proj(x, w, bias, y, N, Cin, Cout, H, W, (hipStream_t)stream);
 }
 
 int64_t nnd_mbv3_pointwise_packed_floats(int Cout, int Cin, int k) {
     NND_REQUIRE(Cout >= 1 && Cin >= 1, "mbv3_pointwise: channels %d -> %d", Cin, Cout);
     NND_REQUIRE(k == 1 || k == 3, "mbv3_pointwise: kernel %d not built (1, 3)", k);
-    MbPlan p;
-    mb_add(p, MB_PW, Cin, Cout, k, 1, MB_NONE);
-    return p.total;
+    return enc_align(enc_mfma_layer(Cin, Cout, k, 1, MB_NONE).floats);
 }
 
 int nnd_mbv3_pointwise_pack(int Cout, int Cin, int k, const float* w, const float* bias, float* packed_host) {
     NND_REQUIRE(Cout >= 1 && Cin >= 1 && w && bias && packed_host, "mbv3_pointwise_pack: bad argument");
     NND_REQUIRE(k == 1 || k == 3, "mbv3_pointwise_pack: kernel %d not built (1, 3)", k);
-    MbPlan p;
-    mb_add(p, MB_PW, Cin, Cout, k, 1, MB_NONE);
-    memset(packed_host, 0, sizeof(float) * p.total);
-    pack_pw(p.layers[0], w, bias, packed_host);
+    const EncLayer l = enc_mfma_layer(Cin, Cout, k, 1, MB_NONE);
+    memset(packed_host, 0, sizeof(float) * enc_align(l.floats));
+    enc_pack_mfma(l, w, bias, nullptr, packed_host);
     return NND_OK;
 }
 
@@ -543,19 +429,17 @@ int nnd_mbv3_pointwise(int Cout, int Cin, int k, const float* packed_dev, const 
     NND_REQUIRE(Cout >= 1 && Cin >= 1 && (k == 1 || k == 3), "mbv3_pointwise: %dx%d %d -> %d not built", k, k, Cin, Cout);
     NND_REQUIRE(act >= MB_NONE && act <= MB_HSWISH, "mbv3_pointwise: activation %d (0 none, 1 ReLU, 2 hard-swish)", act);
     NND_REQUIRE(!(act && residual), "mbv3_pointwise: an activation and a residual are not built together");
-    MbPlan p;
-    mb_add(p, MB_PW, Cin, Cout, k, 1, act);
-    return run_pw(p.layers[0], packed_dev, x, (int64_t)Cin * H * W, y, (int64_t)Cout * H * W, residual, N, H, W, (hipStream_t)stream);
+    return mb_run_pw(enc_mfma_layer(Cin, Cout, k, 1, act), packed_dev, x, y, residual, N, H, W, (hipStream_t)stream);
 }
 
 int nnd_mbv3_num_tensors(const nnd_mbv3_desc* desc) {
-    MbPlan p;
+    EncPlan p;
     if (int rc = mb_plan(desc, &p)) return rc;
     return 2 * (int)p.layers.size();
 }
 
 int64_t nnd_mbv3_packed_floats(const nnd_mbv3_desc* desc) {
-    MbPlan p;
+    EncPlan p;
     if (int rc = mb_plan(desc, &p)) return rc;
     return p.total;
 }
@@ -563,94 +447,38 @@ int64_t nnd_mbv3_packed_floats(const nnd_mbv3_desc* desc) {
 int64_t nnd_mbv3_workspace_floats(const nnd_mbv3_desc* desc, int B, int H, int W) {
     if (int rc = mb_check(desc)) return rc;
     NND_REQUIRE(B >= 1 && H >= 1 && W >= 1 && B <= 32767, "mbv3: bad size %dx%dx%d", B, H, W);
-    const MbWs r = mb_ws(B, H, W);
-    return 2 * mb_align(r.act) + mb_align(r.e) + mb_align(r.d) + mb_align(r.s1) + mb_align(r.gate) + 2 * mb_align(r.part);
+    const MbWs r = mb_ws(2 * B, B, H, W);
+    return r.walk() + enc_align(r.s1);
 }
 
 int nnd_mbv3_pack(const nnd_mbv3_desc* desc, const float* const* t, float* packed_host) {
-    MbPlan p;
+    EncPlan p;
     if (int rc = mb_plan(desc, &p)) return rc;
-    NND_REQUIRE(t && packed_host, "mbv3_pack: null pointer");
-    memset(packed_host, 0, sizeof(float) * p.total);
-    for (size_t i = 0; i < p.layers.size(); ++i) {
-        const MbLayer& l = p.layers[i];
-        const float *w = t[2 * i], *b = t[2 * i + 1];
-        NND_REQUIRE(w && b, "mbv3_pack: layer %zu: weight / bias missing", i);
-        float* base = packed_host + l.off;
-        if (l.kind == MB_PW) {
-            pack_pw(l, w, b, base);
-        } else {
-            const int64_t nw = l.floats - l.cout;
-            memcpy(base, w, sizeof(float) * nw);
-            memcpy(base + nw, b, sizeof(float) * l.cout);
-        }
-    }
-    return NND_OK;
+    return enc_pack(p, 2, t, packed_host, "mbv3_pack");
 }
 
 int nnd_mbv3_forward(const nnd_mbv3_desc* desc, const float* packed, const float* frame1, const float* frame2, float* fmap1, float* fmap2,
                      float* cnet1, float* guide0, float* guide1, float* guide2, float* workspace, int B, int H, int W, void* stream) {
-    MbPlan p;
+    EncPlan p;
     if (int rc = mb_plan(desc, &p)) return rc;
     NND_REQUIRE(packed && frame1 && frame2 && fmap1 && fmap2 && cnet1 && guide0 && guide1 && guide2 && workspace,
                 "mbv3_forward: null pointer");
     NND_REQUIRE(B >= 1 && H >= 1 && W >= 1 && B <= 32767, "mbv3_forward: bad size %dx%dx%d", B, H, W);
     hipStream_t st = (hipStream_t)stream;
-    const MbWs r = mb_ws(B, H, W);
-    float* q = workspace;
-    float* bufA = q; q += mb_align(r.act);
-    float* bufB = q; q += mb_align(r.act);
-    float* E = q; q += mb_align(r.e);
-    float* D = q; q += mb_align(r.d);
-    float* s1 = q; q += mb_align(r.s1);
-    float* gate = q; q += mb_align(r.gate);
-    double* part = reinterpret_cast<double*>(q);  // 64-float aligned
-    const int N = 2 * B;
-    size_t li = 0;
-    auto L = [&]() -> const MbLayer& { return p.layers[li++]; };
+    // stages 0..1 on both frames (2B samples), 2..5 on the left frames; stage 1's map of both frames lies behind the walk's workspace
+    float* s1 = workspace + mb_walk_ws(2 * B, B, H, W);
+    float* const keep[MB_NSTAGES] = {nullptr, s1, guide0, guide1, nullptr, guide2};
     int rc;
-    int h = same_out(H, 2), w = same_out(W, 2);
-    {
-        const MbLayer& l0 = L();
-        hipLaunchKernelGGL(mbv3_stem_kernel, dim3((unsigned)cdiv(h * w, 256), 1, (unsigned)N), dim3(256), 0, st, frame1, frame2, B, bufA,
-                           packed + l0.off, packed + l0.off + MB_STEM_C * 27, H, W, h, w, same_pad_before(H, 3, 2), same_pad_before(W, 3, 2));
-        NND_LAUNCH_CHECK();
-    }
-    const float* x = bufA;
-    for (int i = 0; i < MB_NBLOCKS; ++i) {
-        const MbBlock& b = MB_BLOCKS[i];
-        const int nb = b.stage <= 1 ? N : B;  // stages 2..5: the left frames (the first B samples) only
-        const int ho = same_out(h, b.stride), wo = same_out(w, b.stride);
-        const bool last = i + 1 == MB_NBLOCKS || MB_BLOCKS[i + 1].stage != b.stage;
-        float* keep = !last ? nullptr : b.stage == 1 ? s1 : b.stage == 2 ? guide0 : b.stage == 3 ? guide1 : b.stage == 5 ? guide2 : nullptr;
-        float* out = keep ? keep : (x == bufA ? bufB : bufA);
-        const float* dwin = x;
-        if (b.ir) {
-            if ((rc = run_pw(L(), packed, x, (int64_t)b.cin * h * w, E, (int64_t)b.mid * h * w, nullptr, nb, h, w, st))) return rc;
-            dwin = E;
-        }
-        if ((rc = run_dw(L(), packed, dwin, D, b.rd ? part : nullptr, nb, h, w, st))) return rc;
-        if (b.rd) {
-            const MbLayer& lr = L();
-            const MbLayer& le = L();
-            if ((rc = run_se(lr, le, packed, D, part, gate, nb, ho, wo, st))) return rc;
-        }
-        if ((rc = run_pw(L(), packed, D, (int64_t)b.mid * ho * wo, out, (int64_t)b.cout * ho * wo, b.skip ? x : nullptr, nb, ho, wo, st)))
-            return rc;
-        x = out;
-        h = ho; w = wo;
-        if (b.stage == 1 && last) {  // fnet_proj on both frames' stage-1 map, cnet_proj on the left frames'
-            const int h1 = h, w1 = w;
-            const MbLayer& fp = p.layers[p.layers.size() - 2];
-            const MbLayer& cp = p.layers[p.layers.size() - 1];
-            const int64_t sbs = (int64_t)MB_S1_C * h1 * w1;
-            if ((rc = run_proj(fp, packed, s1, sbs, fmap1, B, h1, w1, st))) return rc;
-            if ((rc = run_proj(fp, packed, s1 + B * sbs, sbs, fmap2, B, h1, w1, st))) return rc;
-            if ((rc = run_proj(cp, packed, s1, sbs, cnet1, B, h1, w1, st))) return rc;
-        }
-    }
-    NND_REQUIRE(li + 2 == p.layers.size(), "mbv3_forward: %zu of %zu layers consumed (plan mismatch)", li, p.layers.size());
-    return NND_OK;
+    if ((rc = mb_walk(p, packed, frame1, frame2, B, 2 * B, B, keep, workspace, H, W, st))) return rc;
+    // fnet_proj on both frames' stage-1 map, cnet_proj on the left frames'
+    const int h1 = same_out(same_out(H, 2), 2), w1 = same_out(same_out(W, 2), 2);
+    const EncLayer& fp = p.layers[p.layers.size() - 2];
+    const EncLayer& cp = p.layers[p.layers.size() - 1];
+    const int64_t sbs = (int64_t)MB_S1_C * h1 * w1;
+    const float *fw = packed + fp.off, *fb = fw + fp.floats - fp.cout, *cw = packed + cp.off, *cb = cw + cp.floats - cp.cout;
+    if ((rc = run_proj(s1, fw, fb, fmap1, B, MB_S1_C, fp.cout, h1, w1, st))) return rc;
+    if ((rc = run_proj(s1 + B * sbs, fw, fb, fmap2, B, MB_S1_C, fp.cout, h1, w1, st))) return rc;
+    return run_proj(s1, cw, cb, cnet1, B, MB_S1_C, cp.cout, h1, w1, st);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // MobileNetV3DepthModel (the reference's MiDaS-style monocular model, nndepth/models/midas/models/mobilenet_v3.py) in ONE C-ABI
-// call (nnd_midas_forward): the MobileNetV3-Large backbone on one frame tensor (mbv3.hip's launchers, taps of stages 1, 2, 4, 5),
+// call (nnd_midas_forward): the MobileNetV3-Large backbone on one frame tensor (mbv3.hip's walk mb_walk, declared in mbv3.h, with
+// the taps of stages 1, 2, 4, 5 kept; layer plan, packer and conv_mfma launcher from enc_plan.h),
 // BaseDecoder (nndepth/decoders/base_decoder.py) with its four UpsamplerBlocks (nndepth/blocks/upsampler_block.py) and the
 // last_conv head.  Exact fp32 throughout: no split arithmetic, no calibration; every BatchNorm is folded on the host
 // (ops.MidasEngine, float64, cast once to fp32).
@@ -19,7 +20,6 @@
 #include "mbv3.h"
 #include "bilinear.h"
 
-#include <atomic>
 #include <cstring>
 
 namespace nnd {
@@ -240,31 +240,15 @@ static int run_head(int C, const float* packed3, const float* packed1, const flo
 }
 
 // k x k conv on conv_mfma (mbv3.hip's pointwise layer): y = act(conv + bias), or with `add`: y = add + relu(conv + bias)
-static int run_conv(const MbLayer& l, const float* blob, const float* x, float* y, const float* add, int N, int H, int W, hipStream_t st) {
-    const int64_t xbs = (int64_t)l.cin * H * W, ybs = (int64_t)l.cout * H * W;
-    if (!add) return run_pw(l, blob, x, xbs, y, ybs, nullptr, N, H, W, st);
-    ConvIO io{};
-    io.src0 = Act{const_cast<float*>(x), xbs, l.cin};
-    io.out0 = Act{y, ybs, l.cout};
-    io.aux0 = Act{const_cast<float*>(add), ybs, l.cout};
-    io.Hin = H; io.Win = W;
-    io.flags = 1;  // ReLU BEFORE the addition (UpsamplerBlock: feat + relu(bn1(conv1(skip))))
-    io.force_ks = l.cl.nchunks >= 2 ? 2 : 1;
-    return launch_conv(l.cl, blob + l.off, io, EPI_AFFINE, N, H, W, st);
+static int run_conv(const EncLayer& l, const float* blob, const float* x, float* y, const float* add, int N, int H, int W, hipStream_t st) {
+    if (!add) return mb_run_pw(l, blob, x, y, nullptr, N, H, W, st);
+    // flags 1: ReLU BEFORE the addition (UpsamplerBlock: feat + relu(bn1(conv1(skip))))
+    return enc_run_mfma(l, blob, x, (int64_t)l.cin * H * W, y, (int64_t)l.cout * H * W, add, EPI_AFFINE, 1, N, H, W, H, W, st);
 }
 
 // ------------------------------------------------------------------------------------------ plan
 enum MdKind { MD_UP = 16, MD_HEAD3 = 17, MD_HEAD1 = 18 };
 constexpr int MD_TAP_C[4] = {24, 40, 112, 160};
-
-static void md_add(MbPlan& p, int kind, int cin, int cout, int k, int64_t floats) {
-    MbLayer l{};
-    l.kind = kind; l.cin = cin; l.cout = cout; l.k = k; l.stride = 1; l.act = MB_RELU;
-    l.off = p.total;
-    l.floats = floats;
-    p.total += mb_align(floats);
-    p.layers.push_back(l);
-}
 
 static int md_check(const nnd_midas_desc* d) {
     NND_REQUIRE(d, "midas: null descriptor");
@@ -277,28 +261,36 @@ static int md_check(const nnd_midas_desc* d) {
 // layer order (= the tensor order of nnd_midas_pack): the backbone (mb_plan_backbone) | skip_layers.0..3 | per UpsamplerBlock 0..3:
 // [conv1 + bn1 (blocks 0..2)] conv2 + bn2, out_conv | last_conv.0, last_conv.2, last_conv.4
 struct MdPlan {
-    MbPlan p;
+    EncPlan p;
     size_t skip0, up0, last0;  // layer indices
 };
 
 static int md_plan(const nnd_midas_desc* d, MdPlan* m) {
     if (int rc = md_check(d)) return rc;
     const int C = d->feature_channels;
-    MbPlan& p = m->p;
+    EncPlan& p = m->p;
     mb_plan_backbone(p);
     m->skip0 = p.layers.size();
-    for (int i = 0; i < 4; ++i) mb_add(p, MB_PW, MD_TAP_C[i], C, 3, 1, MB_RELU);
+    for (int i = 0; i < 4; ++i) enc_add_mfma(p, MD_TAP_C[i], C, 3, 1, MB_RELU);
     m->up0 = p.layers.size();
     for (int i = 0; i < 4; ++i) {
-        if (i < 3) mb_add(p, MB_PW, C, C, 3, 1, MB_RELU);
-        mb_add(p, MB_PW, C, C, 3, 1, MB_RELU);
-        md_add(p, MD_UP, C, C, 1, md_conv_floats(C, C, 1));
+        if (i < 3) enc_add_mfma(p, C, C, 3, 1, MB_RELU);
+        enc_add_mfma(p, C, C, 3, 1, MB_RELU);
+        enc_add_raw(p, MD_UP, C, C, 1, 1, MB_RELU, md_conv_floats(C, C, 1));
     }
     m->last0 = p.layers.size();
-    mb_add(p, MB_PW, C, C, 3, 1, MB_NONE);
-    md_add(p, MD_HEAD3, C, C, 3, md_conv_floats(C, C, 3));
-    md_add(p, MD_HEAD1, C, 1, 1, md_head1_floats(C));
+    enc_add_mfma(p, C, C, 3, 1, MB_NONE);
+    enc_add_raw(p, MD_HEAD3, C, C, 3, 1, MB_RELU, md_conv_floats(C, C, 3));
+    enc_add_raw(p, MD_HEAD1, C, 1, 1, 1, MB_RELU, md_head1_floats(C));
     return NND_OK;
+}
+
+// the layers only this model has (enc_pack's special cases): the up2x convs' fragment layout and the C -> 1 head
+static bool md_pack_special(const EncLayer& l, const float* w, const float* b, float* base) {
+    if (l.kind == MD_UP || l.kind == MD_HEAD3) md_pack_conv(l.cout, l.cin, l.k, w, b, base);
+    else if (l.kind == MD_HEAD1) md_pack_head1(l.cin, w, b, base);
+    else return false;
+    return true;
 }
 
 static int md_check_hw(const char* what, int B, int H, int W) {
@@ -324,9 +316,9 @@ static void md_regions(int C, int B, int H, int W, int64_t* off) {  // off[MDR_C
     sz[MDR_O3] = q / 16; sz[MDR_O2] = q / 4; sz[MDR_O1] = q;
     sz[MDR_DEC] = 4 * q; sz[MDR_T] = 4 * q;
     sz[MDR_PRE] = (int64_t)B * H * W;
-    sz[MDR_BACKBONE] = mb_single_ws(B, H, W);
+    sz[MDR_BACKBONE] = mb_walk_ws(B, B, H, W);
     off[0] = 0;
-    for (int i = 0; i < MDR_COUNT; ++i) off[i + 1] = off[i] + mb_align(sz[i]);
+    for (int i = 0; i < MDR_COUNT; ++i) off[i + 1] = off[i] + enc_align(sz[i]);
 }
 
 }  // namespace nnd
@@ -360,15 +352,15 @@ int nnd_midas_up2x_pw(int Cout, int Cin, const float* packed_dev, const float* x
 
 int64_t nnd_midas_head_packed_floats(int C) {
     if (int rc = md_check_c("midas_head", C)) return rc;
-    return mb_align(md_conv_floats(C, C, 3)) + md_head1_floats(C);
+    return enc_align(md_conv_floats(C, C, 3)) + md_head1_floats(C);
 }
 
 int nnd_midas_head_pack(int C, const float* w2, const float* b2, const float* w4, const float* b4, float* packed_host) {
     if (int rc = md_check_c("midas_head_pack", C)) return rc;
     NND_REQUIRE(w2 && b2 && w4 && b4 && packed_host, "midas_head_pack: null pointer");
-    memset(packed_host, 0, sizeof(float) * (mb_align(md_conv_floats(C, C, 3)) + md_head1_floats(C)));
+    memset(packed_host, 0, sizeof(float) * (enc_align(md_conv_floats(C, C, 3)) + md_head1_floats(C)));
     md_pack_conv(C, C, 3, w2, b2, packed_host);
-    md_pack_head1(C, w4, b4, packed_host + mb_align(md_conv_floats(C, C, 3)));
+    md_pack_head1(C, w4, b4, packed_host + enc_align(md_conv_floats(C, C, 3)));
     return NND_OK;
 }
 
@@ -376,16 +368,14 @@ int nnd_midas_head(int C, const float* packed_dev, const float* t, float* depth,
     if (int rc = md_check_c("midas_head", C)) return rc;
     NND_REQUIRE(packed_dev && t && depth, "midas_head: null pointer");
     if (int rc = md_check_size("midas_head", N, h, w)) return rc;
-    return run_head(C, packed_dev, packed_dev + mb_align(md_conv_floats(C, C, 3)), t, depth, pre_relu, N, h, w, (hipStream_t)stream);
+    return run_head(C, packed_dev, packed_dev + enc_align(md_conv_floats(C, C, 3)), t, depth, pre_relu, N, h, w, (hipStream_t)stream);
 }
 
 int nnd_midas_conv_add(int Cout, int Cin, int k, const float* packed_dev, const float* x, const float* feat, float* y, int N, int H, int W,
                        void* stream) {
     NND_REQUIRE(packed_dev && x && feat && y && N >= 1 && H >= 1 && W >= 1, "midas_conv_add: bad argument");
     NND_REQUIRE(Cout >= 1 && Cin >= 1 && (k == 1 || k == 3), "midas_conv_add: %dx%d %d -> %d not built", k, k, Cin, Cout);
-    MbPlan p;
-    mb_add(p, MB_PW, Cin, Cout, k, 1, MB_RELU);
-    return run_conv(p.layers[0], packed_dev, x, y, feat, N, H, W, (hipStream_t)stream);
+    return run_conv(enc_mfma_layer(Cin, Cout, k, 1, MB_RELU), packed_dev, x, y, feat, N, H, W, (hipStream_t)stream);
 }
 
 // ---- the model
@@ -421,27 +411,7 @@ int64_t nnd_midas_workspace_offset(const nnd_midas_desc* desc, int which, int B,
 int nnd_midas_pack(const nnd_midas_desc* desc, const float* const* t, float* packed_host) {
     MdPlan m;
     if (int rc = md_plan(desc, &m)) return rc;
-    NND_REQUIRE(t && packed_host, "midas_pack: null pointer");
-    const MbPlan& p = m.p;
-    memset(packed_host, 0, sizeof(float) * p.total);
-    for (size_t i = 0; i < p.layers.size(); ++i) {
-        const MbLayer& l = p.layers[i];
-        const float *w = t[2 * i], *b = t[2 * i + 1];
-        NND_REQUIRE(w && b, "midas_pack: layer %zu: weight / bias missing", i);
-        float* base = packed_host + l.off;
-        if (l.kind == MB_PW) {
-            pack_pw(l, w, b, base);
-        } else if (l.kind == MD_UP || l.kind == MD_HEAD3) {
-            md_pack_conv(l.cout, l.cin, l.k, w, b, base);
-        } else if (l.kind == MD_HEAD1) {
-            md_pack_head1(l.cin, w, b, base);
-        } else {
-            const int64_t nw = l.floats - l.cout;
-            memcpy(base, w, sizeof(float) * nw);
-            memcpy(base + nw, b, sizeof(float) * l.cout);
-        }
-    }
-    return NND_OK;
+    return enc_pack(m.p, 2, t, packed_host, "midas_pack", md_pack_special);
 }
 
 int nnd_midas_forward(const nnd_midas_desc* desc, const float* packed, const float* x, float* depth, float* workspace, int B, int H, int W,
@@ -452,13 +422,14 @@ int nnd_midas_forward(const nnd_midas_desc* desc, const float* packed, const flo
     if (int rc = md_check_hw("midas_forward", B, H, W)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int C = desc->feature_channels;
-    const MbPlan& p = m.p;
+    const EncPlan& p = m.p;
     int64_t off[MDR_COUNT + 1];
     md_regions(C, B, H, W, off);
     auto R = [&](int i) { return workspace + off[i]; };
     int rc;
     float* taps[4] = {R(MDR_TAP0), R(MDR_TAP0 + 1), R(MDR_TAP0 + 2), R(MDR_TAP0 + 3)};
-    if ((rc = mb_single_forward(p, packed, x, taps, R(MDR_BACKBONE), B, H, W, st))) return rc;
+    float* const keep[MB_NSTAGES] = {nullptr, taps[0], taps[1], nullptr, taps[2], taps[3]};  // one frame tensor, B samples throughout
+    if ((rc = mb_walk(p, packed, x, x, B, B, B, keep, R(MDR_BACKBONE), H, W, st))) return rc;
     for (int i = 0; i < 4; ++i)
         if ((rc = run_conv(p.layers[m.skip0 + i], packed, taps[i], R(MDR_SKIP0 + i), nullptr, B, H >> (i + 2), W >> (i + 2), st))) return rc;
     // UpsamplerBlocks 3 (no skip input: its conv1 / bn1 are never run), 2, 1, 0

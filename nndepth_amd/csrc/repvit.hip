@@ -21,10 +21,13 @@
 //   cnet_proj[j] 1x1 + GELU on the left frames' map                                conv_mfma, EPI_GELU
 // The layer scales ride in EPI_AFFINE's per-channel scale (y = residual + acc * ls + ls * bias): the epilogue already carries a
 // per-channel scale, so the weights stay as trained and no new epilogue mode is needed.
-// Every conv_mfma launch fixes its split-K factor per layer (ConvIO::force_ks: 2 from two 32-channel K chunks on, else 1): each output
+// Every conv_mfma launch fixes its split-K factor per layer (enc_plan.h: enc_run_mfma; 2 from two 32-channel K chunks on, else 1): each output
 // has the same K order whatever the batch, so a pair's maps do not depend on the batch it runs in, and the two half-K chains keep the
 // fp32 accumulation error at PyTorch's level.  The depthwise kernels accumulate in float64 and round once.  Activations are NCHW in the caller's workspace.
-#include "common.h"
+// The layer plan, the packer and the conv_mfma launcher are enc_plan.h's, shared with mbv3.hip and midas.hip; the depthwise tap loop
+// and the stem's patch gather are enc_valu.h's, shared with mbv3.hip.
+#include "enc_plan.h"
+#include "enc_valu.h"
 #include "bilinear.h"
 
 #include <algorithm>
@@ -53,18 +56,7 @@ __global__ void __launch_bounds__(256) dwconv_kernel(const float* __restrict__ x
     const int iy0 = oy * stride - K / 2, ix0 = ox * stride - K / 2;
     // float64 accumulation, rounded once: a 49-tap fp32 chain was 3-4.5x PyTorch's own fp32 error at k = 7 (per-kernel test); the
     // kernel is bound by latency / HBM, not by its 2 x 49 flops per output
-    double acc = 0.0;
-#pragma unroll
-    for (int dy = 0; dy < K; ++dy) {
-        const int iy = iy0 + dy;
-        if (iy < 0 || iy >= Hin) continue;
-#pragma unroll
-        for (int dx = 0; dx < K; ++dx) {
-            const int ix = ix0 + dx;
-            if (ix < 0 || ix >= Win) continue;
-            acc = fma((double)wp[dy * K + dx], (double)xp[(long)iy * Win + ix], acc);
-        }
-    }
+    const double acc = dw_taps<K>(xp, wp, iy0, ix0, Hin, Win);
     float v = (float)(acc + (double)bias[c]);
     if (gelu) v = gelu_exact(v);
     y[((long)n * C + c) * Ho * Wo + idx] = v;
@@ -86,16 +78,7 @@ __global__ void __launch_bounds__(256) stem_conv_kernel(const float* __restrict_
     const int oy = idx / Wo, ox = idx - oy * Wo;
     const float* xp = n < nsplit ? x + (long)n * 3 * Hin * Win : x1 + (long)(n - nsplit) * 3 * Hin * Win;
     float in[27];
-#pragma unroll
-    for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int iy = oy * stride - 1 + dy, ix = ox * stride - 1 + dx;
-                const bool ok = iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
-                in[(ci * 3 + dy) * 3 + dx] = ok ? xp[((long)ci * Hin + iy) * Win + ix] : 0.f;
-            }
+    stem_gather(xp, oy, ox, stride, 1, 1, Hin, Win, in);
     float* yp = y + (long)n * STEM_C * Ho * Wo + idx;
 #pragma unroll 4
     for (int co = 0; co < STEM_C; ++co) {
@@ -174,44 +157,10 @@ __global__ void __launch_bounds__(256) upsample_add_relu_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------ plan
-enum RvKind { RV_STEM = 0, RV_DW = 1, RV_PW = 2 };
 enum RvAct { RV_NONE = 0, RV_GELU = 1, RV_RESID = 2 };  // RV_RESID: y = x_in + scale * (acc + bias) (EPI_AFFINE, residual)
 
-struct RvLayer {
-    int kind, cin, cout, k, stride, act;
-    ConvLayer cl;         // RV_PW: conv_mfma layout
-    int64_t off, floats;  // blob offset / size (RV_STEM, RV_DW: weights then bias)
-};
-
-struct RvPlan {
-    std::vector<RvLayer> layers;
-    int64_t total = 0;
-};
-
-static int rv_add(RvPlan& p, int kind, int cin, int cout, int k, int stride, int act) {
-    RvLayer l{};
-    l.kind = kind; l.cin = cin; l.cout = cout; l.k = k; l.stride = stride; l.act = act;
-    l.off = p.total;
-    if (kind == RV_PW) {
-        NND_REQUIRE(stride == 1 || stride == 2, "repvit: stride %d", stride);
-        ConvLayer L;
-        L.KH = 1; L.KW = 1; L.Cin = cin; L.Cout = cout; L.stride = stride; L.arith = 0;
-        // 32-channel K chunks at stride 1 (conv_ci_t would take 128 from Cin = 128 on), so that split-K 2 (run_pw) applies from Cin = 64
-        L.CI_T = stride == 1 ? 32 : conv_ci_t(1, 1, cin, stride, cout);
-        L.nchunks = cdiv(cin, L.CI_T);
-        L.ncb = cdiv(cout, 32);
-        int64_t off = 0;
-        L.w_off = off; off += L.w_floats();
-        L.b_off = off; off += L.b_floats();
-        L.s_off = off; off += L.b_floats();
-        l.cl = L;
-        l.floats = off;
-    } else {
-        l.floats = (int64_t)cout * (kind == RV_STEM ? cin : 1) * k * k + cout;
-    }
-    p.total += (l.floats + 63) / 64 * 64;
-    p.layers.push_back(l);
-    return NND_OK;
+static void rv_add_raw(EncPlan& p, int kind, int cin, int cout, int k, int stride, int act) {
+    enc_add_raw(p, kind, cin, cout, k, stride, act, (int64_t)cout * (kind == ENC_STEM ? cin : 1) * k * k + cout);
 }
 
 static int rv_check(const nnd_repvit_desc* d) {
@@ -236,40 +185,38 @@ static int rv_check(const nnd_repvit_desc* d) {
     return NND_OK;
 }
 
-static int rv_plan(const nnd_repvit_desc* d, RvPlan* p) {
+static int rv_plan(const nnd_repvit_desc* d, EncPlan* p) {
     if (int rc = rv_check(d)) return rc;
-    p->layers.clear();
-    p->total = 0;
-    rv_add(*p, RV_STEM, 3, STEM_C, 3, d->stem_strides[0], RV_GELU);
-    rv_add(*p, RV_DW, STEM_C, STEM_C, 3, d->stem_strides[1], RV_GELU);
-    if (int rc = rv_add(*p, RV_PW, STEM_C, STEM_C, 1, d->stem_strides[2], RV_GELU)) return rc;
+    rv_add_raw(*p, ENC_STEM, 3, STEM_C, 3, d->stem_strides[0], RV_GELU);
+    rv_add_raw(*p, ENC_DW, STEM_C, STEM_C, 3, d->stem_strides[1], RV_GELU);
+    enc_add_mfma(*p, STEM_C, STEM_C, 1, d->stem_strides[2], RV_GELU);
     int cin = STEM_C;
     for (int i = 0; i < 4; ++i) {
         const int c = d->channels[i];
-        rv_add(*p, RV_DW, cin, cin, d->patch_size, d->down_strides[i], RV_NONE);
-        rv_add(*p, RV_PW, cin, c, 1, 1, RV_GELU);
+        rv_add_raw(*p, ENC_DW, cin, cin, d->patch_size, d->down_strides[i], RV_NONE);
+        enc_add_mfma(*p, cin, c, 1, 1, RV_GELU);
         for (int b = 0; b < d->num_blocks[i]; ++b) {
             if (d->mixer[i] == 0) {
-                rv_add(*p, RV_DW, c, c, 3, 1, RV_NONE);
+                rv_add_raw(*p, ENC_DW, c, c, 3, 1, RV_NONE);
             } else {
-                rv_add(*p, RV_PW, c, 1 + 2 * c, 1, 1, RV_NONE);  // qkv_proj (norm folded)
-                rv_add(*p, RV_PW, c, c, 1, 1, RV_RESID);         // out_proj, x + ls1 * (.)
+                enc_add_mfma(*p, c, 1 + 2 * c, 1, 1, RV_NONE);  // qkv_proj (norm folded)
+                enc_add_mfma(*p, c, c, 1, 1, RV_RESID);         // out_proj, x + ls1 * (.)
             }
             if (d->ffn_hidden[i] > 0) {
-                rv_add(*p, RV_PW, c, d->ffn_hidden[i], 1, 1, RV_GELU);  // fc1
-                rv_add(*p, RV_PW, d->ffn_hidden[i], c, 1, 1, RV_RESID);  // fc2, x + ls * (.)
+                enc_add_mfma(*p, c, d->ffn_hidden[i], 1, 1, RV_GELU);   // fc1
+                enc_add_mfma(*p, d->ffn_hidden[i], c, 1, 1, RV_RESID);  // fc2, x + ls * (.)
             }
         }
         cin = c;
     }
     const int f0 = d->fusion_dim[0], f1 = d->fusion_dim[1];
-    rv_add(*p, RV_PW, d->channels[3], d->cnet_dim, 1, 1, RV_GELU);  // cnet_proj[0..2]
-    rv_add(*p, RV_PW, f0, d->cnet_dim, 1, 1, RV_GELU);
-    rv_add(*p, RV_PW, f0, d->cnet_dim, 1, 1, RV_GELU);
-    rv_add(*p, RV_PW, d->channels[3], f0, 1, 1, RV_NONE);  // fusion 0: coarse (stage 3) / fine (stage 1) halves
-    rv_add(*p, RV_PW, d->channels[1], f0, 1, 1, RV_NONE);
-    rv_add(*p, RV_PW, f0, f1, 1, 1, RV_NONE);              // fusion 1: coarse (fused 1) / fine (stem)
-    rv_add(*p, RV_PW, STEM_C, f1, 1, 1, RV_NONE);
+    enc_add_mfma(*p, d->channels[3], d->cnet_dim, 1, 1, RV_GELU);  // cnet_proj[0..2]
+    enc_add_mfma(*p, f0, d->cnet_dim, 1, 1, RV_GELU);
+    enc_add_mfma(*p, f0, d->cnet_dim, 1, 1, RV_GELU);
+    enc_add_mfma(*p, d->channels[3], f0, 1, 1, RV_NONE);  // fusion 0: coarse (stage 3) / fine (stage 1) halves
+    enc_add_mfma(*p, d->channels[1], f0, 1, 1, RV_NONE);
+    enc_add_mfma(*p, f0, f1, 1, 1, RV_NONE);              // fusion 1: coarse (fused 1) / fine (stem)
+    enc_add_mfma(*p, STEM_C, f1, 1, 1, RV_NONE);
     return NND_OK;
 }
 
@@ -320,35 +267,45 @@ static RvWs rv_ws(const nnd_repvit_desc* d, int N, int H, int W) {
     return r;
 }
 
-static int64_t rv_align(int64_t n) { return (n + 63) / 64 * 64; }
-
-static int run_dw(const RvLayer& l, const float* blob, const float* x, float* y, int N, int Hin, int Win, hipStream_t st) {
-    const int Ho = conv_out(Hin, l.stride), Wo = conv_out(Win, l.stride);
-    const float* w = blob + l.off;
-    const float* b = w + (int64_t)l.cout * l.k * l.k;
-    dim3 grid((unsigned)cdiv(Ho * Wo, 256), (unsigned)l.cout, (unsigned)N);
-    const int g = l.act == RV_GELU;
-    if (l.k == 3) hipLaunchKernelGGL(dwconv_kernel<3>, grid, dim3(256), 0, st, x, y, w, b, l.cout, Hin, Win, Ho, Wo, l.stride, g);
-    else if (l.k == 5) hipLaunchKernelGGL(dwconv_kernel<5>, grid, dim3(256), 0, st, x, y, w, b, l.cout, Hin, Win, Ho, Wo, l.stride, g);
-    else hipLaunchKernelGGL(dwconv_kernel<7>, grid, dim3(256), 0, st, x, y, w, b, l.cout, Hin, Win, Ho, Wo, l.stride, g);
+// ------------------------------------------------------------------------------------------ launchers
+static int run_dw(const float* x, const float* w, const float* bias, float* y, int N, int C, int Hin, int Win, int k, int stride, int gelu,
+                  hipStream_t st) {
+    const int Ho = conv_out(Hin, stride), Wo = conv_out(Win, stride);
+    dim3 grid((unsigned)cdiv(Ho * Wo, 256), (unsigned)C, (unsigned)N);
+    if (k == 3) hipLaunchKernelGGL(dwconv_kernel<3>, grid, dim3(256), 0, st, x, y, w, bias, C, Hin, Win, Ho, Wo, stride, gelu);
+    else if (k == 5) hipLaunchKernelGGL(dwconv_kernel<5>, grid, dim3(256), 0, st, x, y, w, bias, C, Hin, Win, Ho, Wo, stride, gelu);
+    else hipLaunchKernelGGL(dwconv_kernel<7>, grid, dim3(256), 0, st, x, y, w, bias, C, Hin, Win, Ho, Wo, stride, gelu);
     NND_LAUNCH_CHECK();
     return NND_OK;
 }
 
-// 1x1 conv on conv_mfma (NCHW in / out); res: the residual of RV_RESID (same shape as y)
-static int run_pw(const RvLayer& l, const float* blob, const float* x, int64_t xbs, float* y, int64_t ybs, const float* res, int N, int Hin,
-                  int Win, hipStream_t st) {
+static int run_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W,
+                    int stride, hipStream_t st) {
+    const int Ho = conv_out(H, stride), Wo = conv_out(W, stride);
+    hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)cdiv(Ho * Wo, 256), 1, (unsigned)N), dim3(256), 0, st, x, x1, nsplit, y, w, bias, H,
+                       W, Ho, Wo, stride);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+static int run_linattn(const float* qkv, float* out, int N, int C, int H, int W, hipStream_t st) {
+    hipLaunchKernelGGL(linattn_kernel, dim3((unsigned)H, (unsigned)N), dim3(256), 0, st, qkv, out, C, H, W);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+static int run_upsample_add_relu(const float* a, float* y, int N, int C, int h, int w, int H, int W, hipStream_t st) {
+    dim3 grid((unsigned)cdiv(H * W, 256), (unsigned)C, (unsigned)N);
+    hipLaunchKernelGGL(upsample_add_relu_kernel, grid, dim3(256), 0, st, a, y, C, h, w, H, W);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+// 1x1 conv on conv_mfma (NCHW in / out, dense); res: the residual of RV_RESID (same shape as y)
+static int run_pw(const EncLayer& l, const float* blob, const float* x, float* y, const float* res, int N, int Hin, int Win, hipStream_t st) {
     const int Ho = conv_out(Hin, l.stride), Wo = conv_out(Win, l.stride);
-    ConvIO io{};
-    io.src0 = Act{const_cast<float*>(x), xbs, l.cin};
-    io.out0 = Act{y, ybs, l.cout};
-    if (res) io.aux0 = Act{const_cast<float*>(res), ybs, l.cout};
-    io.Hin = Hin; io.Win = Win;
-    // split-K fixed per layer (2 where the layer has 2+ chunks): the two half-K partial tiles are summed in wave order, which halves
-    // the MFMA accumulation chain (a 128- / 384-deep chain was up to 2.7x PyTorch's own fp32 error), and a fixed ks keeps every
-    // output's K order independent of the batch
-    io.force_ks = l.cl.nchunks >= 2 ? 2 : 1;
-    return launch_conv(l.cl, blob + l.off, io, l.act == RV_GELU ? EPI_GELU : EPI_AFFINE, N, Ho, Wo, st);
+    return enc_run_mfma(l, blob, x, (int64_t)l.cin * Hin * Win, y, (int64_t)l.cout * Ho * Wo, res, l.act == RV_GELU ? EPI_GELU : EPI_AFFINE, 0,
+                        N, Hin, Win, Ho, Wo, st);
 }
 
 }  // namespace nnd
@@ -364,14 +321,7 @@ int nnd_repvit_depthwise(const float* x, const float* w, const float* bias, floa
     NND_REQUIRE(k == 3 || k == 5 || k == 7, "repvit_depthwise: kernel %d not built (3, 5, 7)", k);
     NND_REQUIRE(stride == 1 || stride == 2, "repvit_depthwise: stride %d not built (1, 2)", stride);
     NND_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1 && C <= 65535 && N <= 65535, "repvit_depthwise: bad size %dx%dx%dx%d", N, C, H, W);
-    const int Ho = conv_out(H, stride), Wo = conv_out(W, stride);
-    dim3 grid((unsigned)cdiv(Ho * Wo, 256), (unsigned)C, (unsigned)N);
-    hipStream_t st = (hipStream_t)stream;
-    if (k == 3) hipLaunchKernelGGL(dwconv_kernel<3>, grid, dim3(256), 0, st, x, y, w, bias, C, H, W, Ho, Wo, stride, gelu ? 1 : 0);
-    else if (k == 5) hipLaunchKernelGGL(dwconv_kernel<5>, grid, dim3(256), 0, st, x, y, w, bias, C, H, W, Ho, Wo, stride, gelu ? 1 : 0);
-    else hipLaunchKernelGGL(dwconv_kernel<7>, grid, dim3(256), 0, st, x, y, w, bias, C, H, W, Ho, Wo, stride, gelu ? 1 : 0);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_dw(x, w, bias, y, N, C, H, W, k, stride, gelu ? 1 : 0, (hipStream_t)stream);
 }
 
 int nnd_repvit_stem(const float* x, const float* x1, int nsplit, const float* w, const float* bias, float* y, int N, int H, int W, int stride,
@@ -381,69 +331,53 @@ int nnd_repvit_stem(const float* x, const float* x1, int nsplit, const float* w,
     NND_REQUIRE(N >= 1 && H >= 1 && W >= 1 && N <= 65535, "repvit_stem: bad size %dx%dx%d", N, H, W);
     if (!x1) nsplit = N;
     NND_REQUIRE(nsplit >= 1 && nsplit <= N, "repvit_stem: nsplit %d of %d", nsplit, N);
-    const int Ho = conv_out(H, stride), Wo = conv_out(W, stride);
-    hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)cdiv(Ho * Wo, 256), 1, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x,
-                       x1 ? x1 : x, nsplit, y, w, bias, H, W, Ho, Wo, stride);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_stem(x, x1 ? x1 : x, nsplit, w, bias, y, N, H, W, stride, (hipStream_t)stream);
 }
 
 int64_t nnd_repvit_pointwise_packed_floats(int Cout, int Cin, int stride) {
-    RvPlan p;
     NND_REQUIRE(Cout >= 1 && Cin >= 1, "repvit_pointwise: channels %d -> %d", Cin, Cout);
-    if (int rc = rv_add(p, RV_PW, Cin, Cout, 1, stride, RV_NONE)) return rc;
-    return p.total;
+    NND_REQUIRE(stride == 1 || stride == 2, "repvit: stride %d", stride);
+    return enc_align(enc_mfma_layer(Cin, Cout, 1, stride, RV_NONE).floats);
 }
 
 int nnd_repvit_pointwise_pack(int Cout, int Cin, int stride, const float* w, const float* bias, const float* scale, float* packed_host) {
-    RvPlan p;
     NND_REQUIRE(Cout >= 1 && Cin >= 1 && w && bias && packed_host, "repvit_pointwise_pack: bad argument");
-    if (int rc = rv_add(p, RV_PW, Cin, Cout, 1, stride, RV_NONE)) return rc;
-    const RvLayer& l = p.layers[0];
-    memset(packed_host, 0, sizeof(float) * p.total);
-    const float* ws[1] = {w};
-    const float* bs[1] = {bias};
-    int co[1] = {Cout};
-    pack_conv(l.cl, 1, ws, bs, co, packed_host);
-    for (int c = 0; c < l.cl.ncb * 32; ++c) packed_host[l.cl.s_off + c] = c < Cout ? (scale ? scale[c] : 1.f) : 0.f;
+    NND_REQUIRE(stride == 1 || stride == 2, "repvit: stride %d", stride);
+    const EncLayer l = enc_mfma_layer(Cin, Cout, 1, stride, RV_NONE);
+    memset(packed_host, 0, sizeof(float) * enc_align(l.floats));
+    enc_pack_mfma(l, w, bias, scale, packed_host);
     return NND_OK;
 }
 
 int nnd_repvit_pointwise(int Cout, int Cin, int stride, const float* packed_dev, const float* x, const float* residual, float* y, int N,
                          int H, int W, int gelu, void* stream) {
-    RvPlan p;
     NND_REQUIRE(packed_dev && x && y && N >= 1 && H >= 1 && W >= 1, "repvit_pointwise: bad argument");
     NND_REQUIRE(!(gelu && residual), "repvit_pointwise: GELU and a residual are not built together");
-    if (int rc = rv_add(p, RV_PW, Cin, Cout, 1, stride, gelu ? RV_GELU : (residual ? RV_RESID : RV_NONE))) return rc;
-    const int Ho = conv_out(H, stride), Wo = conv_out(W, stride);
-    return run_pw(p.layers[0], packed_dev, x, (int64_t)Cin * H * W, y, (int64_t)Cout * Ho * Wo, residual, N, H, W, (hipStream_t)stream);
+    NND_REQUIRE(stride == 1 || stride == 2, "repvit: stride %d", stride);
+    const EncLayer l = enc_mfma_layer(Cin, Cout, 1, stride, gelu ? RV_GELU : (residual ? RV_RESID : RV_NONE));
+    return run_pw(l, packed_dev, x, y, residual, N, H, W, (hipStream_t)stream);
 }
 
 int nnd_repvit_linear_attention(const float* qkv, float* out, int N, int C, int H, int W, void* stream) {
     NND_REQUIRE(qkv && out && N >= 1 && C >= 1 && H >= 1 && W >= 1 && N <= 65535, "repvit_linear_attention: bad argument");
     NND_REQUIRE(W <= LINATTN_MAXW, "repvit_linear_attention: row of %d > %d columns", W, LINATTN_MAXW);
-    hipLaunchKernelGGL(linattn_kernel, dim3((unsigned)H, (unsigned)N), dim3(256), 0, (hipStream_t)stream, qkv, out, C, H, W);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_linattn(qkv, out, N, C, H, W, (hipStream_t)stream);
 }
 
 int nnd_repvit_upsample_add_relu(const float* a, float* y, int N, int C, int h, int w, int H, int W, void* stream) {
     NND_REQUIRE(a && y && N >= 1 && C >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1 && C <= 65535 && N <= 65535,
                 "repvit_upsample_add_relu: bad argument");
-    dim3 grid((unsigned)cdiv(H * W, 256), (unsigned)C, (unsigned)N);
-    hipLaunchKernelGGL(upsample_add_relu_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, y, C, h, w, H, W);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    return run_upsample_add_relu(a, y, N, C, h, w, H, W, (hipStream_t)stream);
 }
 
 int nnd_repvit_num_tensors(const nnd_repvit_desc* desc) {
-    RvPlan p;
+    EncPlan p;
     if (int rc = rv_plan(desc, &p)) return rc;
     return 3 * (int)p.layers.size();
 }
 
 int64_t nnd_repvit_packed_floats(const nnd_repvit_desc* desc) {
-    RvPlan p;
+    EncPlan p;
     if (int rc = rv_plan(desc, &p)) return rc;
     return p.total;
 }
@@ -452,39 +386,19 @@ int64_t nnd_repvit_workspace_floats(const nnd_repvit_desc* desc, int N, int H, i
     if (int rc = rv_check(desc)) return rc;
     NND_REQUIRE(N >= 1 && H >= 1 && W >= 1, "repvit: bad size %dx%dx%d", N, H, W);
     const RvWs r = rv_ws(desc, N, H, W);
-    return 4 * rv_align(r.m) + rv_align(r.stem) + rv_align(r.s1) + rv_align(r.a0) + rv_align(r.a1);
+    return 4 * enc_align(r.m) + enc_align(r.stem) + enc_align(r.s1) + enc_align(r.a0) + enc_align(r.a1);
 }
 
 int nnd_repvit_pack(const nnd_repvit_desc* desc, const float* const* t, float* packed_host) {
-    RvPlan p;
+    EncPlan p;
     if (int rc = rv_plan(desc, &p)) return rc;
-    NND_REQUIRE(t && packed_host, "repvit_pack: null pointer");
-    memset(packed_host, 0, sizeof(float) * p.total);
-    for (size_t i = 0; i < p.layers.size(); ++i) {
-        const RvLayer& l = p.layers[i];
-        const float *w = t[3 * i], *b = t[3 * i + 1], *s = t[3 * i + 2];
-        NND_REQUIRE(w && b, "repvit_pack: layer %zu: weight / bias missing", i);
-        float* base = packed_host + l.off;
-        if (l.kind == RV_PW) {
-            const float* ws[1] = {w};
-            const float* bs[1] = {b};
-            int co[1] = {l.cout};
-            pack_conv(l.cl, 1, ws, bs, co, base);
-            for (int c = 0; c < l.cl.ncb * 32; ++c) base[l.cl.s_off + c] = c < l.cout ? (s ? s[c] : 1.f) : 0.f;
-        } else {
-            NND_REQUIRE(!s, "repvit_pack: layer %zu (depthwise / stem) takes no scale", i);
-            const int64_t nw = (int64_t)l.cout * (l.kind == RV_STEM ? l.cin : 1) * l.k * l.k;
-            memcpy(base, w, sizeof(float) * nw);
-            memcpy(base + nw, b, sizeof(float) * l.cout);
-        }
-    }
-    return NND_OK;
+    return enc_pack(p, 3, t, packed_host, "repvit_pack");
 }
 
 int nnd_repvit_forward(const nnd_repvit_desc* desc, const float* packed, const float* frames, const float* frames_b, int nsplit,
                        float* feat0, float* feat1, float* feat2, float* cnet0, float* cnet1, float* cnet2, float* workspace, int N, int H,
                        int W, void* stream) {
-    RvPlan p;
+    EncPlan p;
     if (int rc = rv_plan(desc, &p)) return rc;
     NND_REQUIRE(packed && frames && feat0 && feat1 && feat2 && cnet0 && cnet1 && cnet2 && workspace, "repvit_forward: null pointer");
     NND_REQUIRE(N >= 1 && H >= 1 && W >= 1, "repvit_forward: bad size %dx%dx%d", N, H, W);
@@ -496,87 +410,79 @@ int nnd_repvit_forward(const nnd_repvit_desc* desc, const float* packed, const f
     const RvWs r = rv_ws(desc, N, H, W);
     float* buf[4];
     float* q = workspace;
-    for (int i = 0; i < 4; ++i, q += rv_align(r.m)) buf[i] = q;
-    float* stem = q; q += rv_align(r.stem);
-    float* s1 = q; q += rv_align(r.s1);
-    float* a0 = q; q += rv_align(r.a0);
+    for (int i = 0; i < 4; ++i, q += enc_align(r.m)) buf[i] = q;
+    float* stem = q; q += enc_align(r.stem);
+    float* s1 = q; q += enc_align(r.s1);
+    float* a0 = q; q += enc_align(r.a0);
     float* a1 = q;
     size_t li = 0;
-    auto L = [&]() -> const RvLayer& { return p.layers[li++]; };
-    auto bs = [](int c, int h, int w) { return (int64_t)c * h * w; };
+    auto L = [&]() -> const EncLayer& { return p.layers[li++]; };
+    auto dw = [&](const EncLayer& l, const float* x, float* y, int h, int w) {  // the next depthwise layer on all N samples
+        const float* wt = packed + l.off;
+        return run_dw(x, wt, wt + l.floats - l.cout, y, N, l.cout, h, w, l.k, l.stride, l.act == RV_GELU, st);
+    };
+    auto pw = [&](const EncLayer& l, const float* x, float* y, const float* res, int n, int h, int w) {
+        return run_pw(l, packed, x, y, res, n, h, w, st);
+    };
     int rc;
     {   // stem
-        const RvLayer& l0 = L();
-        dim3 grid((unsigned)cdiv(s.h_stem0 * s.w_stem0, 256), 1, (unsigned)N);
-        hipLaunchKernelGGL(stem_conv_kernel, grid, dim3(256), 0, st, frames, frames_b ? frames_b : frames, nsplit, buf[0], packed + l0.off,
-                           packed + l0.off + STEM_C * 27, H, W, s.h_stem0, s.w_stem0, l0.stride);
-        NND_LAUNCH_CHECK();
-        if ((rc = run_dw(L(), packed, buf[0], buf[1], N, s.h_stem0, s.w_stem0, st))) return rc;
-        if ((rc = run_pw(L(), packed, buf[1], bs(STEM_C, s.h_stem1, s.w_stem1), stem, bs(STEM_C, s.h[1], s.w[1]), nullptr, N, s.h_stem1,
-                         s.w_stem1, st))) return rc;
+        const EncLayer& l0 = L();
+        const float* wt = packed + l0.off;
+        if ((rc = run_stem(frames, frames_b ? frames_b : frames, nsplit, wt, wt + l0.floats - l0.cout, buf[0], N, H, W, l0.stride, st)))
+            return rc;
+        if ((rc = dw(L(), buf[0], buf[1], s.h_stem0, s.w_stem0))) return rc;
+        if ((rc = pw(L(), buf[1], stem, nullptr, N, s.h_stem1, s.w_stem1))) return rc;
     }
     const float* x = stem;
-    int cin = STEM_C;
     int cur = 0;  // buf[cur]: the running activation once a stage has started; buf[2], buf[3]: hidden / qkv / attention
     for (int i = 0; i < 4; ++i) {
         const int c = desc->channels[i], hi = s.h[i + 1], wi = s.w[i + 1], ho = s.h[i + 2], wo = s.w[i + 2];
-        const int64_t P = bs(1, ho, wo);
-        if ((rc = run_dw(L(), packed, x, buf[2], N, hi, wi, st))) return rc;
-        if ((rc = run_pw(L(), packed, buf[2], cin * bs(1, ho, wo), buf[cur], c * P, nullptr, N, ho, wo, st))) return rc;
+        if ((rc = dw(L(), x, buf[2], hi, wi))) return rc;
+        if ((rc = pw(L(), buf[2], buf[cur], nullptr, N, ho, wo))) return rc;
         for (int b = 0; b < desc->num_blocks[i]; ++b) {
             if (desc->mixer[i] == 0) {
-                if ((rc = run_dw(L(), packed, buf[cur], buf[cur ^ 1], N, ho, wo, st))) return rc;
+                if ((rc = dw(L(), buf[cur], buf[cur ^ 1], ho, wo))) return rc;
                 cur ^= 1;
             } else {
-                if ((rc = run_pw(L(), packed, buf[cur], c * P, buf[2], (1 + 2 * c) * P, nullptr, N, ho, wo, st))) return rc;
+                if ((rc = pw(L(), buf[cur], buf[2], nullptr, N, ho, wo))) return rc;
                 NND_REQUIRE(wo <= LINATTN_MAXW, "repvit: attention row of %d > %d columns", wo, LINATTN_MAXW);
-                hipLaunchKernelGGL(linattn_kernel, dim3((unsigned)ho, (unsigned)N), dim3(256), 0, st, buf[2], buf[3], c, ho, wo);
-                NND_LAUNCH_CHECK();
-                if ((rc = run_pw(L(), packed, buf[3], c * P, buf[cur ^ 1], c * P, buf[cur], N, ho, wo, st))) return rc;
+                if ((rc = run_linattn(buf[2], buf[3], N, c, ho, wo, st))) return rc;
+                if ((rc = pw(L(), buf[3], buf[cur ^ 1], buf[cur], N, ho, wo))) return rc;
                 cur ^= 1;
             }
             if (desc->ffn_hidden[i] > 0) {
-                const int hid = desc->ffn_hidden[i];
-                if ((rc = run_pw(L(), packed, buf[cur], c * P, buf[2], hid * P, nullptr, N, ho, wo, st))) return rc;
-                if ((rc = run_pw(L(), packed, buf[2], hid * P, buf[cur ^ 1], c * P, buf[cur], N, ho, wo, st))) return rc;
+                if ((rc = pw(L(), buf[cur], buf[2], nullptr, N, ho, wo))) return rc;
+                if ((rc = pw(L(), buf[2], buf[cur ^ 1], buf[cur], N, ho, wo))) return rc;
                 cur ^= 1;
             }
         }
         float* keep = i == 1 ? s1 : i == 3 ? feat0 : nullptr;  // stage 1 feeds fusion 0, stage 3 is feats[0]
-        if (keep) NND_HIP_CHECK(hipMemcpyAsync(keep, buf[cur], sizeof(float) * N * c * P, hipMemcpyDeviceToDevice, st));
+        if (keep) NND_HIP_CHECK(hipMemcpyAsync(keep, buf[cur], sizeof(float) * N * c * ho * wo, hipMemcpyDeviceToDevice, st));
         x = buf[cur];
         cur ^= 1;  // the next stage's patch embed writes its 1x1 result into the other buffer (x stays readable)
-        cin = c;
     }
-    const RvLayer& cp0 = L();
-    const RvLayer& cp1 = L();
-    const RvLayer& cp2 = L();
-    const RvLayer& fa0 = L();
-    const RvLayer& fb0 = L();
-    const RvLayer& fa1 = L();
-    const RvLayer& fb1 = L();
-    const int c1 = desc->channels[1], c3 = desc->channels[3], f0 = desc->fusion_dim[0], f1 = desc->fusion_dim[1];
+    const EncLayer& cp0 = L();
+    const EncLayer& cp1 = L();
+    const EncLayer& cp2 = L();
+    const EncLayer& fa0 = L();
+    const EncLayer& fb0 = L();
+    const EncLayer& fa1 = L();
+    const EncLayer& fb1 = L();
     {   // fusion 0: relu(up(A s3 + a) + B s1 + b) at stage 1's resolution
         const int h = s.h[5], w = s.w[5], Hh = s.h[3], Ww = s.w[3];
-        if ((rc = run_pw(fa0, packed, feat0, bs(c3, h, w), a0, bs(f0, h, w), nullptr, N, h, w, st))) return rc;
-        if ((rc = run_pw(fb0, packed, s1, bs(c1, Hh, Ww), feat1, bs(f0, Hh, Ww), nullptr, N, Hh, Ww, st))) return rc;
-        dim3 grid((unsigned)cdiv(Hh * Ww, 256), (unsigned)f0, (unsigned)N);
-        hipLaunchKernelGGL(upsample_add_relu_kernel, grid, dim3(256), 0, st, a0, feat1, f0, h, w, Hh, Ww);
-        NND_LAUNCH_CHECK();
+        if ((rc = pw(fa0, feat0, a0, nullptr, N, h, w))) return rc;
+        if ((rc = pw(fb0, s1, feat1, nullptr, N, Hh, Ww))) return rc;
+        if ((rc = run_upsample_add_relu(a0, feat1, N, desc->fusion_dim[0], h, w, Hh, Ww, st))) return rc;
     }
     {   // fusion 1 at the stem's resolution
         const int h = s.h[3], w = s.w[3], Hh = s.h[1], Ww = s.w[1];
-        if ((rc = run_pw(fa1, packed, feat1, bs(f0, h, w), a1, bs(f1, h, w), nullptr, N, h, w, st))) return rc;
-        if ((rc = run_pw(fb1, packed, stem, bs(STEM_C, Hh, Ww), feat2, bs(f1, Hh, Ww), nullptr, N, Hh, Ww, st))) return rc;
-        dim3 grid((unsigned)cdiv(Hh * Ww, 256), (unsigned)f1, (unsigned)N);
-        hipLaunchKernelGGL(upsample_add_relu_kernel, grid, dim3(256), 0, st, a1, feat2, f1, h, w, Hh, Ww);
-        NND_LAUNCH_CHECK();
+        if ((rc = pw(fa1, feat1, a1, nullptr, N, h, w))) return rc;
+        if ((rc = pw(fb1, stem, feat2, nullptr, N, Hh, Ww))) return rc;
+        if ((rc = run_upsample_add_relu(a1, feat2, N, desc->fusion_dim[1], h, w, Hh, Ww, st))) return rc;
     }
-    const int cd = desc->cnet_dim;
-    if ((rc = run_pw(cp0, packed, feat0, bs(c3, s.h[5], s.w[5]), cnet0, bs(cd, s.h[5], s.w[5]), nullptr, B, s.h[5], s.w[5], st))) return rc;
-    if ((rc = run_pw(cp1, packed, feat1, bs(f0, s.h[3], s.w[3]), cnet1, bs(cd, s.h[3], s.w[3]), nullptr, B, s.h[3], s.w[3], st))) return rc;
-    if ((rc = run_pw(cp2, packed, feat2, bs(f1, s.h[1], s.w[1]), cnet2, bs(cd, s.h[1], s.w[1]), nullptr, B, s.h[1], s.w[1], st))) return rc;
-    return NND_OK;
+    if ((rc = pw(cp0, feat0, cnet0, nullptr, B, s.h[5], s.w[5]))) return rc;
+    if ((rc = pw(cp1, feat1, cnet1, nullptr, B, s.h[3], s.w[3]))) return rc;
+    return pw(cp2, feat2, cnet2, nullptr, B, s.h[1], s.w[1]);
 }
 
 }  // extern "C"

@@ -983,7 +983,48 @@ def _stride1(s, what: str) -> int:
     return int(pair[0])
 
 
-class RepViTEngine:
+def _layer(kind: str, w: torch.Tensor, b: torch.Tensor, stride: int = 1, act: str = "none", skip: bool = False, s=None) -> dict:
+    """One folded layer of an encoder side: weight, bias, optional per-channel scale; k is the weight's kernel size."""
+    return {"kind": kind, "w": w, "b": b, "s": s, "k": w.shape[-1], "stride": stride, "act": act, "skip": skip}
+
+
+class _FoldedEngine:
+    """What the three folded encoder sides share: the layers packed into one blob by the library (nnd_<abi>_num_tensors /
+    _packed_floats / _pack, `_tensors` host tensors per layer: weight, bias [, scale or None]) and the cached workspace."""
+
+    _abi: str  # "repvit" | "mbv3" | "midas"
+    _tensors = 2
+
+    def __init__(self, desc, layers: List[dict], device):
+        self.desc, self.layers = desc, layers
+        name, abi, tpl = type(self).__name__, self._abi, self._tensors
+        n = int(getattr(lib, f"nnd_{abi}_num_tensors")(C.byref(desc)))
+        if n < 0:
+            check(n, f"{abi}_num_tensors")
+        if n != tpl * len(layers):
+            raise NndError(f"{name}: {len(layers)} layers folded, the library expects {n // tpl}")
+        host = []  # kept alive across the call
+        for l in layers:
+            host += [None if t is None else t.float().contiguous() for t in (l["w"], l["b"], l["s"])[:tpl]]
+        arr = (C.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in host])
+        total = int(getattr(lib, f"nnd_{abi}_packed_floats")(C.byref(desc)))
+        if total <= 0:
+            check(total, f"{abi}_packed_floats")
+        blob = torch.empty(total, dtype=torch.float32)
+        check(getattr(lib, f"nnd_{abi}_pack")(C.byref(desc), arr, _p(blob)), f"{abi}_pack")
+        self.packed = blob.to(device)
+        self._ws = None
+
+    def _workspace(self, need: int, device: torch.device) -> torch.Tensor:
+        """The cached workspace, grown to `need` floats (a negative `need` is the library's status: raised)."""
+        if need < 0:
+            check(need, f"{self._abi}_workspace_floats")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.float32, device=device)
+        return self._ws
+
+
+class RepViTEngine(_FoldedEngine):
     """The encoder side of Coarse2FineGroupRepViTRAFTStereo on the HIP path (csrc/repvit.hip, ONE call: nnd_repvit_forward), packed
     from the train-time modules of nndepth_amd.rep_vit (or of a reference instance: the same layout).  `fold(...)` turns every block
     into the plain layer chain the kernels run, in float64 on the host:
@@ -996,24 +1037,7 @@ class RepViTEngine:
       FeatureFusionBlock    the 1x1 conv3 split in its two input halves and composed with conv1 / conv2
     then casts once to fp32.  Each layer is a dict {kind: stem|dw|pw, w, b, s (scale or None), stride, act: none|gelu|resid}."""
 
-    def __init__(self, desc: RepViTDesc, layers: List[dict], device):
-        self.desc, self.layers = desc, layers
-        n = int(lib.nnd_repvit_num_tensors(C.byref(desc)))
-        if n < 0:
-            check(n, "repvit_num_tensors")
-        if n != 3 * len(layers):
-            raise NndError(f"RepViTEngine: {len(layers)} layers folded, the library expects {n // 3}")
-        host = []
-        for l in layers:
-            host += [l["w"].contiguous(), l["b"].contiguous(), None if l["s"] is None else l["s"].contiguous()]
-        arr = (C.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in host])
-        total = int(lib.nnd_repvit_packed_floats(C.byref(desc)))
-        if total <= 0:
-            check(total, "repvit_packed_floats")
-        blob = torch.empty(total, dtype=torch.float32)
-        check(lib.nnd_repvit_pack(C.byref(desc), arr, _p(blob)), "repvit_pack")
-        self.packed = blob.to(device)
-        self._ws = None
+    _abi, _tensors = "repvit", 3
 
     # ---------------------------------------------------------------- checks
     @staticmethod
@@ -1085,9 +1109,6 @@ class RepViTEngine:
     # ---------------------------------------------------------------- host fold
     @staticmethod
     def fold(fnet, cnet_proj, fusion_blocks) -> List[dict]:
-        def lay(kind, w, b, stride=1, act="none", s=None):
-            return {"kind": kind, "w": w.float(), "b": b.float(), "s": None if s is None else s.float(), "stride": stride, "act": act}
-
         def ls_of(t):
             return _d(t).reshape(-1) if t is not None else None
 
@@ -1095,12 +1116,12 @@ class RepViTEngine:
             w, b = _conv_wb(conv)
             if ls is None:
                 ls = torch.ones(w.shape[0], dtype=torch.float64)
-            return lay("pw", w, ls * b, act="resid", s=ls)
+            return _layer("pw", w, ls * b, act="resid", s=ls)
 
         L = []
         for i, m in enumerate(fnet.stem):
             w, b = _fold_mobileone(m)
-            L.append(lay("stem" if i == 0 else ("dw" if m.groups > 1 else "pw"), w, b, _stride1(m.stride, "stem"), "gelu"))
+            L.append(_layer("stem" if i == 0 else ("dw" if m.groups > 1 else "pw"), w, b, _stride1(m.stride, "stem"), "gelu"))
         for i in range(4):
             stage = getattr(fnet, f"stage_{i}")
             lk, pw = stage[0].proj
@@ -1108,14 +1129,14 @@ class RepViTEngine:
             if hasattr(lk, "small_conv"):
                 ws, bs = _fold_conv_bn(lk.small_conv, lk.kernel_size)
                 w, b = w + ws, b + bs
-            L.append(lay("dw", w, b, _stride1(lk.stride, "patch embed"), "none"))  # no activation: conv.py:454
+            L.append(_layer("dw", w, b, _stride1(lk.stride, "patch embed"), "none"))  # no activation: conv.py:454
             w, b = _fold_mobileone(pw)
-            L.append(lay("pw", w, b, 1, "gelu"))
+            L.append(_layer("pw", w, b, 1, "gelu"))
             for blk in stage[1]:
                 if type(blk).__name__ == "AttentionBlock":
                     s, t = _bn_affine(blk.norm)
                     wq, bq = _conv_wb(blk.token_mixer.qkv_proj)
-                    L.append(lay("pw", wq * s.reshape(1, -1, 1, 1), bq + wq[:, :, 0, 0] @ t, 1, "none"))
+                    L.append(_layer("pw", wq * s.reshape(1, -1, 1, 1), bq + wq[:, :, 0, 0] @ t, 1, "none"))
                     L.append(resid(blk.token_mixer.out_proj, ls_of(getattr(blk, "layer_scale_1", None))))
                     ffn, ls = blk.convffn, ls_of(getattr(blk, "layer_scale_2", None))
                 else:
@@ -1123,26 +1144,26 @@ class RepViTEngine:
                     wm, bm = _fold_mobileone(tm.mixer)
                     wn, bn = _fold_mobileone(tm.norm)
                     lsm = _d(tm.layer_scale).reshape(-1, 1, 1, 1) if tm.use_layer_scale else torch.ones(tm.dim, 1, 1, 1, dtype=torch.float64)
-                    L.append(lay("dw", _identity_kernel(tm.dim, tm.dim, tm.kernel_size) + lsm * (wm - wn), lsm.reshape(-1) * (bm - bn), 1,
+                    L.append(_layer("dw", _identity_kernel(tm.dim, tm.dim, tm.kernel_size) + lsm * (wm - wn), lsm.reshape(-1) * (bm - bn), 1,
                                  "none"))
                     ffn = blk.convffn if blk.use_ffn else None
                     ls = ls_of(getattr(blk, "layer_scale", None)) if ffn is not None and blk.use_layer_scale else None
                 if ffn is not None:
                     w, b = _conv_wb(ffn.fc1)
-                    L.append(lay("pw", w, b, 1, "gelu"))
+                    L.append(_layer("pw", w, b, 1, "gelu"))
                     L.append(resid(ffn.fc2, ls))
         for m in cnet_proj:
             w, b = _fold_mobileone(m)
-            L.append(lay("pw", w, b, 1, "gelu"))
+            L.append(_layer("pw", w, b, 1, "gelu"))
         for fb in fusion_blocks:
             w1, b1 = _conv_wb(fb.conv1)
             w2, b2 = _conv_wb(fb.conv2)
             w3, b3 = _conv_wb(fb.conv3)
             c1 = w1.shape[0]
             w3a, w3b = w3[:, :c1, 0, 0], w3[:, c1:, 0, 0]
-            L.append(lay("pw", (w3a @ w1[:, :, 0, 0])[:, :, None, None], w3a @ b1, 1, "none"))        # coarse half (before the upsample)
-            L.append(lay("pw", (w3b @ w2[:, :, 0, 0])[:, :, None, None], w3b @ b2 + b3, 1, "none"))   # fine half
-        return L
+            L.append(_layer("pw", (w3a @ w1[:, :, 0, 0])[:, :, None, None], w3a @ b1, 1, "none"))        # coarse half (before the upsample)
+            L.append(_layer("pw", (w3b @ w2[:, :, 0, 0])[:, :, None, None], w3b @ b2 + b3, 1, "none"))   # fine half
+        return [dict(l, w=l["w"].float(), b=l["b"].float(), s=None if l["s"] is None else l["s"].float()) for l in L]
 
     @staticmethod
     def fold_forward(layers: List[dict], desc: RepViTDesc, frame1: torch.Tensor, frame2: torch.Tensor):
@@ -1216,14 +1237,10 @@ class RepViTEngine:
         f = lambda n, c, hw: torch.empty((n, c) + tuple(hw), dtype=torch.float32, device=d)  # noqa: E731
         feats = [f(N, ds.channels[3], s3_hw), f(N, ds.fusion_dim[0], s1_hw), f(N, ds.fusion_dim[1], stem_hw)]
         cnets = [f(B, ds.cnet_dim, s3_hw), f(B, ds.cnet_dim, s1_hw), f(B, ds.cnet_dim, stem_hw)]
-        need = int(lib.nnd_repvit_workspace_floats(C.byref(ds), N, H, W))
-        if need < 0:
-            check(need, "repvit_workspace_floats")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
-            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        ws = self._workspace(int(lib.nnd_repvit_workspace_floats(C.byref(ds), N, H, W)), d)
         with torch.cuda.device(d):
             check(lib.nnd_repvit_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), B, *[_p(t) for t in feats + cnets],
-                                         _p(self._ws), N, H, W, _stream(d)), "repvit_forward")
+                                         _p(ws), N, H, W, _stream(d)), "repvit_forward")
         return feats, cnets
 
 
@@ -1242,31 +1259,70 @@ def _mbv3_layout() -> List[Tuple[str, Tuple[int, ...]]]:
     return _MBV3_LAYOUT
 
 
-class MobileNetV3Engine:
+def _check_mbv3_backbone(enc, hooks, who: str, what: str, any_order: bool = False) -> None:
+    """NndError unless `enc` (named `what` in `who`'s messages) is nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder with
+    tf_mobilenetv3_large_100's parameter layout and the feature hooks `hooks` (any_order: in any order)."""
+    from . import mobilenetv3 as mb
+    if not isinstance(enc, mb.MobilenetV3LargeEncoder) or not isinstance(getattr(enc, "backbone", None), mb.MobileNetV3Features):
+        raise NndError(f"{who}: {what} is a {type(enc).__name__}, not nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder")
+    got = [(k, tuple(v.shape)) for k, v in enc.state_dict().items()]
+    want = _mbv3_layout()
+    if got != want:
+        bad = next((w for g, w in zip(got, want) if g != w), want[len(got)] if len(got) < len(want) else got[len(want)])
+        raise NndError(f"{who}: {what}'s parameters differ from tf_mobilenetv3_large_100's layout (first difference at "
+                       f"{bad[0]}); a replaced or reshaped block is not built")
+    if (sorted(enc.feature_hooks) if any_order else list(enc.feature_hooks)) != list(hooks):
+        raise NndError(f"{who}: feature_hooks {enc.feature_hooks} (built: {list(hooks)})")
+
+
+def _mbv3_conv(x: torch.Tensor, l: dict, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One folded MobileNetV3 / MiDaS layer as F.conv2d in x's dtype: TF "same" padding for the stem and the depthwise convs,
+    padding k // 2 for the others (0 for a 1x1); then the layer's activation, then the residual."""
+    from .mobilenetv3 import same_pad
+    F = torch.nn.functional
+    w, b = l["w"].to(x), l["b"].to(x)
+    if l["kind"] in ("stem", "dw"):
+        y = F.conv2d(same_pad(x, l["k"], l["stride"]), w, b, stride=l["stride"], groups=x.shape[1] if l["kind"] == "dw" else 1)
+    else:
+        y = F.conv2d(x, w, b, padding=l["k"] // 2)
+    if l["act"] == "relu":
+        y = F.relu(y)
+    elif l["act"] == "hswish":
+        y = F.hardswish(y)
+    elif l["act"] == "hsigmoid":
+        y = F.hardsigmoid(y)
+    return res + y if res is not None else y
+
+
+def _mbv3_backbone_forward(it, x: torch.Tensor, n_left: Optional[int] = None) -> List[torch.Tensor]:
+    """The stem and stages 0..5 over the folded layers `it` yields, in the kernels' layer order -> the six stage outputs.  n_left:
+    stages 2..5 run on the first n_left samples only (the left frames; eval BatchNorm is per sample)."""
+    from .mobilenetv3 import block_table
+    x = _mbv3_conv(x, next(it))
+    stages = []
+    for si, specs in enumerate(block_table()[:6]):
+        if si == 2 and n_left is not None:
+            x = x[:n_left]
+        for sp in specs:
+            inp = x
+            if sp["type"] == "ir":
+                x = _mbv3_conv(x, next(it))
+            x = _mbv3_conv(x, next(it))
+            if sp["rd"]:
+                x = x * _mbv3_conv(_mbv3_conv(x.mean((2, 3), keepdim=True), next(it)), next(it))
+            x = _mbv3_conv(x, next(it), res=inp if sp["skip"] else None)
+        stages.append(x)
+    return stages
+
+
+class MobileNetV3Engine(_FoldedEngine):
     """The encoder side of IGEVStereoMBNet on the HIP path (csrc/mbv3.hip, ONE call: nnd_mbv3_forward), packed from the modules of
     nndepth_amd.mobilenetv3 plus fnet_proj / cnet_proj.  `fold(...)` folds every eval-mode BatchNorm into its conv in float64 on the
     host (W * s, t with s = gamma / sqrt(var + eps), t = beta - mean * s); the SE convs and the projections keep their own biases.
     The layers are cast once to fp32 when packed.  Each layer is a dict {kind: stem|dw|pw|se_r|se_e|proj, w, b (float64), k,
     stride, act: none|relu|hswish, skip}."""
 
-    def __init__(self, desc: MobileNetV3Desc, layers: List[dict], device):
-        self.desc, self.layers = desc, layers
-        n = int(lib.nnd_mbv3_num_tensors(C.byref(desc)))
-        if n < 0:
-            check(n, "mbv3_num_tensors")
-        if n != 2 * len(layers):
-            raise NndError(f"MobileNetV3Engine: {len(layers)} layers folded, the library expects {n // 2}")
-        host = []
-        for l in layers:
-            host += [l["w"].float().contiguous(), l["b"].float().contiguous()]
-        arr = (C.c_void_p * n)(*[t.data_ptr() for t in host])
-        total = int(lib.nnd_mbv3_packed_floats(C.byref(desc)))
-        if total <= 0:
-            check(total, "mbv3_packed_floats")
-        blob = torch.empty(total, dtype=torch.float32)
-        check(lib.nnd_mbv3_pack(C.byref(desc), arr, _p(blob)), "mbv3_pack")
-        self.packed = blob.to(device)
-        self._ws = None
+    _abi = "mbv3"
 
     # ---------------------------------------------------------------- checks
     @staticmethod
@@ -1283,16 +1339,7 @@ class MobileNetV3Engine:
     @staticmethod
     def descriptor(fnet, fnet_proj, cnet_proj) -> MobileNetV3Desc:
         from . import mobilenetv3 as mb
-        if not isinstance(fnet, mb.MobilenetV3LargeEncoder) or not isinstance(getattr(fnet, "backbone", None), mb.MobileNetV3Features):
-            raise NndError(f"MobileNetV3Engine: fnet is a {type(fnet).__name__}, not nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder")
-        got = [(k, tuple(v.shape)) for k, v in fnet.state_dict().items()]
-        want = _mbv3_layout()
-        if got != want:
-            bad = next((w for g, w in zip(got, want) if g != w), want[len(got)] if len(got) < len(want) else got[len(want)])
-            raise NndError(f"MobileNetV3Engine: fnet's parameters differ from tf_mobilenetv3_large_100's layout (first difference at "
-                           f"{bad[0]}); a replaced or reshaped block is not built")
-        if sorted(fnet.feature_hooks) != list(mb.HOOKS):
-            raise NndError(f"MobileNetV3Engine: feature_hooks {fnet.feature_hooks} (built: {list(mb.HOOKS)})")
+        _check_mbv3_backbone(fnet, mb.HOOKS, "MobileNetV3Engine", "fnet", any_order=True)
         cls = {"ds": mb.DepthwiseSeparable, "ir": mb.InvertedResidual, "cn": mb.ConvBnAct}
         for i, (stage, specs) in enumerate(zip(fnet.backbone.blocks, mb.block_table())):
             for j, (blk, spec) in enumerate(zip(stage, specs)):
@@ -1323,82 +1370,43 @@ class MobileNetV3Engine:
     @staticmethod
     def fold_backbone(fnet) -> List[dict]:
         """The backbone's layers alone (stem and stages 0..5), shared with MidasEngine."""
-        def lay(kind, w, b, k=1, stride=1, act="none", skip=False):
-            return {"kind": kind, "w": w, "b": b, "k": k, "stride": stride, "act": act, "skip": skip}
-
         def cbn(conv, bn):
             s, t = _bn_affine(bn)
             return _d(conv.weight) * s.reshape(-1, 1, 1, 1), t
 
         bb = fnet.backbone
-        L = [lay("stem", *cbn(bb.conv_stem, bb.bn1), 3, 2, "hswish")]
+        L = [_layer("stem", *cbn(bb.conv_stem, bb.bn1), 2, "hswish")]
         for stage in list(bb.blocks)[:6]:  # stage 6's output is never used
             for blk in stage:
                 sp = blk.spec
                 act = "relu" if sp["relu"] else "hswish"
                 if sp["type"] == "ds":
-                    L.append(lay("dw", *cbn(blk.conv_dw, blk.bn1), sp["k"], sp["stride"], act))
-                    L.append(lay("pw", *cbn(blk.conv_pw, blk.bn2), skip=sp["skip"]))
+                    L.append(_layer("dw", *cbn(blk.conv_dw, blk.bn1), sp["stride"], act))
+                    L.append(_layer("pw", *cbn(blk.conv_pw, blk.bn2), skip=sp["skip"]))
                     continue
-                L.append(lay("pw", *cbn(blk.conv_pw, blk.bn1), act=act))
-                L.append(lay("dw", *cbn(blk.conv_dw, blk.bn2), sp["k"], sp["stride"], act))
+                L.append(_layer("pw", *cbn(blk.conv_pw, blk.bn1), act=act))
+                L.append(_layer("dw", *cbn(blk.conv_dw, blk.bn2), sp["stride"], act))
                 if sp["rd"]:
-                    L.append(lay("se_r", *_conv_wb(blk.se.conv_reduce), act="relu"))
-                    L.append(lay("se_e", *_conv_wb(blk.se.conv_expand), act="hsigmoid"))
-                L.append(lay("pw", *cbn(blk.conv_pwl, blk.bn3), skip=sp["skip"]))
+                    L.append(_layer("se_r", *_conv_wb(blk.se.conv_reduce), act="relu"))
+                    L.append(_layer("se_e", *_conv_wb(blk.se.conv_expand), act="hsigmoid"))
+                L.append(_layer("pw", *cbn(blk.conv_pwl, blk.bn3), skip=sp["skip"]))
         return L
 
     @staticmethod
     def fold(fnet, fnet_proj, cnet_proj) -> List[dict]:
-        def lay(kind, w, b, k=1, stride=1, act="none", skip=False):
-            return {"kind": kind, "w": w, "b": b, "k": k, "stride": stride, "act": act, "skip": skip}
-
         L = MobileNetV3Engine.fold_backbone(fnet)
         for seq in (fnet_proj, cnet_proj):
-            L.append(lay("proj", *_conv_wb(seq[0]), 3, 1, "relu"))
+            L.append(_layer("proj", *_conv_wb(seq[0]), act="relu"))
         return L
 
     @staticmethod
     def fold_forward(layers: List[dict], frame1: torch.Tensor, frame2: torch.Tensor):
         """The folded chain as plain F.conv2d calls in the kernels' layer order and in the frames' dtype (float64: the fold checked
         without a GPU).  -> (fmap1, fmap2, cnet1, [guide0, guide1, guide2], stage outputs of the left frames)."""
-        from .mobilenetv3 import block_table, same_pad
-        F = torch.nn.functional
-        it = iter(layers)
-
-        def conv(x, l, res=None):
-            w, b = l["w"].to(x), l["b"].to(x)
-            groups = x.shape[1] if l["kind"] == "dw" else 1
-            pad_x = same_pad(x, l["k"], l["stride"]) if l["kind"] in ("stem", "dw") else x
-            y = F.conv2d(pad_x, w, b, stride=l["stride"], padding=l["k"] // 2 if l["kind"] == "proj" else 0, groups=groups)
-            if l["act"] == "relu":
-                y = F.relu(y)
-            elif l["act"] == "hswish":
-                y = F.hardswish(y)
-            elif l["act"] == "hsigmoid":
-                y = F.hardsigmoid(y)
-            return res + y if res is not None else y
-
         B = frame1.shape[0]
-        x = conv(torch.cat([frame1, frame2], 0), next(it))
-        stages = []
-        for si, specs in enumerate(block_table()[:6]):
-            if si == 2:
-                x = x[:B]  # stages 2..5: the left frames only (eval BatchNorm is per sample)
-            for sp in specs:
-                inp = x
-                if sp["type"] == "ir":
-                    x = conv(x, next(it))
-                x = conv(x, next(it))
-                if sp["rd"]:
-                    g = conv(conv(x.mean((2, 3), keepdim=True), next(it)), next(it))
-                    x = x * g
-                x = conv(x, next(it), res=inp if sp["skip"] else None)
-            stages.append(x)
-            if si == 1:
-                fp, cp = layers[-2], layers[-1]
-                fmaps = conv(x, fp)
-                cnet1 = conv(x[:B], cp)
+        stages = _mbv3_backbone_forward(iter(layers), torch.cat([frame1, frame2], 0), n_left=B)
+        fmaps = _mbv3_conv(stages[1], layers[-2])
+        cnet1 = _mbv3_conv(stages[1][:B], layers[-1])
         return fmaps[:B], fmaps[B:], cnet1, [stages[2], stages[3], stages[5]], [s[:B] for s in stages]
 
     @classmethod
@@ -1421,18 +1429,14 @@ class MobileNetV3Engine:
         f = lambda c, s: torch.empty((B, c) + s, dtype=torch.float32, device=d)  # noqa: E731
         fmap1, fmap2, cnet1 = f(ds.fnet_dim, hw[2]), f(ds.fnet_dim, hw[2]), f(ds.cnet_dim, hw[2])
         guides = [f(40, hw[3]), f(80, hw[4]), f(160, hw[5])]
-        need = int(lib.nnd_mbv3_workspace_floats(C.byref(ds), B, H, W))
-        if need < 0:
-            check(need, "mbv3_workspace_floats")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
-            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        ws = self._workspace(int(lib.nnd_mbv3_workspace_floats(C.byref(ds), B, H, W)), d)
         with torch.cuda.device(d):
             check(lib.nnd_mbv3_forward(C.byref(ds), _p(self.packed), _p(frame1), _p(frame2), _p(fmap1), _p(fmap2), _p(cnet1),
-                                       *[_p(g) for g in guides], _p(self._ws), B, H, W, _stream(d)), "mbv3_forward")
+                                       *[_p(g) for g in guides], _p(ws), B, H, W, _stream(d)), "mbv3_forward")
         return fmap1, fmap2, cnet1, guides
 
 
-class MidasEngine:
+class MidasEngine(_FoldedEngine):
     """MobileNetV3DepthModel on the HIP path (csrc/midas.hip, ONE call per forward: nnd_midas_forward), packed from the modules of
     nndepth_amd.midas.  `fold(model)` folds every eval-mode BatchNorm into its conv in float64 on the host, as
     MobileNetV3Engine.fold; the layers are cast once to fp32 when packed.  Layer order: the backbone (MobileNetV3Engine.
@@ -1441,39 +1445,13 @@ class MidasEngine:
 
     MAPS = ("tap0", "tap1", "tap2", "tap3", "decoder", "pre_relu")
 
-    def __init__(self, desc: MidasDesc, layers: List[dict], device):
-        self.desc, self.layers = desc, layers
-        n = int(lib.nnd_midas_num_tensors(C.byref(desc)))
-        if n < 0:
-            check(n, "midas_num_tensors")
-        if n != 2 * len(layers):
-            raise NndError(f"MidasEngine: {len(layers)} layers folded, the library expects {n // 2}")
-        host = []
-        for l in layers:
-            host += [l["w"].float().contiguous(), l["b"].float().contiguous()]
-        arr = (C.c_void_p * n)(*[t.data_ptr() for t in host])
-        total = int(lib.nnd_midas_packed_floats(C.byref(desc)))
-        if total <= 0:
-            check(total, "midas_packed_floats")
-        blob = torch.empty(total, dtype=torch.float32)
-        check(lib.nnd_midas_pack(C.byref(desc), arr, _p(blob)), "midas_pack")
-        self.packed = blob.to(device)
-        self._ws = None
+    _abi = "midas"
 
     @staticmethod
     def descriptor(model) -> MidasDesc:
         """The descriptor of a nndepth_amd.midas.MobileNetV3DepthModel, or NndError naming what the HIP path does not build."""
         from . import midas as md
-        from . import mobilenetv3 as mb
-        enc = getattr(model, "encoder", None)
-        if not isinstance(enc, mb.MobilenetV3LargeEncoder) or not isinstance(getattr(enc, "backbone", None), mb.MobileNetV3Features):
-            raise NndError(f"MidasEngine: encoder is a {type(enc).__name__}, not nndepth_amd.mobilenetv3.MobilenetV3LargeEncoder")
-        got = [(k, tuple(v.shape)) for k, v in enc.state_dict().items()]
-        if got != _mbv3_layout():
-            raise NndError("MidasEngine: the encoder's parameters differ from tf_mobilenetv3_large_100's layout; a replaced or reshaped "
-                           "block is not built")
-        if list(enc.feature_hooks) != list(md.HOOKS):
-            raise NndError(f"MidasEngine: feature_hooks {enc.feature_hooks} (built: {list(md.HOOKS)})")
+        _check_mbv3_backbone(getattr(model, "encoder", None), md.HOOKS, "MidasEngine", "encoder")
         dec = getattr(model, "decoder", None)
         if not isinstance(dec, md.BaseDecoder) or list(dec.in_channels) != list(md.TAP_CHANNELS) or len(set(dec.out_channels)) != 1:
             raise NndError("MidasEngine: decoder is not BaseDecoder([24, 40, 112, 160], [C] * 4)")
@@ -1493,9 +1471,6 @@ class MidasEngine:
 
     @staticmethod
     def fold(model) -> List[dict]:
-        def lay(kind, w, b, k=1, act="none"):
-            return {"kind": kind, "w": w, "b": b, "k": k, "stride": 1, "act": act, "skip": False}
-
         def cbn(conv, bn):
             s, t = _bn_affine(bn)
             w, b = _conv_wb(conv)
@@ -1504,53 +1479,27 @@ class MidasEngine:
         L = MobileNetV3Engine.fold_backbone(model.encoder)
         dec = model.decoder
         for seq in dec.skip_layers:
-            L.append(lay("skip", *_conv_wb(seq[0]), 3, "relu"))
+            L.append(_layer("skip", *_conv_wb(seq[0]), act="relu"))
         for i, blk in enumerate(dec.upsampler_layers):
             if i < len(dec.upsampler_layers) - 1:  # the last block runs with skip_feat=None: conv1 / bn1 are never evaluated
-                L.append(lay("up_conv1", *cbn(blk.conv1, blk.bn1), 3, "relu"))
-            L.append(lay("up_conv2", *cbn(blk.conv2, blk.bn2), 3, "relu"))
-            L.append(lay("up_out", *_conv_wb(blk.out_conv), 1, "relu"))
+                L.append(_layer("up_conv1", *cbn(blk.conv1, blk.bn1), act="relu"))
+            L.append(_layer("up_conv2", *cbn(blk.conv2, blk.bn2), act="relu"))
+            L.append(_layer("up_out", *_conv_wb(blk.out_conv), act="relu"))
         lc = model.last_conv
-        L.append(lay("last0", *_conv_wb(lc[0]), 3))
-        L.append(lay("last2", *_conv_wb(lc[2]), 3, "relu"))
-        L.append(lay("last4", *_conv_wb(lc[4]), 1, "relu"))
+        L.append(_layer("last0", *_conv_wb(lc[0])))
+        L.append(_layer("last2", *_conv_wb(lc[2]), act="relu"))
+        L.append(_layer("last4", *_conv_wb(lc[4]), act="relu"))
         return L
 
     @staticmethod
     def fold_forward(layers: List[dict], x: torch.Tensor) -> Dict[str, torch.Tensor]:
         """The folded chain as plain F.conv2d / F.interpolate calls in the kernels' layer order and in x's dtype (float64: the
         fold checked without a GPU).  -> {tap0..tap3, decoder, pre_relu, depth}."""
-        from .mobilenetv3 import block_table, same_pad
         F = torch.nn.functional
         it = iter(layers)
-
-        def conv(x, l, res=None):
-            w, b = l["w"].to(x), l["b"].to(x)
-            if l["kind"] in ("stem", "dw"):
-                y = F.conv2d(same_pad(x, l["k"], l["stride"]), w, b, stride=l["stride"], groups=x.shape[1] if l["kind"] == "dw" else 1)
-            else:
-                y = F.conv2d(x, w, b, padding=l["k"] // 2)
-            if l["act"] == "relu":
-                y = F.relu(y)
-            elif l["act"] == "hswish":
-                y = F.hardswish(y)
-            elif l["act"] == "hsigmoid":
-                y = F.hardsigmoid(y)
-            return res + y if res is not None else y
-
+        conv = _mbv3_conv
         up = lambda t: F.interpolate(t, scale_factor=2, mode="bilinear", align_corners=False)  # noqa: E731
-        x = conv(x, next(it))
-        stages = []
-        for specs in block_table()[:6]:
-            for sp in specs:
-                inp = x
-                if sp["type"] == "ir":
-                    x = conv(x, next(it))
-                x = conv(x, next(it))
-                if sp["rd"]:
-                    x = x * conv(conv(x.mean((2, 3), keepdim=True), next(it)), next(it))
-                x = conv(x, next(it), res=inp if sp["skip"] else None)
-            stages.append(x)
+        stages = _mbv3_backbone_forward(it, x)
         taps = [stages[i] for i in (1, 2, 4, 5)]
         skips = [conv(t, next(it)) for t in taps]
         rest = list(it)
@@ -1581,14 +1530,10 @@ class MidasEngine:
         x = x.contiguous()
         B, _, H, W = x.shape
         ds = MidasDesc(feature_channels=self.desc.feature_channels, flags=NND_MIDAS_KEEP_PRE if keep else 0)
-        need = int(lib.nnd_midas_workspace_floats(C.byref(ds), B, H, W))
-        if need < 0:
-            check(need, "midas_workspace_floats")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != d:
-            self._ws = torch.empty(need, dtype=torch.float32, device=d)
+        ws = self._workspace(int(lib.nnd_midas_workspace_floats(C.byref(ds), B, H, W)), d)
         depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
         with torch.cuda.device(d):
-            check(lib.nnd_midas_forward(C.byref(ds), _p(self.packed), _p(x), _p(depth), _p(self._ws), B, H, W, _stream(d)), "midas_forward")
+            check(lib.nnd_midas_forward(C.byref(ds), _p(self.packed), _p(x), _p(depth), _p(ws), B, H, W, _stream(d)), "midas_forward")
         if not keep:
             return depth
         Cc = ds.feature_channels
@@ -1599,7 +1544,7 @@ class MidasEngine:
             if off < 0:
                 check(off, "midas_workspace_offset")
             n = shp[0] * shp[1] * shp[2] * shp[3]
-            maps[name] = self._ws[off:off + n].view(shp)
+            maps[name] = ws[off:off + n].view(shp)
         return depth, maps
 
 

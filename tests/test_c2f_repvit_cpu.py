@@ -2,6 +2,7 @@
 (tests/golden/c2f_repvit.npz, scripts/make_golden_c2f_repvit.py), the containers' PyTorch forward and the host fold
 (ops.RepViTEngine.fold) against the reference's encoder-side maps, and the refusals of the C-ABI / Python side."""
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -127,6 +128,34 @@ def test_cabi_refuses_bad_descriptors_before_any_launch():
     bad = RepViTDesc.from_buffer_copy(d)
     bad.stem_strides[0] = 4
     assert lib.nnd_repvit_forward(C.byref(bad), None, None, None, 1, None, None, None, None, None, None, None, 2, 64, 96, None) < 0
+
+
+# (num_tensors, packed_floats, SHA-256 of the packed blob) per configuration, as the commit before the encoder sides moved onto one
+# layer plan (csrc/enc_plan.h) produced them (weightgen 'c2frv.')
+PLAN_PINS = {
+    "default": (180, 2360064, "5524dfda1bc9454f95abfafd7806332c17af8588a129952aae48f0959997c3d2"),
+    "alt": (102, 952576, "b456ea84952f89ebbe8ed2f47309f2b183643224035132c738c4d2158f3dbc87"),
+}
+
+
+@pytest.mark.parametrize("cfg", list(CONFIGS))
+def test_repvit_plan_and_pack_unchanged(cfg):
+    """nnd_repvit_* build their plan and pack through the code they share with nnd_mbv3_* and nnd_midas_* (csrc/enc_plan.h).  Sizes
+    and the SHA-256 of the packed blob are the values of the commit before that refactor (PLAN_PINS; the workspace and the
+    single-layer sizes are the same for both configurations)."""
+    from nndepth_amd._lib import lib
+    from nndepth_amd.ops import RepViTEngine
+    m = build(cfg)
+    d = RepViTEngine.descriptor(m.fnet, m.cnet_proj, m.fusion_blocks)
+    n, floats, sha = PLAN_PINS[cfg]
+    assert lib.nnd_repvit_num_tensors(C.byref(d)) == n
+    assert lib.nnd_repvit_packed_floats(C.byref(d)) == floats
+    assert lib.nnd_repvit_workspace_floats(C.byref(d), 2, 64, 96) == 215296
+    assert lib.nnd_repvit_workspace_floats(C.byref(d), 2, 512, 960) == 17218560
+    assert lib.nnd_repvit_pointwise_packed_floats(192, 64, 1) == 12672
+    assert lib.nnd_repvit_pointwise_packed_floats(16, 16, 2) == 576
+    eng = RepViTEngine(d, RepViTEngine.fold(m.fnet, m.cnet_proj, m.fusion_blocks), "cpu")
+    assert hashlib.sha256(eng.packed.numpy().tobytes()).hexdigest() == sha
 
 
 def test_python_side_names_what_it_refuses():

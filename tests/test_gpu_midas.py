@@ -223,3 +223,26 @@ def test_igev_mbnet_encoder_side_still_matches_its_fixture():
         bar = 2.0 * float(g[name + "_err64"]) + 1e-6 * float(g[name + "_maxabs"])
         print(f"{name}: HIP vs reference fixture {err:.3e}, bar {bar:.3e}")
         assert err <= bar, (name, err, bar)
+
+
+def test_both_models_run_the_same_backbone_walk():
+    """The two models share ONE backbone walk (mbv3.hip: mb_walk).  With the same MobilenetV3LargeEncoder weights in both, MiDaS'
+    taps of stages 2 and 5 equal the stereo encoder side's guide0 and guide2 bit for bit on x = frame1.  B = 2: the stereo call
+    runs stages 0..1 on 4 samples and stages 2..5 on 2, the MiDaS call runs 2 throughout (fixed split-K per layer, per-sample
+    kernels: no output depends on the batch it runs in).  64x96 is the smallest size MiDaS accepts."""
+    from nndepth_amd.igev_stereo import IGEVStereoMBNet
+    from nndepth_amd.ops import MidasEngine, MobileNetV3Engine
+    md = build()
+    ig = IGEVStereoMBNet(iters=4)
+    weightgen.fill_module_(ig, "igevmb.")
+    ig.fnet.load_state_dict(md.encoder.state_dict(), strict=True)
+    ig = ig.eval().to(DEV)
+    assert list(md.encoder.feature_hooks) == [1, 2, 4, 5] and list(ig.fnet.feature_hooks) == [1, 2, 3, 4, 5]
+    f1, f2 = (t.to(DEV) for t in weightgen.synthetic_frames(11, 2, 64, 96))
+    with torch.no_grad():
+        _, maps = MidasEngine.from_model(md, DEV).forward(f1, keep=True)
+        _, _, _, guides = MobileNetV3Engine.from_modules(ig.fnet, ig.fnet_proj, ig.cnet_proj, DEV).forward(f1, f2)
+    assert maps["tap1"].shape == guides[0].shape == (2, 40, 8, 12) and maps["tap3"].shape == guides[2].shape == (2, 160, 2, 3)
+    assert maps["tap1"].abs().max().item() > 0 and maps["tap3"].abs().max().item() > 0
+    assert torch.equal(maps["tap1"], guides[0])
+    assert torch.equal(maps["tap3"], guides[2])

@@ -173,3 +173,22 @@ def test_mbv3_plan_and_pack_unchanged():
     m.eval()
     eng = MobileNetV3Engine(d, MobileNetV3Engine.fold(m.fnet, m.fnet_proj, m.cnet_proj), "cpu")
     assert hashlib.sha256(eng.packed.numpy().tobytes()).hexdigest() == "085ceb81451f949d1efa6a84d83b2279d41495ed25603b26befbdc4f019811aa"
+
+
+def test_midas_plan_and_pack_unchanged():
+    """nnd_midas_* build their plan, pack and size their workspace through the code they share with nnd_repvit_* and nnd_mbv3_*
+    (csrc/enc_plan.h, mbv3.hip's one backbone walk).  Sizes, offsets and the SHA-256 of the packed blob as the commit before that
+    refactor produced them (the model of build(), weightgen 'midas.')."""
+    from nndepth_amd._lib import lib
+    from nndepth_amd.ops import MidasEngine
+    m = build()
+    d = MidasEngine.descriptor(m)
+    assert lib.nnd_midas_num_tensors(C.byref(d)) == 158
+    assert lib.nnd_midas_packed_floats(C.byref(d)) == 3483584
+    assert lib.nnd_midas_workspace_floats(C.byref(d), 1, 64, 96) == 511488
+    assert lib.nnd_midas_workspace_floats(C.byref(d), 2, 544, 960) == 86486784
+    assert [lib.nnd_midas_workspace_offset(C.byref(d), i, 1, 64, 96) for i in range(6)] == [0, 9216, 13056, 15744, 130752, 327360]
+    assert lib.nnd_midas_up2x_pw_packed_floats(64, 64) == 4160
+    assert lib.nnd_midas_head_packed_floats(64) == 36993
+    eng = MidasEngine(d, MidasEngine.fold(m), "cpu")
+    assert hashlib.sha256(eng.packed.numpy().tobytes()).hexdigest() == "34c3c9fed865fa83cd8a0bfa5912a9d8dadb1ae6b5484611aea9482cc273ab1a"
