@@ -49,20 +49,14 @@ class BasicUpdateBlock(nn.Module):
         self.flow_head = fh
         self.mask = nn.Sequential(_conv(hidden_dim, hidden_dim * 2, 3, 1), nn.ReLU(inplace=True),
                                   _conv(hidden_dim * 2, sps * 9, 1, 0))
-        # arithmetic of the fused loops' convolutions: "fp32" (exact fp32 MFMA, default) or "bf16x3" (csrc/conv_split.hip)
+        # arithmetic of the fused loops' convolutions: "fp32" (exact fp32 MFMA, default), "bf16x3" (3 bf16 pieces) or "fp16x2"
+        # (2 range-scaled fp16 pieces), both in csrc/conv_split.hip
         self.engine = ops.UpdateBlockEngine(hidden_dim, context_dim, cor_planes, flow_channel, sps * 9, gru, arithmetic)
-        self._packed_version = None
-
-    def _version(self):
-        return tuple((p.data_ptr(), p._version, str(p.device)) for p in self.parameters())
+        self._packed = ops.ParamCache()
 
     def sync_engine(self, device) -> ops.UpdateBlockEngine:
         """(Re)pack the parameters for the HIP kernels if they changed since the last call."""
-        v = (self._version(), str(device))
-        if v != self._packed_version:
-            self.engine.load(self.state_dict(), device=device)
-            self._packed_version = v
-        return self.engine
+        return self._packed.get((self,), device, lambda: self.engine.load(self.state_dict(), device=device))
 
     @torch.no_grad()
     def forward(self, net: torch.Tensor, inp: torch.Tensor, corr: torch.Tensor, flow: torch.Tensor):

@@ -73,7 +73,7 @@ class LocalFeatureTransformer(nn.Module):
             raise ValueError("only the linear attention of CREStereo is provided")
         self.d_model, self.nhead, self.layer_names = d_model, nhead, list(layer_names)
         self.layers = nn.ModuleList([LoFTREncoderLayer(d_model, nhead) for _ in self.layer_names])
-        self._engines, self._version = None, None
+        self._engines = ops.ParamCache()
 
     def _layer_step(self, run, feat0, feat1):
         for i, name in enumerate(self.layer_names):
@@ -97,12 +97,9 @@ class LocalFeatureTransformer(nn.Module):
             n, c, h, w = map0.shape
             a, b = self.forward(map0.permute(0, 2, 3, 1).reshape(n, h * w, c), map1.permute(0, 2, 3, 1).reshape(n, h * w, c))
             return a.reshape(n, h, w, c).permute(0, 3, 1, 2), b.reshape(n, h, w, c).permute(0, 3, 1, 2)
-        v = (tuple((p.data_ptr(), p._version) for p in self.parameters()), str(map0.device))
-        if v != self._version:
-            self._engines = [ops.LoftrEngine(self.d_model, self.nhead).load(layer.state_dict(), device=map0.device)
-                             for layer in self.layers]
-            self._version = v
-        return self._layer_step(lambda i, a, b: self._engines[i].forward(a.float(), b.float()), map0, map1)
+        engines = self._engines.get((self,), map0.device, lambda: [
+            ops.LoftrEngine(self.d_model, self.nhead).load(layer.state_dict(), device=map0.device) for layer in self.layers])
+        return self._layer_step(lambda i, a, b: engines[i].forward(a.float(), b.float()), map0, map1)
 
 
 # ------------------------------------------------------------------ the model
@@ -128,7 +125,7 @@ class CREStereoBase(AutoCalibrate, nn.Module):
         self.tracing, self.include_preprocessing = tracing, include_preprocessing
         self.fused_loop = fused_loop
         self.hip_encoder = hip_encoder
-        self._enc_engine, self._enc_version = None, None
+        self._enc_cache, self._off_cache = ops.ParamCache(), ops.ParamCache()
         self.fnet = BasicEncoder(output_dim=num_fnet_channels, norm_fn="instance", dropout=0)
         self.fnet_ds = 8
         self.update_block = BasicUpdateBlock(hidden_dim=hidden_dim, cor_planes=4 * 9, flow_channel=2,
@@ -154,26 +151,17 @@ class CREStereoBase(AutoCalibrate, nn.Module):
             if why:
                 raise NndError(f"CREStereoBase: the HIP encoder cannot run this fnet ({why}); pass hip_encoder=False to run "
                                "the encoder's PyTorch-ROCm modules explicitly")
-            tensors = list(self.fnet.state_dict().values())
-            v = (tuple((t.data_ptr(), t._version) for t in tensors), str(frame1.device))
-            if v != self._enc_version:
-                if self._enc_engine is None:
-                    self._enc_engine = ops.EncoderEngine(self.fnet.conv2.out_channels, self.fnet.norm_fn, 0, self.arithmetic)
-                self._enc_engine.load(self.fnet.state_dict(), None, device=frame1.device)
-                self._enc_version = v
+            eng = self._enc_cache.get((self.fnet,), frame1.device, lambda: ops.EncoderEngine(
+                self.fnet.conv2.out_channels, self.fnet.norm_fn, 0, self.arithmetic).load(self.fnet.state_dict(), None, device=frame1.device))
             B = frame1.shape[0]
-            fmaps, _ = self._enc_engine.forward(frame1.float(), frames_b=frame2.float())  # no torch.cat copy (basic_encoder.py:74-76)
+            fmaps, _ = eng.forward(frame1.float(), frames_b=frame2.float())  # no torch.cat copy (basic_encoder.py:74-76)
             return fmaps[:B], fmaps[B:]
         return self.fnet([frame1, frame2])  # explicit opt-in (hip_encoder=False): PyTorch-ROCm modules
 
     def _offset_convs(self, device):
         """conv_offset_16 / conv_offset_8 packed for the MFMA conv (repacked when their parameters change)."""
         mods = (self.conv_offset_16, self.conv_offset_8)
-        v = (tuple((p.data_ptr(), p._version) for m in mods for p in m.parameters()), str(device))
-        if getattr(self, "_off_version", None) != v:
-            self._off_engines = tuple(ops.Conv2d(m.weight, m.bias, device=device) for m in mods)
-            self._off_version = v
-        return self._off_engines
+        return self._off_cache.get(mods, device, lambda: tuple(ops.Conv2d(m.weight, m.bias, device=device) for m in mods))
 
     def _stage(self, corr_fn, net, inp, flow, offset, n_iters: int, iter_mode: bool, outs: List[Dict[str, torch.Tensor]],
                last: bool = False):

@@ -17,7 +17,6 @@ two hooks for subclasses (`_init_fnet`, `_init_cost_volume_filter`, `forward_fne
 `IGEVStereoMBNet` is the reference's only concrete model (its STEREO_MODELS["igev_stereo_mbnet"]), built on the timm-free
 MobileNetV3-Large containers of nndepth_amd.mobilenetv3.
 """
-import itertools
 from typing import Dict, List, Optional
 
 import torch
@@ -30,7 +29,7 @@ from . import ops
 from ._lib import NndError
 from .blocks import BasicUpdateBlock
 from .cost_volume import GeometryAwareCostVolume
-from .raft_stereo import AutoCalibrate, check_outputs, last_only, load_weights, require_eval
+from .raft_stereo import AutoCalibrate, FoldedEncoderSide, check_outputs, last_only, load_weights, require_eval
 from .upsample import convex_upsample
 
 
@@ -83,7 +82,7 @@ class CostVolumeFilterNetwork(nn.Module):
         self.final_conv = _cbr3d(c, c, 1)
         self.hip = True  # on the GPU at inference: Conv3d / upsample / gating in HIP (False keeps the PyTorch ops)
         self.arithmetic = "fp32"  # "bf16x3": stride-1 Conv3d layers on the split-bf16 MFMA kernel (csrc/conv_split.hip)
-        self._hip, self._hip_version = None, None
+        self._hip = ops.ParamCache()
 
     def forward(self, x: torch.Tensor, features: List[torch.Tensor]) -> torch.Tensor:
         if self.hip:  # no silent fallback: `.hip = False` is the explicit opt-in to the PyTorch ops below
@@ -103,10 +102,9 @@ class CostVolumeFilterNetwork(nn.Module):
 
     # ---- HIP path (csrc/conv3d.hip): the whole hourglass on depth-major volumes, every Conv3d one MFMA-conv launch per sample
     def _engines(self, device):
-        tensors = list(self.state_dict().values())
-        v = (tuple((t.data_ptr(), t._version) for t in tensors), str(device), self.arithmetic)
-        if v == self._hip_version:
-            return self._hip
+        return self._hip.get((self,), device, lambda: self._build_engines(device), extra=(self.arithmetic,))
+
+    def _build_engines(self, device):
         def c3(m, stride=1, split=0):
             bn = (m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var)
             return ops.Conv3dNorm(m.conv.weight, None, stride, bn, m.bn.eps, m.relu.negative_slope, split, device, self.arithmetic)
@@ -123,7 +121,6 @@ class CostVolumeFilterNetwork(nn.Module):
         e["proj_3"] = c3(self.proj_3, split=self.conv3_up.conv.out_channels)
         e["proj_2"] = c3(self.proj_2, split=self.conv2_up.conv.out_channels)
         e["g3u"], e["g2u"] = gate(self.conv3_up_feat_guided), gate(self.conv2_up_feat_guided)
-        self._hip, self._hip_version = e, v
         return e
 
     def forward_rows(self, rows: torch.Tensor, features: List[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -179,17 +176,15 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
             self.cv_regularizer.arithmetic = arithmetic  # 544x960 sample with fp16x2: profiles/r03_igev_regulariser_layers_*.txt)
         self.corr_fn = GeometryAwareCostVolume
         self.cv_squeezer = nn.Conv3d(cv_groups, 1, 3, 1, 1)
+        self._sq_cache = ops.ParamCache()
         self.tracing, self.include_preprocessing = tracing, include_preprocessing
         self.weights, self.strict_load = weights, strict_load
         self.fused_loop = fused_loop
 
     def _squeezer_host(self):
         """Host copy of the cv_squeezer parameters (kernel arguments of nnd_igev_init_disparity), refreshed when they change."""
-        w, b = self.cv_squeezer.weight, self.cv_squeezer.bias
-        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
-        if getattr(self, "_sq_cache", (None,))[0] != key:
-            self._sq_cache = (key, w.detach().float().cpu().contiguous(), None if b is None else b.detach().float().cpu().contiguous())
-        return self._sq_cache[1], self._sq_cache[2]
+        sq = self.cv_squeezer
+        return self._sq_cache.get((sq,), "cpu", lambda: (ops._host(sq.weight), ops._host(sq.bias)))
 
     def _init_fnet(self):
         raise NotImplementedError("Must be implemented in child class")
@@ -261,35 +256,6 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
         return outs
 
 
-class MobileNetV3EncoderSide:
-    """The encoder side of IGEVStereoMBNet — MobileNetV3 `fnet`, `fnet_proj`, `cnet_proj` and the guide split — on HIP: ONE C-ABI
-    call per forward (csrc/mbv3.hip: nnd_mbv3_forward, exact fp32 whatever the model's `arithmetic`), packed by
-    ops.MobileNetV3Engine from the modules' parameters (BatchNorms folded on the host in float64) and repacked when a parameter's
-    data_ptr / _version changes."""
-
-    def __init__(self):
-        self.engine, self.version = None, None
-
-    def run(self, owner: nn.Module, fnet, fnet_proj, cnet_proj, frame1: torch.Tensor, frame2: torch.Tensor):
-        """-> (fmap1, fmap2, cnet1, [guide 1/8, guide 1/16, guide 1/32]) exactly as IGEVStereoMBNet.forward_fnet returns them."""
-        if owner.training or fnet.training:
-            raise NndError(f"{type(owner).__name__}: the HIP encoder side is inference-only (BatchNorm is folded with its running "
-                           "statistics): call model.eval() first")
-        # the module walk, the descriptor and the fold run only when a parameter / buffer changed (data_ptr, _version) or one was
-        # added / removed; otherwise this tuple is the whole per-call check
-        v = (tuple((t.data_ptr(), t._version) for m in (fnet, fnet_proj, cnet_proj)
-                   for t in itertools.chain(m.parameters(), m.buffers())), tuple(id(m) for m in fnet.modules()), str(frame1.device))
-        if v != self.version:
-            why = ops.MobileNetV3Engine.blocker(owner, fnet, fnet_proj, cnet_proj)
-            if why:
-                raise NndError(f"{type(owner).__name__}: the HIP encoder side cannot run this model ({why}); pass hip_encoder=False "
-                               "to run the encoder side's PyTorch-ROCm modules explicitly")
-            self.engine = ops.MobileNetV3Engine.from_modules(fnet, fnet_proj, cnet_proj, frame1.device)
-            self.version = v
-        # the two frame tensors are read where they lie: no torch.cat copy (model.py:191)
-        return self.engine.forward(frame1.float(), frame2.float())
-
-
 class IGEVStereoMBNet(IGEVStereoBase):
     """Drop-in for the reference's `IGEVStereoMBNet` (nndepth/models/igev_stereo/model.py:163-203): its constructor kwargs, its
     state_dict keys in its order (fnet.backbone.* as timm 1.0.16's tf_mobilenetv3_large_100(features_only=True) names them,
@@ -299,7 +265,7 @@ class IGEVStereoMBNet(IGEVStereoBase):
     (`pretrained=True` in its MobilenetV3LargeEncoder) is not reproduced, so trained parameters come only through `weights=` (a
     reference checkpoint loads with strict=True) or load_state_dict.
 
-    hip_encoder=True (default): the whole encoder side is ONE HIP call (MobileNetV3EncoderSide); a module the HIP encoder side does
+    hip_encoder=True (default): the whole encoder side is ONE HIP call (raft_stereo.FoldedEncoderSide); a module the HIP encoder side does
     not build (training mode, a replaced block) raises NndError naming it.  hip_encoder=False is the explicit opt-in to the
     containers' PyTorch-ROCm forward.  `arithmetic`, `outputs`, `fused_loop`: as on IGEVStereoBase (the encoder side stays exact
     fp32)."""
@@ -309,7 +275,7 @@ class IGEVStereoMBNet(IGEVStereoBase):
         self.fnet_proj = nn.Sequential(nn.Conv2d(24, self.hidden_dim * 2, 3, 1, 1), nn.ReLU(False))
         self.cnet_proj = nn.Sequential(nn.Conv2d(24, self.context_dim * 2, 3, 1, 1), nn.ReLU(False))
         self.hip_encoder = hip_encoder
-        self._encoder_side = MobileNetV3EncoderSide()
+        self._encoder_side = FoldedEncoderSide(ops.MobileNetV3Engine, track_modules=True)
         if self.weights is not None:
             load_weights(self, self.weights, self.strict_load)
 
@@ -322,7 +288,7 @@ class IGEVStereoMBNet(IGEVStereoBase):
 
     def forward_fnet(self, frame1: torch.Tensor, frame2: torch.Tensor):
         if self.hip_encoder:
-            return self._encoder_side.run(self, self.fnet, self.fnet_proj, self.cnet_proj, frame1, frame2)
+            return self._encoder_side.run(self, (self.fnet, self.fnet_proj, self.cnet_proj), frame1, frame2)
         B = frame1.shape[0]  # explicit opt-in (hip_encoder=False): the containers' PyTorch-ROCm forward
         feats = self.fnet(torch.cat([frame1, frame2], dim=0))
         fmaps = feats[0]

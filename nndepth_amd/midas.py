@@ -16,7 +16,6 @@ BatchNorms on the host in float64 and repacks only when a parameter changes).  I
 H and W must be multiples of 32.  hip=False is the explicit PyTorch path of these modules (any device / dtype; the float64 oracle of
 the tests); there is no silent fallback from one to the other.
 """
-import itertools
 from typing import List, Optional
 
 import torch
@@ -90,7 +89,7 @@ class MobileNetV3DepthModel(nn.Module):
             nn.Conv2d(c, 1, kernel_size=1, padding=0, stride=1),
             nn.ReLU(),
         )
-        self._engine, self._version = None, None
+        self._engine = ops.ParamCache()
         if weights is not None:
             if not (weights.endswith(".pth") or weights.endswith(".safetensors")):
                 raise ValueError(f"Unsupported weight format: {weights}")
@@ -108,17 +107,12 @@ class MobileNetV3DepthModel(nn.Module):
 
     # ------------------------------------------------------------------ HIP path
     def engine(self, device) -> "ops.MidasEngine":
-        """The packed engine for the current parameters: refolded and repacked only when a parameter / buffer changed (data_ptr,
-        _version) or a module was replaced."""
+        """The packed engine for the current parameters: refolded and repacked only when a parameter / buffer changed or a module
+        was replaced (ops.ParamCache)."""
         if self.training:
             raise NndError(f"{type(self).__name__} is inference-only on the HIP path: call model.eval() first (BatchNorm is folded with "
                            "its running statistics; pass hip=False for the PyTorch modules)")
-        v = (tuple((t.data_ptr(), t._version) for t in itertools.chain(self.parameters(), self.buffers())),
-             tuple(id(m) for m in self.modules()), str(device))
-        if v != self._version:
-            self._engine = ops.MidasEngine.from_model(self, device)
-            self._version = v
-        return self._engine
+        return self._engine.get((self,), device, lambda: ops.MidasEngine.from_model(self, device), track_modules=True)
 
     def forward_maps(self, x: torch.Tensor):
         """HIP forward that also returns the intermediate maps (views of the engine's workspace, valid until the next call)."""

@@ -6,9 +6,10 @@ raise otherwise — there is no CPU or eager fallback.
 """
 import contextlib
 import ctypes as C
+import itertools
 import os
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -37,6 +38,31 @@ def _stream(device: torch.device) -> C.c_void_p:
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _host(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.detach().to("cpu", torch.float32).contiguous()
+
+
+class ParamCache:
+    """"Repack when the parameters changed", once: `get` returns what `build()` made for the current key and calls it again
+    only when the key changed.  The key: (data_ptr, _version) of every parameter and buffer of `modules` (an in-place edit bumps
+    _version, a replaced tensor has another data_ptr), the id of every submodule with `track_modules` (a replaced block), the
+    device the packed object is for, and `extra`.  A `build()` that raises leaves the cache as it was."""
+
+    def __init__(self):
+        self.key, self.value = None, None
+
+    def get(self, modules: Sequence[torch.nn.Module], device, build: Callable[[], object], extra: tuple = (),
+            track_modules: bool = False):
+        mods = [s for m in modules for s in m.modules()]  # one walk: nn.Module.parameters() + buffers() would make two slower ones
+        key = (tuple((t.data_ptr(), t._version) for s in mods for t in itertools.chain(s._parameters.values(), s._buffers.values())
+                     if t is not None),
+               tuple(map(id, mods)) if track_modules else (), str(device), extra)
+        if key != self.key:
+            self.value = build()
+            self.key = key
+        return self.value
 
 
 # ------------------------------------------------------------- fp16x2 activation-range calibration
@@ -75,6 +101,15 @@ def _calib_flags(engine) -> int:
     if getattr(_calib_tls, "require", False) and not engine.calibrated:
         raise NeedsCalibration(f"{type(engine).__name__}: fp16x2 activation scales not calibrated")
     return 0
+
+
+def _call_desc(engine, extra_flags: int = 0):
+    """The descriptor of ONE C-ABI call: a copy of `engine.desc` that carries this call's flags (NND_FLAG_CALIBRATE inside
+    `with calibration()` for an fp16x2 engine, plus `extra_flags`).  The engine's own descriptor is never written after
+    __init__, so calls on one engine from several threads do not race on it and no flag reaches a later call."""
+    d = type(engine.desc).from_buffer_copy(engine.desc)
+    d.flags = (_calib_flags(engine) if engine.arithmetic == "fp16x2" else 0) | extra_flags
+    return d
 
 
 @contextlib.contextmanager
@@ -168,8 +203,7 @@ class Conv2d:
         n = int(lib.nnd_conv2d_packed_floats_ex(self.Cout, self.Cin, self.KH, self.KW, self.arith))
         if n <= 0:
             check(n, "conv2d_packed_floats")
-        w = weight.detach().to("cpu", torch.float32).contiguous()
-        b = bias.detach().to("cpu", torch.float32).contiguous()
+        w, b = _host(weight), _host(bias)
         blob = torch.empty(n, dtype=torch.float32)
         check(lib.nnd_conv2d_pack_ex(_p(w), _p(b), self.Cout, self.Cin, self.KH, self.KW, self.arith, _p(blob)), "conv2d_pack")
         self.packed_host = blob
@@ -311,6 +345,23 @@ def update_block_keys(gru: str = "sep_conv") -> List[str]:
     return [f"{n}.{s}" for n in names for s in ("weight", "bias")]
 
 
+class _RefineCall(NamedTuple):
+    """UpdateBlockEngine._refine_call: what a refine loop's C-ABI call line needs."""
+    desc: UpdateBlockDesc
+    d: torch.device
+    net: torch.Tensor
+    inp: torch.Tensor
+    init: Optional[torch.Tensor]
+    up: torch.Tensor
+    stride: int
+    low: torch.Tensor
+    net_out: torch.Tensor
+    ws: torch.Tensor
+    B: int
+    H: int
+    W: int
+
+
 class UpdateBlockEngine:
     """Packed parameters + workspace for one BasicUpdateBlock configuration."""
 
@@ -355,11 +406,6 @@ class UpdateBlockEngine:
         return self
 
     # ---- fp16x2 activation range (include/nndepth_amd.h "fp16x2 activation range")
-    def _desc(self):
-        """The descriptor for one C-ABI call: carries NND_FLAG_CALIBRATE inside `with ops.calibration()`."""
-        self.desc.flags = _calib_flags(self) if self.arithmetic == "fp16x2" else 0
-        return C.byref(self.desc)
-
     @staticmethod
     def _keep_all(keep_all: Optional[bool], last_only: bool) -> bool:
         """keep_all=None (default): every iteration's map unless last_only."""
@@ -367,21 +413,12 @@ class UpdateBlockEngine:
             raise NndError("refine: last_only=True computes one upsampled map; it cannot be combined with keep_all=True")
         return (not last_only) if keep_all is None else bool(keep_all)
 
-    def _refine_desc(self, last_only: bool) -> UpdateBlockDesc:
-        """The descriptor of one refine call: a copy of `self.desc` with this call's flags, so NND_FLAG_LAST_UPSAMPLE_ONLY never
-        reaches a later call (update_block_forward refuses it)."""
-        d = UpdateBlockDesc.from_buffer_copy(self.desc)
-        d.flags = (_calib_flags(self) if self.arithmetic == "fp16x2" else 0) | (NND_FLAG_LAST_UPSAMPLE_ONLY if last_only else 0)
-        return d
-
     def _calibration_finish(self, status: Optional[torch.Tensor]) -> None:
-        self.desc.flags = 0
         check(lib.nnd_update_block_calibration_finish(C.byref(self.desc), _p(self.packed), _p(status), _stream(self.packed.device)),
               "update_block_calibration_finish")
 
     def activation_ranges(self) -> Dict[str, float]:
         """{convolution: largest |activation| its fp16x2 operands represent} (65504 / the layer's activation scale)."""
-        self.desc.flags = 0
         n = int(lib.nnd_update_block_scale_slots(C.byref(self.desc), None, 0))
         offs = (C.c_int64 * n)()
         check(min(0, int(lib.nnd_update_block_scale_slots(C.byref(self.desc), offs, n))), "update_block_scale_slots")
@@ -431,86 +468,69 @@ class UpdateBlockEngine:
         delta = torch.empty_like(flow)
         ws = self.workspace(B, H, W, d)
         with torch.cuda.device(d):
-            check(lib.nnd_update_block_forward(self._desc(), _p(self.packed), _p(net), _p(inp), _p(corr), _p(flow),
+            check(lib.nnd_update_block_forward(C.byref(_call_desc(self)), _p(self.packed), _p(net), _p(inp), _p(corr), _p(flow),
                                                _p(net_out), _p(mask), _p(delta), _p(ws), B, H, W, _stream(d)),
                   "update_block_forward")
         return net_out, mask, delta
+
+    def _refine_call(self, what: str, tensors, net, inp, init, channels: int, rate: int, iters: int,
+                     keep_all: Optional[bool], last_only: bool) -> "_RefineCall":
+        """What the four refine loops share in front of their C-ABI call: the argument checks that precede any launch, this call's
+        descriptor, and the outputs (`channels` = 1 disparity, 2 CREStereo flow).  `tensors`: the loop's own device inputs."""
+        if self.packed is None:
+            raise NndError("UpdateBlockEngine: parameters not loaded")
+        keep_all = self._keep_all(keep_all, last_only)
+        desc = _call_desc(self, NND_FLAG_LAST_UPSAMPLE_ONLY if last_only else 0)  # (update_block_forward refuses that flag)
+        d = _dev(*tensors, net, inp, self.packed)
+        net, inp = net.contiguous(), inp.contiguous()
+        B, _, H, W = net.shape
+        self._check_state(what, net, inp, init, channels)
+        if init is not None:
+            _dev(init)
+            init = init.contiguous()
+        up = torch.empty((iters if keep_all else 1, B, channels, rate * H, rate * W), dtype=torch.float32, device=d)
+        low = torch.empty((B, channels, H, W), dtype=torch.float32, device=d)
+        return _RefineCall(desc, d, net, inp, init, up, up[0].numel() if keep_all else 0, low, torch.empty_like(net),
+                           self.workspace(B, H, W, d), B, H, W)
 
     def refine(self, pyr, num_levels: int, radius: int, net, inp, rate: int, iters: int,
                disp_init=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """Fused loop -> (up (iters or 1, B,1,rate*H,rate*W), low (B,1,H,W), net (B,hid,H,W)).
         keep_all (default unless last_only): every iteration's upsampled map; False: the last one, all of them computed.
         last_only: the last iteration's map alone is computed (NND_FLAG_LAST_UPSAMPLE_ONLY), the same bits as keep_all's up[-1]."""
-        if self.packed is None:
-            raise NndError("UpdateBlockEngine: parameters not loaded")
-        keep_all = self._keep_all(keep_all, last_only)
-        desc = self._refine_desc(last_only)
-        d = _dev(pyr, net, inp, self.packed)
-        net, inp = net.contiguous(), inp.contiguous()
-        B, _, H, W = net.shape
-        self._check_state("refine", net, inp, disp_init, 1)
+        c = self._refine_call("refine", (pyr,), net, inp, disp_init, 1, rate, iters, keep_all, last_only)
+        B, H, W = c.B, c.H, c.W
         if pyr.numel() != pyramid_layout(B, H, W, num_levels)[2]:
             raise NndError(f"refine: pyramid holds {pyr.numel()} floats, a {B}x{H}x{W} pyramid of {num_levels} levels has "
                            f"{pyramid_layout(B, H, W, num_levels)[2]}")
-        if disp_init is not None:
-            _dev(disp_init)
-        n_up = iters if keep_all else 1
-        up = torch.empty((n_up, B, 1, rate * H, rate * W), dtype=torch.float32, device=d)
-        low = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
-        net_out = torch.empty_like(net)
-        ws = self.workspace(B, H, W, d)
-        stride = up[0].numel() if keep_all else 0
-        if disp_init is not None:
-            disp_init = disp_init.contiguous()
-        with torch.cuda.device(d):
-            check(lib.nnd_raft_stereo_refine(C.byref(desc), _p(self.packed), _p(pyr), num_levels, radius,
-                                             _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low), _p(net_out),
-                                             _p(ws), B, H, W, rate, iters, _stream(d)), "raft_stereo_refine")
-        return up, low, net_out
+        with torch.cuda.device(c.d):
+            check(lib.nnd_raft_stereo_refine(C.byref(c.desc), _p(self.packed), _p(pyr), num_levels, radius,
+                                             _p(c.net), _p(c.inp), _p(c.init), _p(c.up), c.stride, _p(c.low), _p(c.net_out),
+                                             _p(c.ws), B, H, W, rate, iters, _stream(c.d)), "raft_stereo_refine")
+        return c.up, c.low, c.net_out
 
     def refine_group(self, group_pyr, num_groups: int, num_levels: int, radius: int, net, inp, rate: int, iters: int,
                      disp_init=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """One cascade stage of Coarse2FineGroupRepViTRAFTStereo (raft_stereo/model.py:297-311): refine() with GroupCorrBlock1D's
         lookup over the pyramid of raft_group_corr_build -> (up, low, net)."""
-        if self.packed is None:
-            raise NndError("UpdateBlockEngine: parameters not loaded")
-        keep_all = self._keep_all(keep_all, last_only)
-        desc = self._refine_desc(last_only)
-        d = _dev(group_pyr, net, inp, self.packed)
-        net, inp = net.contiguous(), inp.contiguous()
-        B, _, H, W = net.shape
-        self._check_state("refine_group", net, inp, disp_init, 1)
+        c = self._refine_call("refine_group", (group_pyr,), net, inp, disp_init, 1, rate, iters, keep_all, last_only)
+        B, H, W = c.B, c.H, c.W
         need = pyramid_layout(B * num_groups, H, W, num_levels)[2]
         if group_pyr.numel() != need:
             raise NndError(f"refine_group: pyramid holds {group_pyr.numel()} floats, expected {need} for B*G={B * num_groups}, "
                            f"{H}x{W}, {num_levels} levels")
-        n_up = iters if keep_all else 1
-        up = torch.empty((n_up, B, 1, rate * H, rate * W), dtype=torch.float32, device=d)
-        low = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
-        net_out = torch.empty_like(net)
-        ws = self.workspace(B, H, W, d)
-        stride = up[0].numel() if keep_all else 0
-        if disp_init is not None:
-            _dev(disp_init)
-            disp_init = disp_init.contiguous()
-        with torch.cuda.device(d):
-            check(lib.nnd_raft_stereo_group_refine(C.byref(desc), _p(self.packed), _p(group_pyr), num_groups, num_levels, radius,
-                                                   _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low), _p(net_out),
-                                                   _p(ws), B, H, W, rate, iters, _stream(d)), "raft_stereo_group_refine")
-        return up, low, net_out
+        with torch.cuda.device(c.d):
+            check(lib.nnd_raft_stereo_group_refine(C.byref(c.desc), _p(self.packed), _p(group_pyr), num_groups, num_levels, radius,
+                                                   _p(c.net), _p(c.inp), _p(c.init), _p(c.up), c.stride, _p(c.low), _p(c.net_out),
+                                                   _p(c.ws), B, H, W, rate, iters, _stream(c.d)), "raft_stereo_group_refine")
+        return c.up, c.low, c.net_out
 
     def refine_igev(self, feat_pyr, geo_pyr, num_groups: int, num_levels: int, radius: int, net, inp, rate: int,
                     iters: int, disp_init=None, keep_all: Optional[bool] = None, interleaved=None, last_only: bool = False):
         """IGEV loop (absolute coordinates, combined lookup) -> (up, low, net) like refine().
         interleaved: optional igev_interleave_pyramids(feat_pyr, geo_pyr, ...) — the loop then gathers from it."""
-        if self.packed is None:
-            raise NndError("UpdateBlockEngine: parameters not loaded")
-        keep_all = self._keep_all(keep_all, last_only)
-        desc = self._refine_desc(last_only)
-        d = _dev(feat_pyr, geo_pyr, net, inp, self.packed)
-        net, inp = net.contiguous(), inp.contiguous()
-        B, _, H, W = net.shape
-        self._check_state("refine_igev", net, inp, disp_init, 1)
+        c = self._refine_call("refine_igev", (feat_pyr, geo_pyr), net, inp, disp_init, 1, rate, iters, keep_all, last_only)
+        B, H, W = c.B, c.H, c.W
         need = pyramid_layout(B * num_groups, H, W, num_levels)[2]
         if feat_pyr.numel() != need or geo_pyr.numel() != need:
             raise NndError(f"refine_igev: pyramids hold {feat_pyr.numel()} / {geo_pyr.numel()} floats, expected {need} "
@@ -520,58 +540,35 @@ class UpdateBlockEngine:
             need_il = int(lib.nnd_igev_interleaved_floats(B, num_groups, H, W, num_levels))
             if interleaved.numel() != need_il:
                 raise NndError(f"refine_igev: interleaved copy holds {interleaved.numel()} floats, expected {need_il}")
-        if disp_init is not None:
-            _dev(disp_init)
-        n_up = iters if keep_all else 1
-        up = torch.empty((n_up, B, 1, rate * H, rate * W), dtype=torch.float32, device=d)
-        low = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
-        net_out = torch.empty_like(net)
-        ws = self.workspace(B, H, W, d)
-        stride = up[0].numel() if keep_all else 0
-        if disp_init is not None:
-            disp_init = disp_init.contiguous()
-        with torch.cuda.device(d):
-            check(lib.nnd_igev_stereo_refine(C.byref(desc), _p(self.packed), _p(feat_pyr), _p(geo_pyr), _p(interleaved), num_groups,
-                                             num_levels, radius, _p(net), _p(inp), _p(disp_init), _p(up), stride, _p(low),
-                                             _p(net_out), _p(ws), B, H, W, rate, iters, _stream(d)), "igev_stereo_refine")
-        return up, low, net_out
+        with torch.cuda.device(c.d):
+            check(lib.nnd_igev_stereo_refine(C.byref(c.desc), _p(self.packed), _p(feat_pyr), _p(geo_pyr), _p(interleaved), num_groups,
+                                             num_levels, radius, _p(c.net), _p(c.inp), _p(c.init), _p(c.up), c.stride, _p(c.low),
+                                             _p(c.net_out), _p(c.ws), B, H, W, rate, iters, _stream(c.d)), "igev_stereo_refine")
+        return c.up, c.low, c.net_out
 
     def refine_cre(self, fmap1, fmap2, net, inp, rate: int, iters: int, flow_init=None, extra_offset=None,
                    scratch=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """One CREStereo cascade stage (AGCL -> update block -> flow += delta -> 2-channel upsample, `iters` times)
         -> (up (iters or 1, B,2,rate*H,rate*W), flow (B,2,H,W), net).  extra_offset=None: iter mode."""
-        if self.packed is None:
-            raise NndError("UpdateBlockEngine: parameters not loaded")
-        keep_all = self._keep_all(keep_all, last_only)
-        desc = self._refine_desc(last_only)
-        d = _dev(fmap1, fmap2, net, inp, self.packed)
-        fmap1, fmap2, net, inp = (t.contiguous() for t in (fmap1, fmap2, net, inp))
-        B, Cf, H, W = fmap1.shape
-        if fmap2.shape != fmap1.shape or tuple(net.shape[2:]) != (H, W) or net.shape[0] != B:
+        c = self._refine_call("refine_cre", (fmap1, fmap2), net, inp, flow_init, 2, rate, iters, keep_all, last_only)
+        B, H, W = c.B, c.H, c.W
+        fmap1, fmap2 = fmap1.contiguous(), fmap2.contiguous()
+        Cf = fmap1.shape[1]
+        if fmap2.shape != fmap1.shape or tuple(fmap1.shape) != (B, Cf, H, W):
             raise NndError(f"refine_cre: shapes fmap {tuple(fmap1.shape)} / {tuple(fmap2.shape)}, net {tuple(net.shape)}")
-        self._check_state("refine_cre", net, inp, flow_init, 2)
         if extra_offset is not None and extra_offset.numel() != B * 18 * H * W:
             raise NndError(f"refine_cre: extra_offset shape {tuple(extra_offset.shape)} != {(B, 18, H, W)}")
-        n_up = iters if keep_all else 1
-        up = torch.empty((n_up, B, 2, rate * H, rate * W), dtype=torch.float32, device=d)
-        low = torch.empty((B, 2, H, W), dtype=torch.float32, device=d)
-        net_out = torch.empty_like(net)
-        ws = self.workspace(B, H, W, d)
-        stride = up[0].numel() if keep_all else 0
-        if flow_init is not None:
-            flow_init = flow_init.contiguous()
-            _dev(flow_init)
         need = fmap2.numel() if extra_offset is None else 2 * fmap2.numel()  # warped map / the two channels-last copies
         if extra_offset is not None:
             extra_offset = extra_offset.contiguous()
             _dev(extra_offset)
         if scratch is None or scratch.numel() < need:
-            scratch = torch.empty(need, dtype=torch.float32, device=d)
-        with torch.cuda.device(d):
-            check(lib.nnd_cre_stereo_refine(C.byref(desc), _p(self.packed), _p(fmap1), _p(fmap2), Cf, _p(extra_offset),
-                                            _p(scratch), scratch.numel(), _p(net), _p(inp), _p(flow_init), _p(up), stride, _p(low),
-                                            _p(net_out), _p(ws), B, H, W, rate, iters, _stream(d)), "cre_stereo_refine")
-        return up, low, net_out
+            scratch = torch.empty(need, dtype=torch.float32, device=c.d)
+        with torch.cuda.device(c.d):
+            check(lib.nnd_cre_stereo_refine(C.byref(c.desc), _p(self.packed), _p(fmap1), _p(fmap2), Cf, _p(extra_offset),
+                                            _p(scratch), scratch.numel(), _p(c.net), _p(c.inp), _p(c.init), _p(c.up), c.stride,
+                                            _p(c.low), _p(c.net_out), _p(c.ws), B, H, W, rate, iters, _stream(c.d)), "cre_stereo_refine")
+        return c.up, c.low, c.net_out
 
     # ---- profiling (bench.py roofline)
     def conv_names(self) -> List[str]:
@@ -793,8 +790,16 @@ def agcl_corr_offset(fmap1: torch.Tensor, fmap2: torch.Tensor, flow: torch.Tenso
 
 
 # ------------------------------------------------------------------ conv + folded norm, encoder (include/nndepth_amd.h)
-def _host(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    return None if t is None else t.detach().to("cpu", torch.float32).contiguous()
+def _pack_conv_norm(abi: str, desc, weight, bias, bn, eps: float, device) -> torch.Tensor:
+    """One conv [+ eval-mode BatchNorm folded by the library] packed through nnd_<abi>_packed_floats / nnd_<abi>_pack -> the blob on
+    `device`.  `bn` = (weight, bias, running_mean, running_var) or None."""
+    n = int(getattr(lib, f"nnd_{abi}_packed_floats")(C.byref(desc)))
+    if n <= 0:
+        check(n, f"{abi}_packed_floats")
+    host = [_host(t) for t in (weight, bias) + (tuple(bn) if bn is not None else (None,) * 4)]  # kept alive across the call
+    blob = torch.empty(n, dtype=torch.float32)
+    check(getattr(lib, f"nnd_{abi}_pack")(C.byref(desc), *[_p(t) for t in host], float(eps), _p(blob)), f"{abi}_pack")
+    return blob.to(device)
 
 
 class ConvNorm:
@@ -805,14 +810,7 @@ class ConvNorm:
                  device="cuda"):
         Cout, Cin, KH, KW = (int(v) for v in weight.shape)
         self.desc = ConvDesc(Cout, Cin, KH, KW, int(stride))
-        n = int(lib.nnd_conv_packed_floats(C.byref(self.desc)))
-        if n <= 0:
-            check(n, "conv_packed_floats")
-        w, b = _host(weight), _host(bias)
-        g, be, m, v = (_host(t) for t in bn) if bn is not None else (None, None, None, None)
-        blob = torch.empty(n, dtype=torch.float32)
-        check(lib.nnd_conv_pack(C.byref(self.desc), _p(w), _p(b), _p(g), _p(be), _p(m), _p(v), float(eps), _p(blob)), "conv_pack")
-        self.packed = blob.to(device)
+        self.packed = _pack_conv_norm("conv", self.desc, weight, bias, bn, eps, device)
 
     def __call__(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False,
                  relu_after_residual: bool = False) -> torch.Tensor:
@@ -890,7 +888,6 @@ class EncoderEngine:
         return self
 
     def _calibration_finish(self, status: Optional[torch.Tensor]) -> None:
-        self.desc.flags = 0
         check(lib.nnd_encoder_calibration_finish(C.byref(self.desc), _p(self.packed), _p(status), _stream(self.packed.device)),
               "encoder_calibration_finish")
 
@@ -919,9 +916,8 @@ class EncoderEngine:
         need = int(lib.nnd_encoder_workspace_floats(C.byref(self.desc), N, H, W))
         if self._ws is None or self._ws.numel() < need or self._ws.device != d:
             self._ws = torch.empty(need, dtype=torch.float32, device=d)
-        self.desc.flags = _calib_flags(self) if self.arithmetic == "fp16x2" else 0
         with torch.cuda.device(d):
-            check(lib.nnd_encoder_forward2(C.byref(self.desc), _p(self.packed), _p(frames), _p(frames_b), nsplit, _p(fmap), _p(cnet), n_cnet,
+            check(lib.nnd_encoder_forward2(C.byref(_call_desc(self)), _p(self.packed), _p(frames), _p(frames_b), nsplit, _p(fmap), _p(cnet), n_cnet,
                                            _p(self._ws), N, H, W, _stream(d)), "encoder_forward")
         return fmap, cnet
 
@@ -1632,8 +1628,7 @@ def igev_init_disparity(geo_level0: torch.Tensor, weight: torch.Tensor, bias: Op
     d = _dev(geo_level0)
     assert geo_level0.numel() == B * G * H * W * D and tuple(weight.shape) == (1, G, 3, 3, 3)
     # 27*G floats passed by value to the kernel: hand in host tensors (a device tensor costs a synchronising copy here)
-    wh = weight.detach().to("cpu", torch.float32).contiguous()
-    bh = None if bias is None else bias.detach().to("cpu", torch.float32).contiguous()
+    wh, bh = _host(weight), _host(bias)
     out = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
     with torch.cuda.device(d):
         check(lib.nnd_igev_init_disparity(_p(geo_level0.contiguous()), _p(wh), _p(bh), _p(out), B, G, H, W, D, _stream(d)),
@@ -1746,17 +1741,9 @@ class Conv3dNorm:
         self.desc = Conv3dDesc(Cout, cin0, Cin - cin0, int(stride), UpdateBlockEngine.ARITHMETIC[arithmetic], 0)
         self.calibrated = False
         self.leaky = float(leaky_slope)
-        n = int(lib.nnd_conv3d_packed_floats(C.byref(self.desc)))
-        if n <= 0:
-            check(n, "conv3d_packed_floats")
-        w, b = _host(weight), _host(bias)
-        g, be, m, v = (_host(t) for t in bn) if bn is not None else (None, None, None, None)
-        blob = torch.empty(n, dtype=torch.float32)
-        check(lib.nnd_conv3d_pack(C.byref(self.desc), _p(w), _p(b), _p(g), _p(be), _p(m), _p(v), float(eps), _p(blob)), "conv3d_pack")
-        self.packed = blob.to(device)
+        self.packed = _pack_conv_norm("conv3d", self.desc, weight, bias, bn, eps, device)
 
     def _calibration_finish(self, status: Optional[torch.Tensor]) -> None:
-        self.desc.flags = 0
         check(lib.nnd_conv3d_calibration_finish(C.byref(self.desc), _p(self.packed), _p(status), _stream(self.packed.device)),
               "conv3d_calibration_finish")
 
@@ -1774,9 +1761,8 @@ class Conv3dNorm:
         st, D = self.desc.stride, Dp - 2
         Do, Ho, Wo = (D + st - 1) // st, (H + st - 1) // st, (W + st - 1) // st
         y = torch.empty((N, Do + 2, self.desc.Cout, Ho, Wo), dtype=torch.float32, device=d)
-        self.desc.flags = _calib_flags(self) if self.arithmetic == "fp16x2" else 0
         with torch.cuda.device(d):
-            check(lib.nnd_conv3d_forward(C.byref(self.desc), _p(self.packed), _p(x0), _p(x1), _p(y), N, D, H, W, self.leaky,
+            check(lib.nnd_conv3d_forward(C.byref(_call_desc(self)), _p(self.packed), _p(x0), _p(x1), _p(y), N, D, H, W, self.leaky,
                                          _stream(d)), "conv3d_forward")
         return y
 

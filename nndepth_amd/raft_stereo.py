@@ -20,7 +20,6 @@ The classes are inference-only (eval-mode BatchNorm is folded into the convoluti
 `patch(model)` installs the same kernels behind the three duck-typed seams of an *unmodified*
 reference model instance: `corr_fn`, `update_block`, `convex_upsample`.
 """
-import itertools
 from typing import Dict, List, Optional
 
 import torch
@@ -69,6 +68,17 @@ def last_only(model: nn.Module) -> bool:
     return check_outputs(getattr(model, "outputs", "all")) == "last"
 
 
+def calibration_passes(run, max_passes: int, error: str) -> None:
+    """`run()` inside `ops.calibration()` until no layer saw inf / NaN at the scale it had (status bit 0: that layer's scale was
+    lowered by 2^12 since, so go again); NndError(error) if one still does after `max_passes` passes."""
+    for _ in range(max_passes):
+        with ops.calibration() as c, torch.no_grad():
+            run()
+        if not (c.status & 1):
+            return
+    raise NndError(error)
+
+
 class AutoCalibrate:
     """fp16x2 activation range (include/nndepth_amd.h "fp16x2 activation range", csrc/calib.hip), shared by the model classes.
 
@@ -87,15 +97,12 @@ class AutoCalibrate:
         outputs = getattr(self, "outputs", "all")
         self.outputs = "all"  # the mask head records its range over every iteration, whatever the model returns
         try:
-            for _ in range(max_passes):
-                with ops.calibration() as c, torch.no_grad():
-                    self._forward(*args, **kwargs)
-                if not (c.status & 1):  # bit 0: a layer saw inf / NaN at the scale it had (lowered by 2^12 since): go again
-                    return self
+            calibration_passes(lambda: self._forward(*args, **kwargs), max_passes,
+                               f"{type(self).__name__}.calibrate: activations still overflow fp16 after {max_passes} passes "
+                               "(non-finite inputs or weights?)")
         finally:
             self.outputs = outputs
-        raise NndError(f"{type(self).__name__}.calibrate: activations still overflow fp16 after {max_passes} passes "
-                       "(non-finite inputs or weights?)")
+        return self
 
     def _forward_calibrated(self, *args, **kwargs):
         """`_forward`, calibrating first if an fp16x2 engine on its path still has the default activation scales."""
@@ -136,7 +143,7 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
         self.tracing, self.include_preprocessing = tracing, include_preprocessing
         self.fused_loop = fused_loop
         self.hip_encoder = hip_encoder
-        self._enc_engine, self._enc_version = None, None
+        self._enc_cache = ops.ParamCache()
         self.fnet = BasicEncoder(output_dim=fnet_dim)
         self.cnet_proj = nn.Sequential(nn.Conv2d(fnet_dim, context_dim + hidden_dim, 3, padding=1), nn.ReLU(False))
         self.update_block = BasicUpdateBlock(hidden_dim=hidden_dim, cor_planes=corr_levels * (2 * corr_radius + 1),
@@ -156,15 +163,10 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
 
     def _encoder_engine(self, device) -> "ops.EncoderEngine":
         """(Re)pack fnet + cnet_proj for the HIP encoder if their parameters / buffers changed."""
-        tensors = list(self.fnet.state_dict().values()) + list(self.cnet_proj.state_dict().values())
-        v = (tuple((t.data_ptr(), t._version) for t in tensors), str(device))
-        if v != self._enc_version:
-            if self._enc_engine is None:
-                self._enc_engine = ops.EncoderEngine(self.fnet_dim, self.fnet.norm_fn, self.context_dim + self.hidden_dim,
-                                                     self.arithmetic)
-            self._enc_engine.load(self.fnet.state_dict(), self.cnet_proj.state_dict(), eps=1e-5, device=device)
-            self._enc_version = v
-        return self._enc_engine
+        def build():
+            eng = ops.EncoderEngine(self.fnet_dim, self.fnet.norm_fn, self.context_dim + self.hidden_dim, self.arithmetic)
+            return eng.load(self.fnet.state_dict(), self.cnet_proj.state_dict(), eps=1e-5, device=device)
+        return self._enc_cache.get((self.fnet, self.cnet_proj), device, build)
 
     def forward_fnet(self, frame1, frame2):
         if self.hip_encoder:
@@ -320,33 +322,32 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
         return outs
 
 
-class RepViTEncoderSide:
-    """The encoder side of Coarse2FineGroupRepViTRAFTStereo — RepViT `fnet`, the three MobileOne `cnet_proj` blocks and the two
-    FeatureFusionBlocks — on HIP: ONE C-ABI call per forward (csrc/repvit.hip: nnd_repvit_forward, exact fp32 whatever the
-    cascade's `arithmetic`), packed by ops.RepViTEngine from the modules' train-time parameters (branches, BatchNorms and layer
-    scales folded on the host in float64) and repacked when a parameter's data_ptr / _version changes."""
+class FoldedEncoderSide:
+    """A whole encoder side on HIP, ONE C-ABI call per forward, exact fp32 whatever the model's `arithmetic`: `engine_cls` is
+    ops.RepViTEngine (Coarse2FineGroupRepViTRAFTStereo: RepViT `fnet`, the three MobileOne `cnet_proj` blocks, the two
+    FeatureFusionBlocks; csrc/repvit.hip) or ops.MobileNetV3Engine (IGEVStereoMBNet: MobileNetV3 `fnet`, `fnet_proj`, `cnet_proj`;
+    csrc/mbv3.hip).  The engine is packed from the modules' train-time parameters (branches, BatchNorms and layer scales folded on
+    the host in float64) and repacked when ops.ParamCache's key changes; `track_modules`: a replaced submodule is such a change."""
 
-    def __init__(self):
-        self.engine, self.version = None, None
+    def __init__(self, engine_cls, track_modules: bool = False):
+        self.engine_cls, self.track_modules, self.cache = engine_cls, track_modules, ops.ParamCache()
 
-    def run(self, owner: nn.Module, fnet, cnet_proj, fusion_blocks, frame1: torch.Tensor, frame2: torch.Tensor):
-        """-> (feats, cnets) exactly as Coarse2FineRAFTStereoBase.forward_features returns them."""
-        if owner.training or fnet.training:
+    def run(self, owner: nn.Module, modules, frame1: torch.Tensor, frame2: torch.Tensor):
+        """modules = the engine's module tuple, fnet first -> what the model's own encoder-side method returns
+        (Coarse2FineRAFTStereoBase.forward_features, IGEVStereoMBNet.forward_fnet)."""
+        if owner.training or modules[0].training:
             raise NndError(f"{type(owner).__name__}: the HIP encoder side is inference-only (BatchNorm is folded with its running "
                            "statistics): call model.eval() first")
-        # the module walk, the descriptor and the fold run only when a parameter / buffer changed (data_ptr, _version) or one was
-        # added / removed (a reparameterised module registers new ones); otherwise this tuple is the whole per-call check
-        v = (tuple((t.data_ptr(), t._version) for m in (fnet, cnet_proj, fusion_blocks)
-                   for t in itertools.chain(m.parameters(), m.buffers())), str(frame1.device))
-        if v != self.version:
-            why = ops.RepViTEngine.blocker(owner, fnet, cnet_proj, fusion_blocks)
+
+        def build():  # the module walk, the descriptor and the fold: only on a key change; otherwise the key is the whole check
+            why = self.engine_cls.blocker(owner, *modules)
             if why:
                 raise NndError(f"{type(owner).__name__}: the HIP encoder side cannot run this model ({why}); pass hip_encoder=False "
                                "to run the encoder side's PyTorch-ROCm modules explicitly")
-            self.engine = ops.RepViTEngine.from_modules(fnet, cnet_proj, fusion_blocks, frame1.device)
-            self.version = v
-        # the two frame tensors are read where they lie: no torch.cat copy (model.py:275)
-        return self.engine.forward(frame1.float(), frame2.float())
+            return self.engine_cls.from_modules(*modules, frame1.device)
+        engine = self.cache.get(modules, frame1.device, build, track_modules=self.track_modules)
+        # the two frame tensors are read where they lie: no torch.cat copy
+        return engine.forward(frame1.float(), frame2.float())
 
 
 class Coarse2FineGroupRepViTRAFTStereo(Coarse2FineRAFTStereoBase):
@@ -354,7 +355,7 @@ class Coarse2FineGroupRepViTRAFTStereo(Coarse2FineRAFTStereoBase):
     constructor kwargs (= `RepViTRAFTStereoModelConfig`, with corr_levels=1 as the reference asserts), its state_dict keys in its
     order (fnet, cnet_proj, update_block, fusion_blocks) and `forward(frame1, frame2) -> List[{"up_disp"}]`.
 
-    hip_encoder=True (default): the whole encoder side is ONE HIP call (RepViTEncoderSide), followed by the HIP cascade of
+    hip_encoder=True (default): the whole encoder side is ONE HIP call (FoldedEncoderSide), followed by the HIP cascade of
     Coarse2FineRAFTStereoBase.refine_stages.  A configuration the HIP encoder side does not build raises NndError naming it;
     hip_encoder=False is the explicit opt-in to the containers' PyTorch-ROCm forward (nndepth_amd.rep_vit)."""
 
@@ -374,7 +375,7 @@ class Coarse2FineGroupRepViTRAFTStereo(Coarse2FineRAFTStereoBase):
         # the reference registers fusion_blocks after update_block (model.py:216-228 run after RAFTStereo.__init__): same order here
         self._modules["fusion_blocks"] = self._modules.pop("fusion_blocks")
         self.hip_encoder = hip_encoder
-        self._encoder_side = RepViTEncoderSide()
+        self._encoder_side = FoldedEncoderSide(ops.RepViTEngine)
         self.weights, self.strict_load = weights, strict_load
         if weights is not None:
             load_weights(self, weights, strict_load)
@@ -396,7 +397,7 @@ class Coarse2FineGroupRepViTRAFTStereo(Coarse2FineRAFTStereoBase):
 
     def forward_features(self, frame1: torch.Tensor, frame2: torch.Tensor):
         if self.hip_encoder:
-            return self._encoder_side.run(self, self.fnet, self.cnet_proj, self.fusion_blocks, frame1, frame2)
+            return self._encoder_side.run(self, (self.fnet, self.cnet_proj, self.fusion_blocks), frame1, frame2)
         return super().forward_features(frame1, frame2)  # explicit opt-in (hip_encoder=False): PyTorch-ROCm modules
 
 
@@ -406,20 +407,20 @@ def patch_coarse2fine(model: nn.Module, arithmetic: str = "fp16x2", fused_loop: 
     `convex_upsample`, `corr_fn` = GroupCorrBlock1D, and `forward` = the reference's encoder side (its own fnet / fusion_blocks /
     cnet_proj modules) followed by Coarse2FineRAFTStereoBase.refine_stages.  `outputs`: as on Coarse2FineRAFTStereoBase.
     hip_encoder=True: the instance's own fnet / cnet_proj / fusion_blocks are packed and run as the ONE HIP call of the drop-in
-    class (RepViTEncoderSide) instead of their PyTorch modules."""
+    class (FoldedEncoderSide) instead of their PyTorch modules."""
     model.outputs = check_outputs(outputs)
     patch(model, arithmetic)
     model.corr_fn = GroupCorrBlock1D
     model.convex_upsample = lambda flow, mask, rate=(4, 4): convex_upsample(flow, mask, rate if isinstance(rate, int) else rate[0])
     model.arithmetic, model.fused_loop = arithmetic, fused_loop
     cls = Coarse2FineRAFTStereoBase
-    side = RepViTEncoderSide() if hip_encoder else None
+    side = FoldedEncoderSide(ops.RepViTEngine) if hip_encoder else None
 
     def forward(frame1, frame2, **kwargs):
         require_eval(model)
         with torch.no_grad():
             if side is not None:
-                feats, cnets = side.run(model, model.fnet, model.cnet_proj, model.fusion_blocks, frame1, frame2)
+                feats, cnets = side.run(model, (model.fnet, model.cnet_proj, model.fusion_blocks), frame1, frame2)
             else:
                 feats, cnets = cls.forward_features(model, frame1, frame2)
             return cls.refine_stages(model, feats, cnets, tuple(frame1.shape[-2:]))
@@ -454,9 +455,5 @@ def patch(model: nn.Module, arithmetic: str = "fp16x2") -> nn.Module:
 def calibrate_patched(model: nn.Module, frame1: torch.Tensor, frame2: torch.Tensor, max_passes: int = 4) -> nn.Module:
     """fp16x2 activation-range calibration of a `patch()`ed reference model on one pair (see AutoCalibrate): the reference's own
     forward runs inside `ops.calibration()`, so the seams record what they stage."""
-    for _ in range(max_passes):
-        with ops.calibration() as c, torch.no_grad():
-            model(frame1, frame2)
-        if not (c.status & 1):
-            return model
-    raise NndError("calibrate_patched: activations still overflow fp16")
+    calibration_passes(lambda: model(frame1, frame2), max_passes, "calibrate_patched: activations still overflow fp16")
+    return model

@@ -80,7 +80,7 @@ def test_model_outputs_switch():
 
 
 def test_refine_last_only_arguments():
-    from nndepth_amd import ops, weightgen
+    from nndepth_amd import _lib, ops, weightgen
     from nndepth_amd._lib import NndError
     from oracle import torch_ref as R
     eng = ops.UpdateBlockEngine(128, 64, 36, 1, 576, "sep_conv", "fp16x2")
@@ -93,6 +93,6 @@ def test_refine_last_only_arguments():
         with pytest.raises(NndError, match="keep_all"):
             call(keep_all=True, last_only=True)
     # the flag is set on a per-call copy of the descriptor, never on the engine's own
-    d = eng._refine_desc(True)
+    d = ops._call_desc(eng, _lib.NND_FLAG_LAST_UPSAMPLE_ONLY)
     assert d.flags == 2 and eng.desc.flags == 0
-    assert eng._refine_desc(False).flags == 0
+    assert ops._call_desc(eng).flags == 0
