@@ -36,6 +36,22 @@ void set_error(const char* fmt, ...);
         }                                                                                \
     } while (0)
 
+// status of a launcher into the caller's `int rc`; returns it on failure
+#define NND_TRY(x)                           \
+    do {                                     \
+        if ((rc = (x)) != NND_OK) return rc; \
+    } while (0)
+
+// What every plan builder checks first: a descriptor starts with struct_size = sizeof(its struct) and carries known flag bits only
+template <class Desc>
+static inline int check_desc(const Desc* d, unsigned allowed_flags, const char* name) {
+    NND_REQUIRE(d, "%s: null descriptor", name);
+    NND_REQUIRE(d->struct_size == (int32_t)sizeof(Desc), "%s: descriptor of %d bytes, this library expects %d (struct_size)", name,
+                d->struct_size, (int)sizeof(Desc));
+    NND_REQUIRE((d->flags & ~allowed_flags) == 0, "%s: unknown flags 0x%x", name, d->flags);
+    return NND_OK;
+}
+
 // Diagnostic / tuning switches (NND_* environment variables, listed in include/nndepth_amd.h): read ONCE when the library is
 // loaded and again only by nnd_reload_switches(); the hot path never calls getenv.  They select between kernels that the parity
 // tests prove equivalent, never a non-HIP path.

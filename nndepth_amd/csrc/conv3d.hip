@@ -8,8 +8,8 @@
 // where the 2-D kernel also strides by 2).  A channel concat of two volumes (proj_2 / proj_3) is the kernel's virtual
 // concat of two such windows.  No im2col, no extra copy; the zero slices provide the depth padding.
 #include "common.h"
+#include "conv_layer.h"
 
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -25,32 +25,54 @@ static int group_of(const nnd_conv3d_desc* d) {
     return d->Cout <= 8 ? 4 : (d->Cout <= 16 ? 2 : 1);
 }
 
-static int conv3d_layer(const nnd_conv3d_desc* d, int J, ConvLayer* L, int64_t* total) {
-    NND_REQUIRE(d, "conv3d: null descriptor");
-    NND_REQUIRE(d->struct_size == (int32_t)sizeof(nnd_conv3d_desc), "conv3d: descriptor of %d bytes, this library expects %d (struct_size)",
-                d->struct_size, (int)sizeof(nnd_conv3d_desc));
-    NND_REQUIRE((d->flags & ~NND_FLAG_CALIBRATE) == 0, "conv3d: unknown flags 0x%x", d->flags);
+// the 2-D layer that computes J adjacent output slices per launch element, at *off
+static int conv3d_layer(const nnd_conv3d_desc* d, int J, ConvLayer* L, int64_t* off) {
+    const int Cin = (J + 2) * (d->Cin0 + d->Cin1);
+    // CI_T = 16: windows of 3*Cin planes (24, 48, 96, 192) -> 16-channel chunks keep the two sources chunk-aligned
+    const bool aligned = d->Cin1 == 0 || ((J + 2) * d->Cin0) % 16 == 0;
+    NND_REQUIRE(aligned, "conv3d: first input of a concat needs (J+2)*Cin0 %% 16 == 0 (Cin0 = %d)", d->Cin0);
+    // split arithmetics: layers (stride 1 and 2) whose plane count is a multiple of 16 on the 16-bit MFMA kernel (conv_split)
+    *L = make_conv_layer(3, 3, Cin, J * d->Cout, d->stride, d->arithmetic, 16, true, off);
+    return NND_OK;
+}
+
+// The blob of one descriptor: [plain layer | J-slice grouped layer | thin3d weights | slab3d weights]; every formulation the shape
+// admits is packed, the forward picks one.  L1 / LJ keep offsets relative to off1 / offJ.
+struct Conv3dPlan {
+    ConvLayer L1, LJ;
+    int J;  // slices per launch element of the grouped layer; 1: none packed
+    bool has_thin, has_slab;
+    int64_t off1, offJ, off_thin, off_slab, total;
+    int64_t tail1, tailJ, tail_slab;  // float offset in the blob of each formulation's fp16x2 scale slot (SPLIT_TAIL_*); -1: it has none
+};
+
+static int make_conv3d_plan(const nnd_conv3d_desc* d, Conv3dPlan* p) {
+    if (int rc = check_desc(d, NND_FLAG_CALIBRATE, "conv3d")) return rc;
     NND_REQUIRE(d->Cout > 0 && d->Cin0 > 0 && d->Cin1 >= 0, "conv3d: bad channel counts");
     NND_REQUIRE(d->stride == 1 || d->stride == 2, "conv3d: stride %d not supported (1, 2)", d->stride);
     NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2, "conv3d: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3) or 2 (fp16x2)");
-    ConvLayer l;
-    l.KH = l.KW = 3;
-    l.Cin = (J + 2) * (d->Cin0 + d->Cin1);
-    l.Cout = J * d->Cout;
-    l.stride = d->stride;
-    // split arithmetics: layers (stride 1 and 2) whose plane count is a multiple of 16 on the 16-bit MFMA kernel (conv_split)
-    l.arith = (d->arithmetic != 0 && conv_split_supported(3, 3, l.Cin, d->stride, d->arithmetic, l.Cout) &&
-               (d->Cin1 == 0 || ((J + 2) * d->Cin0) % 16 == 0)) ? d->arithmetic : 0;
-    l.CI_T = 16;  // windows of 3*Cin planes: 24, 48, 96, 192 -> 16-channel chunks keep the two sources chunk-aligned
-    NND_REQUIRE(d->Cin1 == 0 || ((J + 2) * d->Cin0) % l.CI_T == 0, "conv3d: first input of a concat needs (J+2)*Cin0 %% 16 == 0 (Cin0 = %d)", d->Cin0);
-    l.nchunks = cdiv(l.Cin, l.CI_T);
-    l.ncb = cdiv(l.Cout, 32);
-    int64_t off = 0;
-    l.w_off = off; off += l.w_floats();
-    l.b_off = off; off += l.b_floats();
-    l.s_off = off; off += l.b_floats();
-    *L = l;
-    if (total) *total = off;
+    const int Ct = d->Cin0 + d->Cin1;
+    int64_t off = 0, rel = 0;
+    p->off1 = off;
+    if (int rc = conv3d_layer(d, 1, &p->L1, &rel)) return rc;
+    off += rel;
+    p->J = group_of(d);
+    p->offJ = off;
+    if (p->J > 1) {
+        rel = 0;
+        if (int rc = conv3d_layer(d, p->J, &p->LJ, &rel)) return rc;
+        off += rel;
+    }
+    p->has_thin = thin3d_supported(d->Cout, d->stride);
+    p->off_thin = off;
+    if (p->has_thin) off += thin3d_packed_floats(d->Cout, Ct);
+    p->has_slab = slab3d_supported(d->Cout, d->Cin0, d->Cin1, d->stride, d->arithmetic);
+    p->off_slab = off;
+    if (p->has_slab) off += slab3d_packed_floats(d->Cout, Ct, d->stride);
+    p->tail_slab = p->has_slab ? off - 4 : -1;  // slab3d's part ends with its slot (slab3d.hip: slab3d_packed_floats)
+    p->total = off;
+    p->tail1 = p->L1.arith == 2 ? p->off1 + p->L1.tail_off() : -1;
+    p->tailJ = p->J > 1 && p->LJ.arith == 2 ? p->offJ + p->LJ.tail_off() : -1;
     return NND_OK;
 }
 
@@ -239,15 +261,9 @@ using namespace nnd;
 extern "C" {
 
 int64_t nnd_conv3d_packed_floats(const nnd_conv3d_desc* desc) {
-    ConvLayer L;
-    int64_t t1, tj = 0;
-    if (conv3d_layer(desc, 1, &L, &t1) != NND_OK) return NND_ERR_INVALID;
-    const int J = group_of(desc);
-    if (J > 1 && conv3d_layer(desc, J, &L, &tj) != NND_OK) return NND_ERR_INVALID;
-    const int64_t tt = thin3d_supported(desc->Cout, desc->stride) ? thin3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1) : 0;
-    const int64_t ts = slab3d_supported(desc->Cout, desc->Cin0, desc->Cin1, desc->stride, desc->arithmetic)
-                           ? slab3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1, desc->stride) : 0;
-    return t1 + tj + tt + ts;  // [plain layer | J-slice grouped layer | thin-layer VALU kernel | depth-marching MFMA kernel]
+    Conv3dPlan p;
+    if (make_conv3d_plan(desc, &p) != NND_OK) return NND_ERR_INVALID;
+    return p.total;
 }
 
 // Which formulation a thin (Cout 8 / 16) layer takes.  fp16x2 at stride 1 (conv1.1, conv2_up, proj_2, conv1_up, final_conv):
@@ -258,19 +274,17 @@ int64_t nnd_conv3d_packed_floats(const nnd_conv3d_desc* desc) {
 // 32->16 547 / 277, conv1_up 16->8 1020 / 876, but final_conv 8->8 533 / 600 (K = 6 x 8 x 9 is too short for the workgroup's
 // fixed phases) and the stride-2 layers 330 / 1041 (no stride-2 split kernel): those two kinds stay on the VALU kernel.
 // fp16x2, the regulariser's thin (Cin, Cout, stride) triples: the depth-marching MFMA kernel of slab3d.hip (NND_NO_SLAB3D: the rules below)
-static bool use_slab(const nnd_conv3d_desc* d) {
-    return !switches().no_slab3d && slab3d_supported(d->Cout, d->Cin0, d->Cin1, d->stride, d->arithmetic);
-}
+static bool use_slab(const Conv3dPlan& p) { return p.has_slab && !switches().no_slab3d; }
 
-static bool use_thin(const nnd_conv3d_desc* d) {
-    if (switches().no_thin3d || !thin3d_supported(d->Cout, d->stride)) return false;
+static bool use_thin(const Conv3dPlan& p, const nnd_conv3d_desc* d) {
+    if (switches().no_thin3d || !p.has_thin) return false;
     if (d->arithmetic == 0 || d->stride != 1) return true;
     return d->Cin0 + d->Cin1 <= 8;
 }
 
-// 2-D weights of the J-slice grouped layer: (J*Cout, (J+2)*Ct, 3, 3) with [window of input 0: slice-major, ci][window of input 1]
-static void pack_one(const nnd_conv3d_desc* desc, const ConvLayer& L, int J, const float* w, const float* bias, const float* g,
-                     const float* be, const float* mean, const float* var, float eps, float* base) {
+// 2-D weights of the J-slice grouped layer: (J*Cout, (J+2)*Ct, 3, 3) with [window of input 0: slice-major, ci][window of input 1];
+// every group of Cout output channels takes the layer's folded affine sc / sh (Cout each)
+static void pack_one(const nnd_conv3d_desc* desc, const ConvLayer& L, int J, const float* w, const float* sc, const float* sh, float* base) {
     const int C0 = desc->Cin0, C1 = desc->Cin1, Ct = C0 + C1, Co = desc->Cout, S = J + 2;
     std::vector<float> w2((size_t)J * Co * S * Ct * 9, 0.f);
     for (int j = 0; j < J; ++j)
@@ -286,139 +300,89 @@ static void pack_one(const nnd_conv3d_desc* desc, const ConvLayer& L, int J, con
     const float* bs[1] = {nullptr};
     int cc[1] = {J * Co};
     pack_conv(L, 1, ws, bs, cc, base);
-    float* shift = base + L.b_off;
-    float* scale = base + L.s_off;
-    for (int c = 0; c < L.ncb * 32; ++c) {
-        double sc = 1.0, sh = 0.0;
-        if (c < J * Co) {
-            const int co = c % Co;
-            const double b = bias ? (double)bias[co] : 0.0;
-            if (g) {
-                sc = (double)g[co] / std::sqrt((double)var[co] + (double)eps);
-                sh = (b - (double)mean[co]) * sc + (double)be[co];
-            } else {
-                sh = b;
-            }
-        }
-        scale[c] = (float)sc;
-        shift[c] = (float)sh;
-    }
+    pack_affine(L, base, Co, [&](int co) { return Affine{sc[co], sh[co]}; });
 }
 
 // w (Cout, Cin0+Cin1, 3, 3, 3) [kd, kh, kw]; bias may be NULL (the reference's ConvBn3D has bias=False); bn_* may be NULL
 int nnd_conv3d_pack(const nnd_conv3d_desc* desc, const float* w, const float* bias, const float* bn_gamma, const float* bn_beta,
                     const float* bn_mean, const float* bn_var, float bn_eps, float* packed_host) {
-    ConvLayer L1, LJ;
-    int64_t t1;
-    int rc = conv3d_layer(desc, 1, &L1, &t1);
+    Conv3dPlan p;
+    int rc = make_conv3d_plan(desc, &p);
     if (rc != NND_OK) return rc;
     NND_REQUIRE(w && packed_host, "conv3d_pack: null pointer");
     NND_REQUIRE(!bn_gamma || (bn_beta && bn_mean && bn_var), "conv3d_pack: incomplete batch-norm parameters");
-    pack_one(desc, L1, 1, w, bias, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, packed_host);
-    const int J = group_of(desc);
-    int64_t tj = 0;
-    if (J > 1) {
-        if ((rc = conv3d_layer(desc, J, &LJ, &tj)) != NND_OK) return rc;
-        pack_one(desc, LJ, J, w, bias, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, packed_host + t1);
+    const int Ct = desc->Cin0 + desc->Cin1;
+    std::vector<float> sc(desc->Cout), sh(desc->Cout);  // one folded affine for every formulation
+    for (int co = 0; co < desc->Cout; ++co) {
+        const Affine a = fold_norm(co, bias, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps);
+        sc[co] = a.scale;
+        sh[co] = a.shift;
     }
-    const bool thin = thin3d_supported(desc->Cout, desc->stride);
-    const bool slab = slab3d_supported(desc->Cout, desc->Cin0, desc->Cin1, desc->stride, desc->arithmetic);
-    if (thin || slab) {  // same folded affine; weights in [ci][tap][co] order (VALU kernel) / as A fragments (depth-marching kernel)
-        std::vector<float> sc(desc->Cout), sh(desc->Cout);
-        for (int co = 0; co < desc->Cout; ++co) {
-            const double b = bias ? (double)bias[co] : 0.0;
-            double s1 = 1.0, s0 = b;
-            if (bn_gamma) {
-                s1 = (double)bn_gamma[co] / std::sqrt((double)bn_var[co] + (double)bn_eps);
-                s0 = (b - (double)bn_mean[co]) * s1 + (double)bn_beta[co];
-            }
-            sc[co] = (float)s1;
-            sh[co] = (float)s0;
-        }
-        const int64_t tt = thin ? thin3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1) : 0;
-        if (thin) thin3d_pack(desc->Cout, desc->Cin0 + desc->Cin1, w, sc.data(), sh.data(), packed_host + t1 + tj);
-        if (slab) slab3d_pack(desc->Cout, desc->Cin0 + desc->Cin1, desc->stride, w, sc.data(), sh.data(), packed_host + t1 + tj + tt);
+    pack_one(desc, p.L1, 1, w, sc.data(), sh.data(), packed_host + p.off1);
+    if (p.J > 1) pack_one(desc, p.LJ, p.J, w, sc.data(), sh.data(), packed_host + p.offJ);
+    // weights in [ci][tap][co] order (VALU kernel) / as A fragments (depth-marching kernel)
+    if (p.has_thin) thin3d_pack(desc->Cout, Ct, w, sc.data(), sh.data(), packed_host + p.off_thin);
+    if (p.has_slab) slab3d_pack(desc->Cout, Ct, desc->stride, w, sc.data(), sh.data(), packed_host + p.off_slab);
+    return NND_OK;
+}
+
+// every formulation of the layer that is packed in fp16x2 has its own slot; the one the forwards did not take reports "staged nothing"
+int nnd_conv3d_calibration_finish(const nnd_conv3d_desc* desc, float* packed_dev, int32_t* status_dev, void* stream) {
+    Conv3dPlan p;
+    int rc = make_conv3d_plan(desc, &p);
+    if (rc != NND_OK) return rc;
+    NND_REQUIRE(packed_dev, "conv3d_calibration_finish: null blob");
+    int64_t offs[3];
+    int n = 0;
+    for (int64_t t : {p.tail1, p.tailJ, p.tail_slab})
+        if (t >= 0) offs[n++] = t;
+    return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
+}
+
+// the zero end slices of a depth-major output (N, Do+2, C, Ho*Wo)
+static int zero_end_slices(float* y, int N, int Do, int64_t slice, hipStream_t s) {
+    for (int n = 0; n < N; ++n) {
+        float* yn = y + (int64_t)n * (Do + 2) * slice;
+        NND_HIP_CHECK(hipMemsetAsync(yn, 0, sizeof(float) * slice, s));
+        NND_HIP_CHECK(hipMemsetAsync(yn + (int64_t)(Do + 1) * slice, 0, sizeof(float) * slice, s));
     }
     return NND_OK;
 }
 
 // x0 (N, D+2, Cin0, H, W), x1 (N, D+2, Cin1, H, W) or NULL, y (N, Do+2, Cout, Ho, Wo) — all depth-major with zero end slices
 // (y's end slices are written by this call); Do = ceil(D/stride) etc.  leaky_slope: LeakyReLU negative slope (1 = none).
-// every formulation of the layer that is packed in fp16x2 has its own slot; the one the forwards did not take reports "staged nothing"
-int nnd_conv3d_calibration_finish(const nnd_conv3d_desc* desc, float* packed_dev, int32_t* status_dev, void* stream) {
-    ConvLayer L1, LJ;
-    int64_t t1, tj = 0;
-    int rc = conv3d_layer(desc, 1, &L1, &t1);
-    if (rc != NND_OK) return rc;
-    NND_REQUIRE(packed_dev, "conv3d_calibration_finish: null blob");
-    const int J = group_of(desc);
-    if (J > 1 && (rc = conv3d_layer(desc, J, &LJ, &tj)) != NND_OK) return rc;
-    int64_t offs[3];
-    int n = 0;
-    if (L1.arith == 2) offs[n++] = L1.tail_off();
-    if (J > 1 && LJ.arith == 2) offs[n++] = t1 + LJ.tail_off();
-    if (slab3d_supported(desc->Cout, desc->Cin0, desc->Cin1, desc->stride, desc->arithmetic)) {
-        const int64_t tt = thin3d_supported(desc->Cout, desc->stride) ? thin3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1) : 0;
-        offs[n++] = t1 + tj + tt + slab3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1, desc->stride) - 4;
-    }
-    return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
-}
-
 int nnd_conv3d_forward(const nnd_conv3d_desc* desc, const float* packed, const float* x0, const float* x1, float* y, int N, int D,
                        int H, int W, float leaky_slope, void* stream) {
-    ConvLayer L;
-    int64_t t1;
-    int rc = conv3d_layer(desc, 1, &L, &t1);
+    Conv3dPlan p;
+    int rc = make_conv3d_plan(desc, &p);
     if (rc != NND_OK) return rc;
     NND_REQUIRE(packed && x0 && y && (desc->Cin1 == 0 || x1), "conv3d_forward: null pointer");
     NND_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "conv3d_forward: bad shape");
     CalibScope calib((desc->flags & NND_FLAG_CALIBRATE) && desc->arithmetic == 2);
     hipStream_t s = (hipStream_t)stream;
-    if (use_slab(desc) || use_thin(desc)) {
-        const int st0 = desc->stride;
-        const int Do0 = (D + st0 - 1) / st0, Ho0 = (H + st0 - 1) / st0, Wo0 = (W + st0 - 1) / st0;
-        const int64_t hwo0 = (int64_t)Ho0 * Wo0;
-        for (int n = 0; n < N; ++n) {  // the zero end slices of the output
-            float* yn = y + (int64_t)n * (Do0 + 2) * desc->Cout * hwo0;
-            NND_HIP_CHECK(hipMemsetAsync(yn, 0, sizeof(float) * desc->Cout * hwo0, s));
-            NND_HIP_CHECK(hipMemsetAsync(yn + (int64_t)(Do0 + 1) * desc->Cout * hwo0, 0, sizeof(float) * desc->Cout * hwo0, s));
-        }
-        int64_t tj0 = 0;
-        const int J0 = group_of(desc);
-        ConvLayer LJ0;
-        if (J0 > 1 && (rc = conv3d_layer(desc, J0, &LJ0, &tj0)) != NND_OK) return rc;
-        if (use_slab(desc)) {
-            const int64_t tt0 = thin3d_supported(desc->Cout, st0) ? thin3d_packed_floats(desc->Cout, desc->Cin0 + desc->Cin1) : 0;
-            return slab3d_forward(desc->Cout, desc->Cin0, desc->Cin1, st0, packed + t1 + tj0 + tt0, x0, x1, y, N, D, H, W, leaky_slope, s);
-        }
-        return thin3d_forward(desc->Cout, desc->Cin0, desc->Cin1, st0, packed + t1 + tj0, x0, x1, y, N, D, H, W, leaky_slope, s);
-    }
-    int J = group_of(desc);
-    if (D % J != 0) J = 1;  // the grouped layer needs whole groups of slices; the plain one is always packed as well
-    const float* blob = packed;
-    if (J > 1) {
-        if ((rc = conv3d_layer(desc, J, &L, nullptr)) != NND_OK) return rc;
-        blob = packed + t1;
-    }
-    const int st = desc->stride;
+    const int st = desc->stride, Cout = desc->Cout;
     const int Do = (D + st - 1) / st, Ho = (H + st - 1) / st, Wo = (W + st - 1) / st;
-    NND_REQUIRE(Do / J <= 65535, "conv3d_forward: depth %d exceeds the grid limit", Do);
     const int64_t hw = (int64_t)H * W, hwo = (int64_t)Ho * Wo;
+    // the formulation: slab, thin, or the MFMA layer — grouped where the depth is whole groups of J slices, else the plain one
+    const bool slab = use_slab(p), thin = !slab && use_thin(p, desc);
+    const int J = (slab || thin || D % p.J != 0) ? 1 : p.J;
+    if (!slab && !thin) NND_REQUIRE(Do / J <= 65535, "conv3d_forward: depth %d exceeds the grid limit", Do);
+    NND_TRY(zero_end_slices(y, N, Do, Cout * hwo, s));
+    if (slab) return slab3d_forward(Cout, desc->Cin0, desc->Cin1, st, packed + p.off_slab, x0, x1, y, N, D, H, W, leaky_slope, s);
+    if (thin) return thin3d_forward(Cout, desc->Cin0, desc->Cin1, st, packed + p.off_thin, x0, x1, y, N, D, H, W, leaky_slope, s);
+    const ConvLayer& L = J > 1 ? p.LJ : p.L1;
+    const float* blob = packed + (J > 1 ? p.offJ : p.off1);
     for (int n = 0; n < N; ++n) {
-        float* yn = y + (int64_t)n * (Do + 2) * desc->Cout * hwo;
-        NND_HIP_CHECK(hipMemsetAsync(yn, 0, sizeof(float) * desc->Cout * hwo, s));
-        NND_HIP_CHECK(hipMemsetAsync(yn + (int64_t)(Do + 1) * desc->Cout * hwo, 0, sizeof(float) * desc->Cout * hwo, s));
         ConvIO io{};
         // launch element g computes output slices g*J .. g*J+J-1 from padded input slices st*g*J .. (+J+1)
         io.src0 = Act{const_cast<float*>(x0) + (int64_t)n * (D + 2) * desc->Cin0 * hw, (int64_t)st * J * desc->Cin0 * hw, (J + 2) * desc->Cin0};
         if (desc->Cin1 > 0)
             io.src1 = Act{const_cast<float*>(x1) + (int64_t)n * (D + 2) * desc->Cin1 * hw, (int64_t)st * J * desc->Cin1 * hw, (J + 2) * desc->Cin1};
-        io.out0 = Act{yn + desc->Cout * hwo, (int64_t)J * desc->Cout * hwo, J * desc->Cout};
+        io.out0 = Act{y + ((int64_t)n * (Do + 2) + 1) * Cout * hwo, (int64_t)J * Cout * hwo, J * Cout};
         io.Hin = H; io.Win = W;
         io.flags = leaky_slope != 1.0f ? 4 : 0;
         io.scale = leaky_slope;
-        rc = launch_conv(L, blob, io, EPI_AFFINE, Do / J, Ho, Wo, s);
-        if (rc != NND_OK) return rc;
+        NND_TRY(launch_conv(L, blob, io, EPI_AFFINE, Do / J, Ho, Wo, s));
     }
     return NND_OK;
 }

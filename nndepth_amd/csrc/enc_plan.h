@@ -4,6 +4,7 @@
 // kernels) and conv_mfma's (a ConvLayer: fragments, bias, per-channel scale).
 #pragma once
 #include "common.h"
+#include "conv_layer.h"
 
 #include <cstdint>
 #include <cstring>
@@ -45,31 +46,22 @@ inline void enc_add_raw(EncPlan& p, int kind, int cin, int cout, int k, int stri
 inline EncLayer enc_mfma_layer(int cin, int cout, int k, int stride, int act) {
     EncLayer l{};
     l.kind = ENC_MFMA; l.cin = cin; l.cout = cout; l.k = k; l.stride = stride; l.act = act;
-    ConvLayer L;
-    L.KH = k; L.KW = k; L.Cin = cin; L.Cout = cout; L.stride = stride; L.arith = 0;
     // a stride-1 1x1 takes 32-channel K chunks (conv_ci_t would take 128 from Cin = 128 on), so that split-K 2 (enc_run_mfma) applies
     // from Cin = 64
-    L.CI_T = (k == 1 && stride == 1) ? 32 : conv_ci_t(k, k, cin, stride, cout);
-    L.nchunks = cdiv(cin, L.CI_T);
-    L.ncb = cdiv(cout, 32);
-    int64_t off = 0;
-    L.w_off = off; off += L.w_floats();
-    L.b_off = off; off += L.b_floats();
-    L.s_off = off; off += L.b_floats();
-    l.cl = L;
-    l.floats = off;
+    l.cl = make_conv_layer(k, k, cin, cout, stride, 0, (k == 1 && stride == 1) ? 32 : 0, true, &l.floats);
     return l;
 }
 
 inline void enc_add_mfma(EncPlan& p, int cin, int cout, int k, int stride, int act) { enc_add(p, enc_mfma_layer(cin, cout, k, stride, act)); }
 
-// scale: the per-channel scale of EPI_AFFINE (nullptr: 1)
+// scale: the per-channel scale of EPI_AFFINE (nullptr: 1); the padded channels take scale 0 here, not the 1 of the folded-norm
+// packers (kept as it was: the blob's bytes are pinned, tests/test_pack_pins_cpu.py and the encoder sides' own pins)
 inline void enc_pack_mfma(const EncLayer& l, const float* w, const float* b, const float* scale, float* base) {
     const float* ws[1] = {w};
     const float* bs[1] = {b};
     int co[1] = {l.cout};
     pack_conv(l.cl, 1, ws, bs, co, base);
-    for (int c = 0; c < l.cl.ncb * 32; ++c) base[l.cl.s_off + c] = c < l.cout ? (scale ? scale[c] : 1.f) : 0.f;
+    pack_affine(l.cl, base, l.cout, [&](int c) { return Affine{scale ? scale[c] : 1.f, b[c]}; }, 0.f);
 }
 
 inline void enc_pack_raw(const EncLayer& l, const float* w, const float* b, float* base) {

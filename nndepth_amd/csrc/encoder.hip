@@ -22,9 +22,9 @@
 // conv epilogue: y = acc * (gamma / sqrt(var + eps)) + ((bias - mean) * gamma / sqrt(var + eps) + beta).
 // Intermediate activations live in the tile-major workspace layout (layout.h); the input frames and the outputs are NCHW.
 #include "common.h"
+#include "conv_layer.h"
 #include "layout.h"
 
-#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -43,20 +43,11 @@ static int conv_layer(const nnd_conv_desc* d, ConvLayer* L, int64_t* total, int 
     else
         NND_REQUIRE(k11 || k33 || (d->KH == 1 && d->KW == 5) || (d->KH == 5 && d->KW == 1),
                     "conv: kernel %dx%d not built (1x1, 3x3, 1x5, 5x1)", d->KH, d->KW);
-    ConvLayer l;
-    l.KH = d->KH; l.KW = d->KW; l.Cin = d->Cin; l.Cout = d->Cout; l.stride = d->stride;
     // the stride-1 1x1 projections stay on the streaming fp32 kernel (HBM-bound); 3x3 layers (stride 1 and 2) and the stride-2
     // 1x1 shortcuts may take the split kernel
-    if (arith != 0 && ((k11 && d->stride == 1) || !conv_split_supported(d->KH, d->KW, d->Cin, d->stride, arith, d->Cout))) arith = 0;
-    l.arith = arith;
-    l.CI_T = arith ? 16 : conv_ci_t(d->KH, d->KW, d->Cin, d->stride, d->Cout);
-    l.nchunks = cdiv(d->Cin, l.CI_T);
-    l.ncb = cdiv(d->Cout, 32);
+    if (k11 && d->stride == 1) arith = 0;
     int64_t off = 0;
-    l.w_off = off; off += l.w_floats();
-    l.b_off = off; off += l.b_floats();
-    l.s_off = off; off += l.b_floats();
-    *L = l;
+    *L = make_conv_layer(d->KH, d->KW, d->Cin, d->Cout, d->stride, arith, 0, true, &off);
     if (total) *total = off;
     return NND_OK;
 }
@@ -68,22 +59,7 @@ static void pack_conv_norm(const ConvLayer& L, const float* w, const float* bias
     const float* bs[1] = {nullptr};
     int co[1] = {L.Cout};
     pack_conv(L, 1, ws, bs, co, base);
-    float* shift = base + L.b_off;
-    float* scale = base + L.s_off;
-    for (int c = 0; c < L.ncb * 32; ++c) {
-        double sc = 1.0, sh = 0.0;
-        if (c < L.Cout) {
-            const double b = bias ? (double)bias[c] : 0.0;
-            if (gamma) {
-                sc = (double)gamma[c] / std::sqrt((double)var[c] + (double)eps);
-                sh = (b - (double)mean[c]) * sc + (double)beta[c];
-            } else {
-                sh = b;
-            }
-        }
-        scale[c] = (float)sc;
-        shift[c] = (float)sh;
-    }
+    pack_affine(L, base, L.Cout, [&](int c) { return fold_norm(c, bias, gamma, beta, mean, var, eps); });
 }
 
 // (x_c4 / y_c4: tile-major tensors with 4 channels interleaved, layout.h; the residual follows y's layout)
@@ -436,14 +412,12 @@ struct EncPlan {
     ConvLayer cnet;  // cnet_proj 3x3 (optional)
     int64_t base_cnet;
     int64_t total;
+    int units;  // convs in pack order (6 tensor pointers each): stem | 3 per block | conv2 | cnet_proj (optional)
     int planes[ENC_BLOCKS], strides[ENC_BLOCKS], inpl[ENC_BLOCKS];
 };
 
 static int make_enc_plan(const nnd_encoder_desc* d, EncPlan* p) {
-    NND_REQUIRE(d, "encoder: null descriptor");
-    NND_REQUIRE(d->struct_size == (int32_t)sizeof(nnd_encoder_desc), "encoder: descriptor of %d bytes, this library expects %d (struct_size)",
-                d->struct_size, (int)sizeof(nnd_encoder_desc));
-    NND_REQUIRE((d->flags & ~NND_FLAG_CALIBRATE) == 0, "encoder: unknown flags 0x%x", d->flags);
+    if (int rc = check_desc(d, NND_FLAG_CALIBRATE, "encoder")) return rc;
     NND_REQUIRE(d->output_dim > 0 && d->cnet_dim >= 0, "encoder: bad output_dim / cnet_dim");
     NND_REQUIRE(d->norm >= 0 && d->norm <= 2, "encoder: norm must be 0 (none), 1 (batch, eval) or 2 (instance); group norm is not built");
     NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2, "encoder: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3) or 2 (fp16x2)");
@@ -480,6 +454,7 @@ static int make_enc_plan(const nnd_encoder_desc* d, EncPlan* p) {
         off += t;
     }
     p->total = off;
+    p->units = 1 + 3 * ENC_BLOCKS + 1 + (d->cnet_dim > 0 ? 1 : 0);
     return NND_OK;
 }
 
@@ -527,7 +502,7 @@ int nnd_conv_forward(const nnd_conv_desc* desc, const float* packed_dev, const f
 int nnd_encoder_num_tensors(const nnd_encoder_desc* desc) {
     EncPlan p;
     if (make_enc_plan(desc, &p) != NND_OK) return NND_ERR_INVALID;
-    return 6 * (1 + 3 * ENC_BLOCKS + 1 + (desc->cnet_dim > 0 ? 1 : 0));
+    return 6 * p.units;
 }
 
 int64_t nnd_encoder_packed_floats(const nnd_encoder_desc* desc) {
@@ -551,7 +526,7 @@ int nnd_encoder_pack(const nnd_encoder_desc* desc, const float* const* t, float 
     int rc = make_enc_plan(desc, &p);
     if (rc != NND_OK) return rc;
     NND_REQUIRE(t && packed_host, "encoder_pack: null pointer");
-    const int units = 1 + 3 * ENC_BLOCKS + 1 + (desc->cnet_dim > 0 ? 1 : 0);
+    const int units = p.units;
     for (int u = 0; u < units; ++u) {
         NND_REQUIRE(t[6 * u] && t[6 * u + 1], "encoder_pack: unit %d: null weight / bias", u);
         const bool has_norm = t[6 * u + 2] != nullptr;
@@ -566,13 +541,9 @@ int nnd_encoder_pack(const nnd_encoder_desc* desc, const float* const* t, float 
         for (int co = 0; co < 64; ++co)
             for (int k = 0; k < 147; ++k) packed_host[p.stem_w + (int64_t)k * 64 + co] = q[0][co * 147 + k];  // row 147 stays zero
         for (int c = 0; c < 64; ++c) {
-            double sc = 1.0, sh = q[1][c];
-            if (q[2]) {
-                sc = (double)q[2][c] / std::sqrt((double)q[5][c] + (double)bn_eps);
-                sh = ((double)q[1][c] - (double)q[4][c]) * sc + (double)q[3][c];
-            }
-            packed_host[p.stem_scale + c] = (float)sc;
-            packed_host[p.stem_shift + c] = (float)sh;
+            const Affine a = fold_norm(c, q[1], q[2], q[3], q[4], q[5], bn_eps);
+            packed_host[p.stem_scale + c] = a.scale;
+            packed_host[p.stem_shift + c] = a.shift;
         }
     }
     int u = 1;
@@ -652,10 +623,6 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed, cons
         NND_LAUNCH_CHECK();
     }
     int cur = 0;  // buffer holding the block input
-#define NND_TRY(x)                    \
-    do {                              \
-        if ((rc = (x)) != NND_OK) return rc; \
-    } while (0)
     if (inorm) {  // norm1 + ReLU of the stem
         NND_TRY(in_stats(buf[0], 64 * tiled_plane(h, w), N, 64, h, w, eps, st_a, part, s, c4));
         NND_TRY(in_apply(buf[0], 64 * tiled_plane(h, w), st_a, nullptr, 0, nullptr, N, 64, h, w, true, s, c4));
@@ -691,7 +658,6 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed, cons
     if (cnet_out)
         NND_TRY(run_conv_norm(p.cnet, packed + p.base_cnet, fmap, (int64_t)desc->output_dim * h * w, false, nullptr, 0, cnet_out,
                               (int64_t)desc->cnet_dim * h * w, false, 1, n_cnet, h, w, s));
-#undef NND_TRY
     return NND_OK;
 }
 

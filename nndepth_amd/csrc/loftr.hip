@@ -13,6 +13,7 @@
 //   m = LayerNorm2(W2 relu(W1 [x | m]))                  conv_mfma (virtual concat, ReLU epilogue) x 2 + layernorm_kernel
 //   out = x + m                                          fused into the second layernorm_kernel
 #include "common.h"
+#include "conv_layer.h"
 
 #include <cmath>
 #include <cstring>
@@ -159,14 +160,8 @@ struct LoftrPlan {
 };
 
 static ConvLayer lin(int Cout, int Cin, int64_t* off, int64_t* base) {
-    ConvLayer l;
-    l.KH = l.KW = 1; l.Cin = Cin; l.Cout = Cout; l.stride = 1;
-    l.CI_T = conv_ci_t(1, 1, Cin);
-    l.nchunks = cdiv(Cin, l.CI_T);
-    l.ncb = cdiv(Cout, 32);
     int64_t o = 0;
-    l.w_off = o; o += l.w_floats();
-    l.b_off = o; o += l.b_floats();
+    const ConvLayer l = make_conv_layer(1, 1, Cin, Cout, 1, 0, 0, false, &o);
     *base = *off;
     *off += o;
     return l;
@@ -262,10 +257,6 @@ int nnd_loftr_layer_forward(int d_model, int nhead, const float* packed, const f
     const int nchunks = (int)cdiv64(L, KV_PIX);
     float* partial = t + 2 * map;
     float* kv = partial + (int64_t)N * nhead * nchunks * (32 * 32 + 32);
-#define NND_TRY(x)                    \
-    do {                              \
-        if ((rc = (x)) != NND_OK) return rc; \
-    } while (0)
     NND_TRY(run_lin(p.q, packed + p.bq, x, C, nullptr, 0, bs, 0, q, bs, false, N, H, W, s));
     NND_TRY(run_lin(p.k, packed + p.bk, source, C, nullptr, 0, bs, 0, k, bs, false, N, H, W, s));
     NND_TRY(run_lin(p.v, packed + p.bv, source, C, nullptr, 0, bs, 0, v, bs, false, N, H, W, s));
@@ -288,7 +279,6 @@ int nnd_loftr_layer_forward(int d_model, int nhead, const float* packed, const f
     hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(L, 32), N), dim3(256), 0, s, (const float*)k, (long)bs, packed + p.ln2,
                        packed + p.ln2 + C, x, (long)bs, out, (long)bs, C, L, 1e-5f);
     NND_LAUNCH_CHECK();
-#undef NND_TRY
     return NND_OK;
 }
 

@@ -206,10 +206,7 @@ const int MB_NBLOCKS = (int)(sizeof(MB_BLOCKS) / sizeof(MB_BLOCKS[0]));
 constexpr int MB_S1_C = 24;  // stage 1's width: fnet_proj / cnet_proj input
 
 static int mb_check(const nnd_mbv3_desc* d) {
-    NND_REQUIRE(d, "mbv3: null descriptor");
-    NND_REQUIRE(d->struct_size == (int)sizeof(nnd_mbv3_desc), "mbv3: struct_size %d != sizeof(nnd_mbv3_desc) %d (header mismatch)",
-                d->struct_size, (int)sizeof(nnd_mbv3_desc));
-    NND_REQUIRE(d->flags == 0, "mbv3: unknown flags 0x%x", d->flags);
+    if (int rc = check_desc(d, 0, "mbv3")) return rc;
     NND_REQUIRE(d->fnet_dim >= 1 && d->fnet_dim <= 4096, "mbv3: fnet_dim %d (fnet_proj output channels, 1..4096)", d->fnet_dim);
     NND_REQUIRE(d->cnet_dim >= 1 && d->cnet_dim <= 4096, "mbv3: cnet_dim %d (cnet_proj output channels, 1..4096)", d->cnet_dim);
     return NND_OK;

@@ -251,10 +251,7 @@ enum MdKind { MD_UP = 16, MD_HEAD3 = 17, MD_HEAD1 = 18 };
 constexpr int MD_TAP_C[4] = {24, 40, 112, 160};
 
 static int md_check(const nnd_midas_desc* d) {
-    NND_REQUIRE(d, "midas: null descriptor");
-    NND_REQUIRE(d->struct_size == (int)sizeof(nnd_midas_desc), "midas: struct_size %d != sizeof(nnd_midas_desc) %d (header mismatch)",
-                d->struct_size, (int)sizeof(nnd_midas_desc));
-    NND_REQUIRE((d->flags & ~NND_MIDAS_KEEP_PRE) == 0, "midas: unknown flags 0x%x", d->flags);
+    if (int rc = check_desc(d, NND_MIDAS_KEEP_PRE, "midas")) return rc;
     return md_check_c("midas: feature_channels", d->feature_channels);
 }
 

@@ -164,10 +164,7 @@ static void rv_add_raw(EncPlan& p, int kind, int cin, int cout, int k, int strid
 }
 
 static int rv_check(const nnd_repvit_desc* d) {
-    NND_REQUIRE(d, "repvit: null descriptor");
-    NND_REQUIRE(d->struct_size == (int)sizeof(nnd_repvit_desc), "repvit: struct_size %d != sizeof(nnd_repvit_desc) %d (header mismatch)",
-                d->struct_size, (int)sizeof(nnd_repvit_desc));
-    NND_REQUIRE(d->flags == 0, "repvit: unknown flags 0x%x", d->flags);
+    if (int rc = check_desc(d, 0, "repvit")) return rc;
     for (int i = 0; i < 3; ++i)
         NND_REQUIRE(d->stem_strides[i] == 1 || d->stem_strides[i] == 2, "repvit: stem stride %d not built (1 or 2, as (1, 1) / (2, 2))",
                     d->stem_strides[i]);

@@ -12,6 +12,7 @@
 // conv whose epilogue emits z and r*h; convq's epilogue does the GRU blend in place.  The fused loops enqueue every
 // kernel of every iteration on the caller's stream (enqueue_refine).
 #include "common.h"
+#include "conv_layer.h"
 #include "layout.h"
 
 #include <cstdlib>
@@ -35,6 +36,7 @@ static const char* kConvNames[C_COUNT] = {"encoder.convc1", "encoder.convc2", "e
 struct Plan {
     nnd_update_block_desc d;
     bool sep;
+    int num_tensors;  // host tensors nnd_update_block_pack takes (weight, bias per conv of the reference module)
     ConvLayer L[C_COUNT];
     int64_t f1_w, f1_b;  // raw encoder.convf1 weights [128][fc][49] + bias [128]
     int64_t f1_wt;       // the same weights tap-major [fc*49][128] for the fused flow-branch kernel
@@ -42,27 +44,14 @@ struct Plan {
     int64_t total;
 };
 
-// arith != 0: the layer runs on conv_split.hip (fp32 operands as split bf16 pieces), if that kernel is built for its shape
+// a stride-1 layer without a scale slot at the running offset; arith != 0: the layer runs on conv_split.hip (fp32 operands as split
+// 16-bit pieces), if that kernel is built for its shape
 static ConvLayer mk(int KH, int KW, int Cin, int Cout, int64_t* off, int arith = 0) {
-    ConvLayer l;
-    if (arith != 0 && !conv_split_supported(KH, KW, Cin, 1, arith)) arith = 0;
-    const int CI_T = arith ? 16 : conv_ci_t(KH, KW, Cin, 1, Cout);
-    l.arith = arith;
-    l.KH = KH; l.KW = KW; l.Cin = Cin; l.Cout = Cout; l.CI_T = CI_T;
-    l.nchunks = cdiv(Cin, CI_T);
-    l.ncb = cdiv(Cout, 32);
-    l.w_off = *off;
-    *off += l.w_floats();
-    l.b_off = *off;
-    *off += l.b_floats();
-    return l;
+    return make_conv_layer(KH, KW, Cin, Cout, 1, arith, 0, false, off);
 }
 
 static int make_plan(const nnd_update_block_desc* d, Plan* p) {
-    NND_REQUIRE(d, "update_block: null descriptor");
-    NND_REQUIRE(d->struct_size == (int32_t)sizeof(nnd_update_block_desc), "update_block: descriptor of %d bytes, this library expects %d (struct_size)",
-                d->struct_size, (int)sizeof(nnd_update_block_desc));
-    NND_REQUIRE((d->flags & ~(NND_FLAG_CALIBRATE | NND_FLAG_LAST_UPSAMPLE_ONLY)) == 0, "update_block: unknown flags 0x%x", d->flags);
+    if (int rc = check_desc(d, NND_FLAG_CALIBRATE | NND_FLAG_LAST_UPSAMPLE_ONLY, "update_block")) return rc;
     const int hid = d->hidden_dim, ctx = d->context_dim, cp = d->cor_planes, fc = d->flow_channels, mc = d->mask_channels;
     NND_REQUIRE(hid > 0 && hid % 32 == 0, "update_block: hidden_dim %d must be a positive multiple of 32", hid);
     NND_REQUIRE(ctx > 0 && ctx % 8 == 0, "update_block: context_dim %d must be a positive multiple of 8", ctx);
@@ -78,6 +67,7 @@ static int make_plan(const nnd_update_block_desc* d, Plan* p) {
     auto ar = [&](int id) { return (d->arithmetic != 0 && ((split_mask >> id) & 1u)) ? d->arithmetic : 0; };
     p->d = *d;
     p->sep = d->gru_kind == 0;
+    p->num_tensors = p->sep ? 30 : 24;
     int64_t off = 0;
     const int gin = hid + ctx + hid;
     // convc1: split only where its K is whole 16-channel chunks (IGEV's 576 correlation planes: a 9.6-GFLOP GEMM per iteration at
@@ -555,10 +545,6 @@ static int run_flow_branch(const Plan& p, const float* blob, const Bufs& w, cons
 static int run_update(const Plan& p, const float* blob, const Bufs& w, Act corr, const float* flow, float* mask_dst,
                       float* delta_dst, int B, int H, int W, hipStream_t s) {
     int rc;
-#define NND_TRY(x)                    \
-    do {                              \
-        if ((rc = (x)) != NND_OK) return rc; \
-    } while (0)
     NND_TRY(run_conv(p, blob, w, C_C1, corr, nullptr, nullptr, B, H, W, s));
     NND_TRY(run_conv(p, blob, w, C_C2, corr, nullptr, nullptr, B, H, W, s));
     NND_TRY(run_flow_branch(p, blob, w, flow, corr, B, H, W, s));
@@ -602,7 +588,7 @@ extern "C" {
 int nnd_update_block_num_tensors(const nnd_update_block_desc* desc) {
     Plan p;
     if (make_plan(desc, &p) != NND_OK) return NND_ERR_INVALID;
-    return p.sep ? 30 : 24;
+    return p.num_tensors;
 }
 
 int64_t nnd_update_block_packed_floats(const nnd_update_block_desc* desc) {
@@ -616,8 +602,7 @@ int nnd_update_block_pack(const nnd_update_block_desc* desc, const float* const*
     int rc = make_plan(desc, &p);
     if (rc != NND_OK) return rc;
     NND_REQUIRE(t && out, "update_block_pack: null pointer");
-    const int n = p.sep ? 30 : 24;
-    for (int i = 0; i < n; ++i) NND_REQUIRE(t[i], "update_block_pack: tensor %d is null", i);
+    for (int i = 0; i < p.num_tensors; ++i) NND_REQUIRE(t[i], "update_block_pack: tensor %d is null", i);
     const int hid = p.d.hidden_dim, fc = p.d.flow_channels;
     memset(out, 0, sizeof(float) * p.total);
     auto one = [&](int id, int ti) {
