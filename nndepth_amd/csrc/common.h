@@ -183,15 +183,17 @@ struct ConvIO {
     bool dst_tiled = false;  // ... out0/out1/aux0/aux1/bmap
     bool src_c4 = false;     // tile-major with 4 channels interleaved (layout.h); channel counts / slice starts % 4 == 0
     bool dst_c4 = false;
-    // > 0: only output channels [0, cout_need) are wanted.  The launch keeps the tile configuration picked for the whole layer
-    // (P, split-K, per-wave K order: the same bits in those channels) and drops the waves of the other output-channel blocks
-    // (fewer per workgroup, same grid rows) where the kernel's staging plan allows it, else the rows that hold none of the wanted
-    // blocks; with one row and no such staging plan it runs the whole layer.
+    // > 0: only output channels [0, cout_need) are wanted: the same bits in those channels, from fewer waves or grid rows where
+    // the kernel's staging plan allows it (conv_launch.h: conv_restrict_cout)
     int cout_need = 0;
     // > 0: split-K factor forced for this launch (the picker then chooses among the shapes with this ks).  ks = 1 keeps every output
     // the same K order whatever the batch / map size (repvit.hip: a pair's outputs do not depend on the batch it runs in).
     int force_ks = 0;
 };
+
+// the kernel shapes both convolution kernels are instantiated for (their dispatch chains: conv_mfma.hip launch_conv,
+// conv_split_kernel.h launch_split_ns)
+static inline bool conv_shape_built(int KH, int KW) { return (KH == 1 && (KW == 1 || KW == 5)) || (KW == 1 && KH == 5) || (KH == 3 && KW == 3); }
 
 // input channels per K-chunk for a layer shape (host packer and kernels must agree)
 int conv_ci_t(int KH, int KW, int Cin, int stride = 1, int Cout = 0);

@@ -23,9 +23,7 @@
 //
 // Replaces the nn.Conv2d calls of nndepth/blocks/update_block.py:57-65,26-36,97-112 and
 // nndepth/blocks/gru.py:22-37,53-61 (reference files; semantics restated in oracle/torch_ref.py).
-#include "common.h"
-#include "conv_epilogue.h"
-#include "layout.h"
+#include "conv_launch.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -445,15 +443,19 @@ __global__ void __launch_bounds__(256) conv1x1_stream_kernel(ConvArgs a, int nti
 }
 
 template <int NQ>
-static void launch_conv1x1_stream(const ConvArgs& a, int ntiles, int ncb, int KQ, int B, hipStream_t stream) {
+static void launch_conv1x1_stream(const ConvArgs& a, dim3 grid, int ntiles, int ncb, int KQ, hipStream_t stream) {
     // one sub-tile per wave: two per wave (weight fragments amortised, 172 VGPRs) measured 110 vs 45 us on the 64 -> 64 shortcut
-    hipLaunchKernelGGL((conv1x1_stream_kernel<NQ, 1>), dim3((unsigned)cdiv64((long)ncb * ntiles, 4), 1, B), dim3(256), 0, stream, a, ntiles, ncb, KQ);
+    hipLaunchKernelGGL((conv1x1_stream_kernel<NQ, 1>), grid, dim3(256), 0, stream, a, ntiles, ncb, KQ);
 }
 
 // --------------------------------------------------------------------------- host side
+// the plan of one launch (plan_tile): the picked shape, then what the launch is made of
 struct TileCfg {
     int P, wco, ks, tiles_x, tiles_y, npos, ngroups, ne;
     size_t lds;
+    bool restricted;  // ConvIO::cout_need shrank the workgroups or the grid rows
+    bool stream1x1;   // the streaming 1x1 kernel takes the launch (the shape above is then unused but for the tile counts)
+    dim3 grid, block;
 };
 
 // Chooses the pixel sub-tile shape (SR x SC), P sub-tiles per wave and wco x ks waves per workgroup.
@@ -520,141 +522,112 @@ static bool pick_tile(const ConvLayer& L, int c0, int c1, int B, int H, int W, T
 }
 
 template <int KH, int KW, int CI_T, int P, int NE, int STR = 1>
-static int launch_one(const ConvArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+static int launch_one(const ConvArgs& a, const TileCfg& cfg, hipStream_t stream) {
     auto kern = conv_mfma_kernel<KH, KW, CI_T, P, NE, STR>;
-    if (lds > 64 * 1024) {
+    if (cfg.lds > 64 * 1024) {
         static std::atomic<unsigned> raised{0};
         if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), raised)) return rc;
     }
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
+    hipLaunchKernelGGL(kern, cfg.grid, cfg.block, cfg.lds, stream, a);
     return NND_OK;
 }
 
 template <int KH, int KW, int CI_T>
-static int launch_shape(const ConvArgs& a, const TileCfg& cfg, dim3 grid, dim3 block, hipStream_t stream) {
-    if (cfg.ne <= 8) return launch_one<KH, KW, CI_T, 1, 8>(a, grid, block, cfg.lds, stream);
-    return launch_one<KH, KW, CI_T, 1, 16>(a, grid, block, cfg.lds, stream);
+static int launch_shape(const ConvArgs& a, const TileCfg& cfg, hipStream_t stream) {
+    return cfg.ne <= 8 ? launch_one<KH, KW, CI_T, 1, 8>(a, cfg, stream) : launch_one<KH, KW, CI_T, 1, 16>(a, cfg, stream);
 }
 
-int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W,
-                hipStream_t stream) {
+// The plan of one launch: the picked shape, the streaming-1x1 choice, the restriction to the wanted output channels and the grid.
+// Reads switches(); no HIP call.
+static bool plan_tile(const ConvLayer& L, const ConvIO& io, int epi, int B, int H, int W, TileCfg* cfg) {
+    if (!pick_tile(L, io.src0.C, io.src1.C, B, H, W, cfg, io.force_ks)) return false;
+    // the streaming 1x1 kernel: tile-major sources, planar or 4-channel-interleaved (then Cout % 4 == 0 for a c4 destination)
+    cfg->stream1x1 = !switches().no_conv1x1_stream && L.KH == 1 && L.KW == 1 && L.stride == 1 && io.src1.C == 0 && io.src_tiled &&
+                     (!io.dst_c4 || L.Cout % 4 == 0) && !io.bmap.ptr && (L.Cin == 64 || L.Cin == 96 || L.Cin == 128) &&
+                     (epi == EPI_LINEAR || epi == EPI_RELU || epi == EPI_SCALE || epi == EPI_AFFINE);
+    if (cfg->stream1x1) {
+        cfg->grid = dim3((unsigned)cdiv64((long)L.ncb * cfg->tiles_x * cfg->tiles_y, 4), 1, B), cfg->block = dim3(256);
+        return true;
+    }
+    // ConvIO::cout_need (conv_launch.h conv_restrict_cout): a row may keep fewer output-channel waves if those still cover the patch
+    // (npos <= threads, at most 16 channels per staging thread)
+    auto groups = [&](int wco) { return 64 * wco * cfg->ks / cfg->npos; };
+    int ny = cdiv(L.ncb, cfg->wco);
+    cfg->restricted = conv_restrict_cout(L, io.cout_need, &ny, &cfg->wco,
+                                         [&](int wco) { return groups(wco) > 0 && cdiv(cfg->ks * L.CI_T, groups(wco)) <= 16; });
+    cfg->ngroups = groups(cfg->wco), cfg->ne = cdiv(cfg->ks * L.CI_T, cfg->ngroups);
+    cfg->grid = dim3(cfg->tiles_x * cfg->tiles_y, ny, B), cfg->block = dim3(64 * cfg->wco * cfg->ks);
+    return true;
+}
+
+// LDS sizing rule, re-derived independently of pick_tile (DESIGN.md §4 "staging bounds"): two patch buffers of
+// ks*CI_T channels + the spare word that swallows the stores of non-staging threads, and — aliasing them after the
+// last barrier — one 32x32 partial tile per wave for the split-K exchange; every staging thread needs a slot.
+static int check_tile_plan(const ConvLayer& L, const TileCfg& cfg) {
+    const int SR_ = 32 / NND_SC, st = L.stride;
+    const int PR_ = (SR_ - 1) * st + L.KH, PC_ = (cfg.P * NND_SC - 1) * st + L.KW;
+    const size_t patch = (size_t)st * st * ((PR_ + st - 1) / st) * patch_stride((PC_ + st - 1) / st, NND_SC);
+    NND_REQUIRE(cfg.lds >= ((size_t)2 * cfg.ks * L.CI_T * patch + 1) * sizeof(float) &&
+                    (cfg.ks == 1 || cfg.lds >= (size_t)cfg.wco * cfg.ks * cfg.P * 1024 * sizeof(float)) && cfg.lds <= 160 * 1024,
+                "conv: LDS plan %zu B does not cover the patch buffers / split-K tiles", cfg.lds);
+    NND_REQUIRE(cfg.npos == PR_ * PC_ && cfg.npos * cfg.ngroups <= 64 * cfg.wco * cfg.ks && cfg.ngroups * cfg.ne >= cfg.ks * L.CI_T && cfg.ne <= 16,
+                "conv: staging plan (%d positions x %d groups x %d) does not cover %d channels", cfg.npos, cfg.ngroups, cfg.ne, cfg.ks * L.CI_T);
+    return NND_OK;
+}
+
+static void print_tile_plan(const ConvLayer& L, const ConvIO& io, const TileCfg& cfg) {  // NND_CONV_VERBOSE (tests/test_gpu_conv_configs.py parses it)
+    if (cfg.stream1x1)
+        fprintf(stderr, "[nnd] conv1x1_stream Cin=%d Cout=%d CI_T=%d: grid %ux1x%d%s\n", L.Cin, L.Cout, L.CI_T, cfg.grid.x, (int)cfg.grid.z,
+                io.dst_c4 ? ", c4 destination" : "");
+    else
+        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B%s%s\n",
+                L.KH, L.KW, L.Cin, L.Cout, L.CI_T, cfg.P, cfg.wco, cfg.ks, cfg.ne, cfg.grid.x, cfg.grid.y, cfg.grid.z, cfg.lds,
+                io.cout_need > 0 ? (cfg.restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
+                L.stride == 2 ? ", stride 2" : "");
+}
+
+// check -> plan -> fill args -> verbose -> dispatch
+int launch_conv(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W, hipStream_t stream) {
     if (L.arith != 0) {
         NND_REQUIRE(epi != EPI_GELU && epi != EPI_HSWISH, "conv: EPI_GELU / EPI_HSWISH are built on the exact fp32 kernel only");
         return launch_conv_split(L, blob, io, epi, B, H, W, stream);
     }
-    NND_REQUIRE(io.src0.C + io.src1.C == L.Cin, "conv: source channels %d+%d != Cin %d", io.src0.C, io.src1.C, L.Cin);
+    int rc, Hin, Win;
+    NND_TRY(conv_check_io("conv", L, io, epi, H, W, &Hin, &Win));
     NND_REQUIRE(io.src1.C == 0 || io.src0.C % L.CI_T == 0, "conv: first source (%d ch) must be a multiple of %d", io.src0.C, L.CI_T);
-    const int Hin = io.Hin > 0 ? io.Hin : H, Win = io.Win > 0 ? io.Win : W;
-    NND_REQUIRE(L.stride == 1 || L.stride == 2, "conv: stride %d not supported", L.stride);
-    NND_REQUIRE(H == (Hin + L.stride - 1) / L.stride && W == (Win + L.stride - 1) / L.stride,
-                "conv: output %dx%d does not match input %dx%d at stride %d", H, W, Hin, Win, L.stride);
+    NND_REQUIRE(!io.src_c4 || L.stride == 1, "conv: c4 sources need stride 1");
     NND_REQUIRE((long)(L.Cin + 2 * L.CI_T) * tiled_plane(Hin, Win) < (1L << 31), "conv: plane offsets exceed 32 bits");
-    TileCfg cfg;
     NND_REQUIRE((epi != EPI_GELU && epi != EPI_HSWISH) || (!io.dst_c4 && !io.out1.ptr && !io.bmap.ptr),
                 "conv: EPI_GELU / EPI_HSWISH are built for a planar out0 only");
-    NND_REQUIRE(pick_tile(L, io.src0.C, io.src1.C, B, H, W, &cfg, io.force_ks),
+    TileCfg cfg;
+    NND_REQUIRE(plan_tile(L, io, epi, B, H, W, &cfg),
                 "conv: no tile configuration for %dx%d Cin=%d Cout=%d stride %d (NND_CONV_CFG p=%d ks=%d wco=%d, layer ks=%d)", L.KH, L.KW,
                 L.Cin, L.Cout, L.stride, switches().conv_p, switches().conv_ks, switches().conv_wco, io.force_ks);
-    {   // LDS sizing rule, re-derived independently of pick_tile (DESIGN.md §4 "staging bounds"): two patch buffers of
-        // ks*CI_T channels + the spare word that swallows the stores of non-staging threads, and — aliasing them after the
-        // last barrier — one 32x32 partial tile per wave for the split-K exchange; every staging thread needs a slot.
-        const int SR_ = 32 / NND_SC, st = L.stride;
-        const int PR_ = (SR_ - 1) * st + L.KH, PC_ = (cfg.P * NND_SC - 1) * st + L.KW;
-        const size_t patch = (size_t)st * st * ((PR_ + st - 1) / st) * patch_stride((PC_ + st - 1) / st, NND_SC);
-        NND_REQUIRE(cfg.lds >= ((size_t)2 * cfg.ks * L.CI_T * patch + 1) * sizeof(float) &&
-                        (cfg.ks == 1 || cfg.lds >= (size_t)cfg.wco * cfg.ks * cfg.P * 1024 * sizeof(float)) &&
-                        cfg.lds <= 160 * 1024,
-                    "conv: LDS plan %zu B does not cover the patch buffers / split-K tiles", cfg.lds);
-        NND_REQUIRE(cfg.npos == PR_ * PC_ && cfg.npos * cfg.ngroups <= 64 * cfg.wco * cfg.ks &&
-                        cfg.ngroups * cfg.ne >= cfg.ks * L.CI_T && cfg.ne <= 16,
-                    "conv: staging plan (%d positions x %d groups x %d) does not cover %d channels", cfg.npos, cfg.ngroups,
-                    cfg.ne, cfg.ks * L.CI_T);
-    }
+    NND_TRY(check_tile_plan(L, cfg));
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = io.src0.ptr; a.bs0 = io.src0.bstride; a.c0 = io.src0.C;
-    a.src1 = io.src1.ptr; a.bs1 = io.src1.bstride; a.c1 = io.src1.C;
-    a.wpk = blob + L.w_off;
-    a.bias = blob + L.b_off;
-    a.out0 = io.out0.ptr; a.obs0 = io.out0.bstride;
-    a.out1 = io.out1.ptr; a.obs1 = io.out1.bstride;
-    a.aux0 = io.aux0.ptr; a.abs0 = io.aux0.bstride;
-    a.aux1 = io.aux1.ptr; a.abs1 = io.aux1.bstride;
-    a.bmap = io.bmap.ptr; a.bmbs = io.bmap.bstride;
-    a.ls = make_lay(Hin, Win, io.src_tiled, io.src_c4);
-    a.ld = make_lay(H, W, io.dst_tiled, io.dst_c4);
-    NND_REQUIRE(!io.src_c4 || (io.src_tiled && L.stride == 1 && io.src0.C % 4 == 0 && io.src1.C % 4 == 0),
-                "conv: c4 sources need stride 1 and channel counts %% 4 == 0");
-    // the streaming 1x1 kernel: tile-major sources, planar or 4-channel-interleaved (then Cout % 4 == 0 for a c4 destination)
-    NND_REQUIRE(!io.dst_c4 || (io.dst_tiled && (L.Cout % 4 == 0 || (!io.bmap.ptr && !io.aux0.ptr && !io.aux1.ptr && !io.out1.ptr))),
-                "conv: c4 destination with per-pixel operands needs Cout %% 4 == 0");
-    a.H = H; a.W = W; a.Cout = L.Cout; a.nchunks = L.nchunks; a.epi = epi; a.hidden = io.hidden;
-    a.Hin = Hin; a.Win = Win; a.flags = io.flags;
-    a.cscale = L.s_off >= 0 ? blob + L.s_off : nullptr;
-    NND_REQUIRE(epi != EPI_AFFINE || a.cscale, "conv: EPI_AFFINE needs a packed scale vector");
-    a.tiles_x = cfg.tiles_x; a.wco = cfg.wco; a.ks = cfg.ks;
-    a.npos = cfg.npos; a.ngroups = cfg.ngroups;
-    a.scale = io.scale;
-    const bool no_stream = switches().no_conv1x1_stream;
-    if (!no_stream && L.KH == 1 && L.KW == 1 && L.stride == 1 && io.src1.C == 0 && io.src_tiled && (!io.dst_c4 || L.Cout % 4 == 0) && !io.bmap.ptr &&
-        (L.Cin == 64 || L.Cin == 96 || L.Cin == 128) &&
-        (epi == EPI_LINEAR || epi == EPI_RELU || epi == EPI_SCALE || epi == EPI_AFFINE)) {
-        const int ntiles = cfg.tiles_x * cfg.tiles_y, KQ = L.nchunks * L.CI_T / 8;
-        if (switches().conv_verbose)
-            fprintf(stderr, "[nnd] conv1x1_stream Cin=%d Cout=%d CI_T=%d: grid %ux1x%d%s\n", L.Cin, L.Cout, L.CI_T,
-                    (unsigned)cdiv64((long)L.ncb * ntiles, 4), B, io.dst_c4 ? ", c4 destination" : "");
-        if (L.Cin == 64) launch_conv1x1_stream<8>(a, ntiles, L.ncb, KQ, B, stream);
-        else if (L.Cin == 96) launch_conv1x1_stream<12>(a, ntiles, L.ncb, KQ, B, stream);
-        else launch_conv1x1_stream<16>(a, ntiles, L.ncb, KQ, B, stream);
-        NND_LAUNCH_CHECK();
-        return NND_OK;
-    }
-    int ny = cdiv(L.ncb, cfg.wco);
-    // ConvIO::cout_need: only output-channel blocks [0, nb) are wanted.  The picked shape stays (P, ks, CI_T: the same K chunks and
-    // partial-tile sums for every wave that remains); as in conv_split.hip (restrict_split), each row keeps wco = ceil(nb / ny) of
-    // its output-channel waves if the fewer threads still cover the patch (npos <= threads, at most 16 channels per staging thread),
-    // else the rows without a wanted block are dropped; with one row and no such staging plan the whole layer runs.
-    bool restricted = false;
-    if (io.cout_need > 0 && cdiv(io.cout_need, 32) < L.ncb) {
-        const int nb = cdiv(io.cout_need, 32), wco = cdiv(nb, ny);
-        const int nthreads = 64 * wco * cfg.ks;
-        const int ngroups = nthreads / cfg.npos;
-        const int ne = ngroups > 0 ? cdiv(cfg.ks * L.CI_T, ngroups) : 1 << 20;
-        if (wco < cfg.wco && ne <= 16) {
-            cfg.wco = wco;
-            cfg.ngroups = ngroups;
-            cfg.ne = ne;
-            a.wco = wco;
-            a.ngroups = ngroups;
-            ny = cdiv(nb, wco);
-            restricted = true;
-        } else if (cdiv(nb, cfg.wco) < ny) {
-            ny = cdiv(nb, cfg.wco);
-            restricted = true;
-        }
-    }
-    dim3 grid(cfg.tiles_x * cfg.tiles_y, ny, B), block(64 * cfg.wco * cfg.ks);
-    const bool verbose = switches().conv_verbose;
-    if (verbose)
-        fprintf(stderr, "[nnd] conv %dx%d Cin=%d Cout=%d CI_T=%d: P=%d, wco=%d, ks=%d, ne=%d, grid %ux%ux%u, lds %zu B%s%s\n",
-                L.KH, L.KW, L.Cin, L.Cout, L.CI_T, cfg.P, cfg.wco, cfg.ks, cfg.ne, grid.x, grid.y, grid.z, cfg.lds,
-                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
-                L.stride == 2 ? ", stride 2" : "");
-    int rc = NND_ERR_UNSUPPORTED;
-    if (L.stride == 2) {
-        if (L.KH == 3 && L.KW == 3 && L.CI_T == 16) rc = launch_one<3, 3, 16, 1, 16, 2>(a, grid, block, cfg.lds, stream);
-        else if (L.KH == 1 && L.KW == 1 && L.CI_T == 16) rc = launch_one<1, 1, 16, 1, 16, 2>(a, grid, block, cfg.lds, stream);
-        else set_error("conv %dx%d stride 2 CI_T=%d not instantiated", L.KH, L.KW, L.CI_T);
-    } else
-    if (L.KH == 1 && L.KW == 1 && L.CI_T == 128) rc = launch_shape<1, 1, 128>(a, cfg, grid, block, stream);
-    else if (L.KH == 1 && L.KW == 1 && L.CI_T == 32) rc = launch_shape<1, 1, 32>(a, cfg, grid, block, stream);
-    else if (L.KH == 3 && L.KW == 3 && L.CI_T == 32) rc = launch_shape<3, 3, 32>(a, cfg, grid, block, stream);
-    else if (L.KH == 3 && L.KW == 3 && L.CI_T == 16) rc = launch_shape<3, 3, 16>(a, cfg, grid, block, stream);
-    else if (L.KH == 1 && L.KW == 5 && L.CI_T == 32) rc = launch_shape<1, 5, 32>(a, cfg, grid, block, stream);
-    else if (L.KH == 5 && L.KW == 1 && L.CI_T == 32) rc = launch_shape<5, 1, 32>(a, cfg, grid, block, stream);
-    else if (L.KH == 1 && L.KW == 5 && L.CI_T == 64) rc = launch_shape<1, 5, 64>(a, cfg, grid, block, stream);
-    else if (L.KH == 5 && L.KW == 1 && L.CI_T == 64) rc = launch_shape<5, 1, 64>(a, cfg, grid, block, stream);
-    else set_error("conv %dx%d CI_T=%d not instantiated", L.KH, L.KW, L.CI_T);
+    conv_fill_args(L, blob, io, epi, H, W, Hin, Win, &a);
+    a.tiles_x = cfg.tiles_x; a.wco = cfg.wco; a.ks = cfg.ks; a.npos = cfg.npos; a.ngroups = cfg.ngroups;
+    if (switches().conv_verbose) print_tile_plan(L, io, cfg);
+    const int ntiles = cfg.tiles_x * cfg.tiles_y, KQ = L.nchunks * L.CI_T / 8, KH = L.KH, KW = L.KW, CI_T = L.CI_T;
+    rc = NND_ERR_UNSUPPORTED;
+    if (cfg.stream1x1) {
+        rc = NND_OK;
+        if (L.Cin == 64) launch_conv1x1_stream<8>(a, cfg.grid, ntiles, L.ncb, KQ, stream);
+        else if (L.Cin == 96) launch_conv1x1_stream<12>(a, cfg.grid, ntiles, L.ncb, KQ, stream);
+        else launch_conv1x1_stream<16>(a, cfg.grid, ntiles, L.ncb, KQ, stream);
+    } else if (L.stride == 2) {
+        if (KH == 3 && KW == 3 && CI_T == 16) rc = launch_one<3, 3, 16, 1, 16, 2>(a, cfg, stream);
+        else if (KH == 1 && KW == 1 && CI_T == 16) rc = launch_one<1, 1, 16, 1, 16, 2>(a, cfg, stream);
+        else set_error("conv %dx%d stride 2 CI_T=%d not instantiated", KH, KW, CI_T);
+    } else if (KH == 1 && KW == 1 && CI_T == 128) rc = launch_shape<1, 1, 128>(a, cfg, stream);
+    else if (KH == 1 && KW == 1 && CI_T == 32) rc = launch_shape<1, 1, 32>(a, cfg, stream);
+    else if (KH == 3 && KW == 3 && CI_T == 32) rc = launch_shape<3, 3, 32>(a, cfg, stream);
+    else if (KH == 3 && KW == 3 && CI_T == 16) rc = launch_shape<3, 3, 16>(a, cfg, stream);
+    else if (KH == 1 && KW == 5 && CI_T == 32) rc = launch_shape<1, 5, 32>(a, cfg, stream);
+    else if (KH == 5 && KW == 1 && CI_T == 32) rc = launch_shape<5, 1, 32>(a, cfg, stream);
+    else if (KH == 1 && KW == 5 && CI_T == 64) rc = launch_shape<1, 5, 64>(a, cfg, stream);
+    else if (KH == 5 && KW == 1 && CI_T == 64) rc = launch_shape<5, 1, 64>(a, cfg, stream);
+    else set_error("conv %dx%d CI_T=%d not instantiated", KH, KW, CI_T);
     if (rc != NND_OK) return rc;
     NND_LAUNCH_CHECK();
     return NND_OK;

@@ -26,6 +26,7 @@
 //
 // Replaces (when selected) the same nn.Conv2d calls as conv_mfma.hip: nndepth/blocks/update_block.py:57-65,26-36,97-112,
 // nndepth/blocks/gru.py:22-37,53-61.
+#include "conv_launch.h"
 #include "conv_split_kernel.h"
 #include "flow_branch.h"
 
@@ -70,13 +71,10 @@ float bf16_to_f(uint16_t h) {
 // at 68x120 the 12-wave shapes of round 2 (3 x 2, 4 x 2, 6 x 2 blocks x sub-tiles) become 2 x 3, 2 x 4, 4 x 3.
 bool pick_split(const ConvLayer& L, int c0, int c1, int B, int H, int W, bool fast_ok, SplitCfg* out) {
     const int NS = L.arith, STR = L.stride;
-    // patch geometry of one sub-tile (SplitGeom in conv_split_kernel.h): positions staged and bytes in LDS
-    const int PRI = 3 * STR + L.KH, PCI = 7 * STR + L.KW, k11 = L.KH * L.KW == 1;
-    const int nph = STR == 1 ? 1 : (k11 ? 1 : 4);
-    const int prp = STR == 1 ? PRI : (L.KH == 1 ? 4 : (PRI + 1) / 2), pcp = STR == 1 ? PCI : (L.KW == 1 ? 8 : (PCI + 1) / 2);
-    const int npos = (STR == 2 && k11) ? 32 : PRI * PCI;
-    const size_t subb = (size_t)nph * prp * split_row_bytes(pcp, NS);
-    const int tiles_x = cdiv(W, 8), ntiles = tiles_x * cdiv(H, 4);
+    // patch geometry of one sub-tile (the kernel's own: split_patch in conv_split_kernel.h): positions staged and bytes in LDS
+    const int npos = split_patch(L.KH, L.KW, NS, STR).NPOS;
+    const size_t subb = split_patch(L.KH, L.KW, NS, STR).SUBB;
+    int tiles_x, ntiles = split_tiles(H, W, &tiles_x);
     int force_ny = switches().split_ny, force_ks = switches().split_ks, force_p = switches().split_p;
     const bool forced = force_ny > 0 || force_ks > 0 || force_p > 0;
     const long px_wgs2 = (long)cdiv(ntiles, 2) * B;
@@ -134,7 +132,7 @@ bool pick_split(const ConvLayer& L, int c0, int c1, int B, int H, int W, bool fa
                                           // 2-wave workgroups: 64 -> 64 at 272x480x2 takes 178 us with P = 4 against 111 with P = 2,
                                           // profiles/r03_split_encoder_shapes.txt)
                     if (STR == 2 && !fast) continue;  // the stride-2 kernels exist in the FAST regime only
-                    const int nu = cdiv(P * npos * 2 * ks, 64 * waves);  // staging units per thread
+                    const int nu = split_staging_units(P, npos, ks, waves);  // per thread
                     if (nu > 4 || (P == 3 && nu > 3)) continue;
                     size_t lds = (size_t)2 * ks * P * subb;
                     const size_t red = ks > 1 ? (size_t)waves * P * 4096 : 0;
@@ -153,7 +151,7 @@ bool pick_split(const ConvLayer& L, int c0, int c1, int B, int H, int W, bool fa
                     if (nu > 2 && P == 2) t *= 1.2;                // register-heavy staging variant
                     if (t < best) {
                         best = t;
-                        *out = {ny, wco, ks, P, ntiles, tiles_x, P == 2 ? (nu <= 2 ? 2 : 4) : (nu <= 3 ? 3 : 4), fast, lds, STR};
+                        *out = {ny, wco, ks, P, ntiles, tiles_x, split_nu_variant(nu), fast, lds, STR};  // (P == 2 here)
                         found = true;
                     }
                 }
@@ -166,92 +164,66 @@ bool pick_split(const ConvLayer& L, int c0, int c1, int B, int H, int W, bool fa
     return rule && search(-1, -1, -1);  // the regime rule's shape does not exist for this layer: the cost model decides
 }
 
-// ConvIO::cout_need: only output-channel blocks [0, nb) are wanted.  The shape picked for the whole layer stays (P, ks, the K chunks
-// of wave (cbi, kj) and the order the ks partial tiles are summed in), so those channels get the same bits.  The workgroups keep
-// their pixels and the grid its rows where it can: each row keeps wco = ceil(nb / ny) of its output-channel waves (one row: the
-// waves of the unwanted blocks are dropped), if the fewer threads still stage the patch with an instantiated number of staging
-// units (nu <= 4).  Otherwise the rows without a wanted block are dropped; with one row and no such variant the whole layer runs
-// (returns false).  (Dropping rows alone does not make the launch shorter where the whole layer is one workgroup per CU or fewer:
-// each workgroup takes as long as before — RAFT-Stereo at 544x960, flow_head.conv1+mask.0: 2 rows of 128 workgroups of 12 waves,
-// one row 23.7 us against 23.5 for both.)
+// ConvIO::cout_need (conv_launch.h): a row may keep fewer output-channel waves if they still stage the patch with an instantiated NU (nu <= 4)
 bool restrict_split(const ConvLayer& L, int cout_need, SplitCfg* cfg) {
-    const int nb = cdiv(cout_need, 32);
-    if (cout_need <= 0 || nb >= L.ncb) return false;
-    const int wco = cdiv(nb, cfg->ny);
-    const int STR = L.stride, PRI = 3 * STR + L.KH, PCI = 7 * STR + L.KW;
-    const int npos = (STR == 2 && L.KH * L.KW == 1) ? 32 : PRI * PCI;
-    const int nu = cdiv(cfg->P * npos * 2 * cfg->ks, 64 * wco * cfg->ks);
-    if (cfg->P == 2 && nu <= 4 && wco < cfg->wco) {
-        cfg->wco = wco;
-        cfg->ny = cdiv(nb, wco);
-        cfg->nu = nu <= 2 ? 2 : 4;
-        return true;
-    }
-    const int ny = cdiv(nb, cfg->wco);
-    if (ny >= cfg->ny) return false;
-    cfg->ny = ny;
+    const int npos = split_patch(L.KH, L.KW, L.arith, L.stride).NPOS;
+    auto units = [&](int wco) { return split_staging_units(cfg->P, npos, cfg->ks, wco * cfg->ks); };
+    if (!conv_restrict_cout(L, cout_need, &cfg->ny, &cfg->wco, [&](int wco) { return cfg->P == 2 && units(wco) <= 4; })) return false;
+    cfg->nu = split_nu_variant(units(cfg->wco));
     return true;
+}
+
+// The plan of one launch: the picked shape, restricted to the wanted output channels, and its grid.  Reads switches(); no HIP call.
+// FAST regime: any source layout the kernel addresses as plane + pixel offset — c4 tile-major (the refinement loops' own
+// tensors), planar tile-major (the encoder's) or NCHW (C-ABI tensors: cnet_proj reads the feature map, the Conv3d layers
+// their depth-major volumes); per candidate shape the picker also requires full super-chunks that never straddle the two
+// sources.  NND_SPLIT_NO_FAST (diagnostic) keeps the generic kernel.
+// (the stride-2 kernels exist in the FAST regime only: the diagnostic switch does not apply to them)
+bool split_fast_ok(const ConvLayer& L) { return !switches().split_no_fast || L.stride == 2; }
+bool plan_split(const ConvLayer& L, const ConvIO& io, int B, int H, int W, SplitCfg* cfg) {
+    if (!pick_split(L, io.src0.C, io.src1.C, B, H, W, split_fast_ok(L), cfg)) return false;
+    cfg->restricted = restrict_split(L, io.cout_need, cfg);
+    cfg->grid = dim3(cdiv(cfg->ntiles, cfg->P), cfg->ny, B), cfg->block = dim3(64 * cfg->wco * cfg->ks);
+    return true;
+}
+
+void print_split_plan(const ConvLayer& L, const ConvIO& io, const SplitCfg& cfg) {  // NND_CONV_VERBOSE (tests/test_gpu_conv_configs.py parses it)
+    fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B%s%s\n", L.KH,
+            L.KW, L.Cin, L.Cout, L.arith, cfg.ny, cfg.wco, cfg.ks, cfg.P, cfg.nu, cfg.fast ? ", fast" : "", cfg.grid.x, cfg.grid.y, cfg.grid.z, cfg.lds,
+            io.cout_need > 0 ? (cfg.restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
+            L.stride == 2 ? ", stride 2" : "");
 }
 }  // namespace
 
 // the kernel instantiations live in conv_split_ns2.hip / conv_split_ns3.hip
-template <>
-int launch_split_ns<2>(const ConvArgs& a, const SplitCfg& cfg, int KH, int KW, dim3 grid, dim3 block, hipStream_t stream);
-template <>
-int launch_split_ns<3>(const ConvArgs& a, const SplitCfg& cfg, int KH, int KW, dim3 grid, dim3 block, hipStream_t stream);
+extern template int launch_split_ns<2>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
+extern template int launch_split_ns<3>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 
 bool conv_split_supported(int KH, int KW, int Cin, int stride, int arith, int Cout) {
     if ((arith != 3 && arith != 2) || (stride != 1 && stride != 2) || Cin % 16 != 0) return false;
     // stride 2: planar sources only (checked at launch), and at least 3 output-channel blocks: the 9 x 17-position patch of a
     // sub-tile is staged by the workgroup's output-channel waves, fewer of them would need more than 4 staging units per thread
     if (stride == 2) return ((KH == 3 && KW == 3) || (KH == 1 && KW == 1)) && Cout >= 96;
-    return (KH == 3 && KW == 3) || (KH == 1 && KW == 5) || (KH == 5 && KW == 1) || (KH == 1 && KW == 1);
+    return conv_shape_built(KH, KW);
 }
 
+// check -> plan -> fill args -> calibrate -> verbose -> dispatch
 int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W, hipStream_t stream) {
+    int rc, Hin, Win;
     NND_REQUIRE(conv_split_supported(L.KH, L.KW, L.Cin, L.stride, L.arith, L.Cout), "conv_split: %dx%d Cin=%d Cout=%d stride %d arith %d not built",
                 L.KH, L.KW, L.Cin, L.Cout, L.stride, L.arith);
-    NND_REQUIRE(io.src0.C + io.src1.C == L.Cin, "conv_split: source channels %d+%d != Cin %d", io.src0.C, io.src1.C, L.Cin);
+    NND_TRY(conv_check_io("conv_split", L, io, epi, H, W, &Hin, &Win));
     NND_REQUIRE(L.CI_T == 16 && L.nchunks * 16 == L.Cin, "conv_split: layer was not planned for 16-channel chunks");
-    const int Hin = io.Hin > 0 ? io.Hin : H, Win = io.Win > 0 ? io.Win : W;  // input size (stride 2: the caller passes it)
-    NND_REQUIRE(L.stride == 1 ? (Hin == H && Win == W) : (H == (Hin + 1) / 2 && W == (Win + 1) / 2),
-                "conv_split: output %dx%d does not match input %dx%d at stride %d", H, W, Hin, Win, L.stride);
     NND_REQUIRE(L.stride == 1 || io.src1.C == 0, "conv_split: stride 2 is built for one source");
     NND_REQUIRE((long)(L.Cin + 64) * tiled_plane(Hin, Win) < (1L << 31), "conv_split: plane offsets exceed 32 bits");
     SplitCfg cfg;
-    // FAST regime: any source layout the kernel addresses as plane + pixel offset — c4 tile-major (the refinement loops' own
-    // tensors), planar tile-major (the encoder's) or NCHW (C-ABI tensors: cnet_proj reads the feature map, the Conv3d layers
-    // their depth-major volumes); per candidate shape the picker also requires full super-chunks that never straddle the two
-    // sources.  NND_SPLIT_NO_FAST (diagnostic) keeps the generic kernel.
-    // (the stride-2 kernels exist in the FAST regime only: the diagnostic switch does not apply to them)
-    const bool fast_ok = !switches().split_no_fast || L.stride == 2;
-    NND_REQUIRE(pick_split(L, io.src0.C, io.src1.C, B, H, W, fast_ok, &cfg),
+    NND_REQUIRE(plan_split(L, io, B, H, W, &cfg),
                 "conv_split: no configuration for %dx%d Cin=%d (%d+%d) Cout=%d stride %d (NND_SPLIT_CFG ny=%d ks=%d P=%d%s)", L.KH, L.KW,
                 L.Cin, io.src0.C, io.src1.C, L.Cout, L.stride, switches().split_ny, switches().split_ks, switches().split_p,
-                fast_ok ? "" : ", NND_SPLIT_NO_FAST");
-    const bool restricted = restrict_split(L, io.cout_need, &cfg);
+                split_fast_ok(L) ? "" : ", NND_SPLIT_NO_FAST");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = io.src0.ptr; a.bs0 = io.src0.bstride; a.c0 = io.src0.C;
-    a.src1 = io.src1.ptr; a.bs1 = io.src1.bstride; a.c1 = io.src1.C;
-    a.wpk = blob + L.w_off;
-    a.bias = blob + L.b_off;
-    a.out0 = io.out0.ptr; a.obs0 = io.out0.bstride;
-    a.out1 = io.out1.ptr; a.obs1 = io.out1.bstride;
-    a.aux0 = io.aux0.ptr; a.abs0 = io.aux0.bstride;
-    a.aux1 = io.aux1.ptr; a.abs1 = io.aux1.bstride;
-    a.bmap = io.bmap.ptr; a.bmbs = io.bmap.bstride;
-    a.ls = make_lay(Hin, Win, io.src_tiled, io.src_c4);
-    a.ld = make_lay(H, W, io.dst_tiled, io.dst_c4);
-    NND_REQUIRE(!io.src_c4 || (io.src_tiled && io.src0.C % 4 == 0 && io.src1.C % 4 == 0), "conv_split: c4 sources need channel counts %% 4 == 0");
-    NND_REQUIRE(!io.dst_c4 || (io.dst_tiled && (L.Cout % 4 == 0 || (!io.bmap.ptr && !io.aux0.ptr && !io.aux1.ptr && !io.out1.ptr))),
-                "conv_split: c4 destination with per-pixel operands needs Cout %% 4 == 0");
-    a.H = H; a.W = W; a.Cout = L.Cout; a.nchunks = L.nchunks; a.epi = epi; a.hidden = io.hidden;
-    a.Hin = Hin; a.Win = Win; a.flags = io.flags;
-    a.cscale = L.s_off >= 0 ? blob + L.s_off : nullptr;
-    NND_REQUIRE(epi != EPI_AFFINE || a.cscale, "conv_split: EPI_AFFINE needs a packed scale vector");
+    conv_fill_args(L, blob, io, epi, H, W, Hin, Win, &a);
     a.tiles_x = cfg.tiles_x; a.wco = cfg.wco; a.ks = cfg.ks; a.npos = cfg.ntiles;
-    a.scale = io.scale;
 #ifdef NND_DBG_STAMPS  // NND_DBG_STAMP_LAUNCH=n: only the n-th conv_split launch of the process records its stamps (default: every launch)
     {
         static std::atomic<int> launches{0};
@@ -260,22 +232,11 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
         a.dbg_stamp = only < 0 || idx == only;
     }
 #endif
-    if (calibrating() && L.arith == 2) {  // record the largest |activation| this launch stages (calib.hip)
-        const float* tail = blob + L.tail_off();
-        if (int rc = calib_amax_act(io.src0, a.ls, B, Hin, Win, tail, stream)) return rc;
-        if (int rc = calib_amax_act(io.src1, a.ls, B, Hin, Win, tail, stream)) return rc;
-    }
-    dim3 grid(cdiv(cfg.ntiles, cfg.P), cfg.ny, B), block(64 * cfg.wco * cfg.ks);
-    const bool verbose = switches().conv_verbose;
-    if (verbose)
-        fprintf(stderr, "[nnd] conv_split %dx%d Cin=%d Cout=%d pieces=%d: ny=%d, wco=%d, ks=%d, P=%d, nu=%d%s, grid %ux%ux%u, lds %zu B%s%s\n", L.KH,
-                L.KW, L.Cin, L.Cout, L.arith, cfg.ny, cfg.wco, cfg.ks, cfg.P, cfg.nu, cfg.fast ? ", fast" : "", grid.x, grid.y, grid.z, cfg.lds,
-                io.cout_need > 0 ? (restricted ? ", restricted to the wanted output channels" : ", whole layer (not restrictable)") : "",
-                L.stride == 2 ? ", stride 2" : "");
-    int rc = L.arith == 3 ? launch_split_ns<3>(a, cfg, L.KH, L.KW, grid, block, stream)
-                          : launch_split_ns<2>(a, cfg, L.KH, L.KW, grid, block, stream);
-    NND_REQUIRE(rc != NND_ERR_UNSUPPORTED, "conv_split: shape %dx%d P=%d nu=%d %s is not instantiated", L.KH, L.KW, cfg.P, cfg.nu,
-                cfg.fast ? "fast" : "generic");
+    if (calibrating() && L.arith == 2)  // record the largest |activation| this launch stages (calib.hip)
+        for (const Act* src : {&io.src0, &io.src1}) NND_TRY(calib_amax_act(*src, a.ls, B, Hin, Win, blob + L.tail_off(), stream));
+    if (switches().conv_verbose) print_split_plan(L, io, cfg);
+    rc = L.arith == 3 ? launch_split_ns<3>(a, cfg, L.KH, L.KW, stream) : launch_split_ns<2>(a, cfg, L.KH, L.KW, stream);
+    NND_REQUIRE(rc != NND_ERR_UNSUPPORTED, "conv_split: shape %dx%d P=%d nu=%d %s is not instantiated", L.KH, L.KW, cfg.P, cfg.nu, cfg.fast ? "fast" : "generic");
     if (rc != NND_OK) return rc;
     NND_LAUNCH_CHECK();
     return NND_OK;
@@ -381,8 +342,7 @@ int make_flow_branch_args(const ConvLayer& f2, const float* blob, const float* w
     a.c.out0 = io.out0.ptr; a.c.obs0 = io.out0.bstride;
     a.c.ld = make_lay(H, W, true, io.dst_c4);
     a.c.H = H; a.c.W = W; a.c.Hin = H; a.c.Win = W; a.c.Cout = f2.Cout; a.c.epi = EPI_RELU;
-    a.c.tiles_x = cdiv(W, 8);
-    a.c.npos = a.c.tiles_x * cdiv(H, 4);
+    a.c.npos = split_tiles(H, W, &a.c.tiles_x);
     a.c.scale = 1.f;
     return NND_OK;
 }

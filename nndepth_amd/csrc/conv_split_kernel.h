@@ -96,16 +96,29 @@ __device__ __forceinline__ void split_static_for(F&& f) {
     split_static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
-// LDS geometry of one sub-tile's patch (bytes): stride 1: PR x PC positions; stride 2: 4 phases (1 for a 1x1) of PRP x PCP
+// LDS geometry of one sub-tile's patch (bytes): stride 1: PR x PC positions; stride 2: 4 phases (1 for a 1x1) of PRP x PCP.
+// The one definition: the kernel reads it as SplitGeom<>, the host's picker and restriction (conv_split.hip) call it.
+struct SplitPatch {
+    int PRI, PCI, NPH, PRP, PCP, NPOS, PS, ROWB, PHB, SUBB;
+};
+__host__ __device__ constexpr SplitPatch split_patch(int KH, int KW, int NS, int STR) {
+    const int PRI = 3 * STR + KH, PCI = 7 * STR + KW;                 // input positions covered by a 4x8 output sub-tile
+    const int NPH = STR == 1 ? 1 : (KH * KW == 1 ? 1 : 4);            // parity phases stored
+    const int PRP = STR == 1 ? PRI : (KH == 1 ? 4 : (PRI + 1) / 2);   // rows / columns of a phase grid
+    const int PCP = STR == 1 ? PCI : (KW == 1 ? 8 : (PCI + 1) / 2);
+    const int NPOS = STR == 1 ? PRI * PCI : (KH * KW == 1 ? 32 : PRI * PCI);  // positions staged per sub-tile
+    const int ROWB = split_row_bytes(PCP, NS);
+    return {PRI, PCI, NPH, PRP, PCP, NPOS, split_pos_bytes(NS), ROWB, PRP * ROWB, NPH * PRP * ROWB};
+}
 template <int KH, int KW, int NS, int STR>
 struct SplitGeom {
-    static constexpr int PRI = 3 * STR + KH, PCI = 7 * STR + KW;                 // input positions covered by a 4x8 output sub-tile
-    static constexpr int NPH = STR == 1 ? 1 : (KH * KW == 1 ? 1 : 4);            // parity phases stored
-    static constexpr int PRP = STR == 1 ? PRI : (KH == 1 ? 4 : (PRI + 1) / 2);   // rows / columns of a phase grid
-    static constexpr int PCP = STR == 1 ? PCI : (KW == 1 ? 8 : (PCI + 1) / 2);
-    static constexpr int NPOS = STR == 1 ? PRI * PCI : (KH * KW == 1 ? 32 : PRI * PCI);  // positions staged per sub-tile
-    static constexpr int PS = split_pos_bytes(NS), ROWB = split_row_bytes(PCP, NS), PHB = PRP * ROWB, SUBB = NPH * PHB;
+    static constexpr SplitPatch G = split_patch(KH, KW, NS, STR);
+    static constexpr int PRI = G.PRI, PCI = G.PCI, NPH = G.NPH, PRP = G.PRP, PCP = G.PCP, NPOS = G.NPOS;
+    static constexpr int PS = G.PS, ROWB = G.ROWB, PHB = G.PHB, SUBB = G.SUBB;
 };
+// staging units (patch position x 8 channels) per thread of a workgroup of `waves` waves, and the instantiated NU that serves it
+__host__ __device__ constexpr int split_staging_units(int P, int npos, int ks, int waves) { return (P * npos * 2 * ks + 64 * waves - 1) / (64 * waves); }
+__host__ __device__ constexpr int split_nu_variant(int nu) { return nu <= 2 ? 2 : 4; }
 
 // Schedule of the PIPELINED walk (round 4, FAST regime, kernels with >= 5 taps): the staging of super-chunk K + 1 is cut into
 // micro-step slots that hang behind the MFMA groups of the units [U0, NUNIT - 2] of super-chunk K, SPU slots per unit; slot q
@@ -628,14 +641,20 @@ __global__ void __launch_bounds__(MAXT) conv_split_kernel(ConvArgs a) {
 }
 
 // --------------------------------------------------------------------------- host side shared by the instantiation units
+// the plan of one launch (conv_split.hip plan_split): the picked shape, then what the launch is made of
 struct SplitCfg {
     int ny, wco, ks, P, ntiles, tiles_x, nu;
     bool fast;
     size_t lds;
     int stride;
+    bool restricted;  // ConvIO::cout_need shrank the workgroups or the grid rows
+    dim3 grid, block;
 };
 
 constexpr int SPLIT_MAX_WAVES = 12;
+
+// 4x8-pixel sub-tiles of an H x W map (the kernels number them row-major, *tiles_x per row)
+inline int split_tiles(int H, int W, int* tiles_x) { return (*tiles_x = cdiv(W, 8)) * cdiv(H, 4); }
 
 template <int KH, int KW, int NS, int P, int NU, bool FAST, bool SRC4, int AD, int MAXT, int STR = 1>
 int launch_split_kernel(const ConvArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
@@ -668,46 +687,36 @@ constexpr int split_fast_ad() {
 // every instantiation of one (KH, KW, NS): generic and FAST (c4 / planar tile-major sources), P = 2, NU 2 | 4, 768 threads.
 // (P = 3 / 4 with 8 waves were measured at 68x120 and lose to P = 2 with 12 waves on every layer — profiles/r03_split_shape_sweep_68x120.txt
 //  — so they are not instantiated; the kernel template itself stays general in P.)
+template <int KH, int KW, int NS, bool FAST, bool SRC4, int STR>
+int launch_split_nu(const ConvArgs& a, const SplitCfg& cfg, hipStream_t stream) {
+    constexpr int AD = FAST ? split_fast_ad<KH, KW, NS>() : 1;
+    if (split_nu_variant(cfg.nu) == 2) return launch_split_kernel<KH, KW, NS, 2, 2, FAST, SRC4, AD, 768, STR>(a, cfg.grid, cfg.block, cfg.lds, stream);
+    return launch_split_kernel<KH, KW, NS, 2, 4, FAST, SRC4, AD, 768, STR>(a, cfg.grid, cfg.block, cfg.lds, stream);
+}
 template <int KH, int KW, int NS>
-int launch_split_shape(const ConvArgs& a, const SplitCfg& cfg, dim3 grid, dim3 block, hipStream_t stream) {
-    constexpr int FAD = split_fast_ad<KH, KW, NS>();
+int launch_split_shape(const ConvArgs& a, const SplitCfg& cfg, hipStream_t stream) {
     if (cfg.P != 2) return NND_ERR_UNSUPPORTED;
+    const bool src4 = a.ls.ci == 4;
     if (cfg.stride == 2) {  // FAST regime only; planar or 4-channel-interleaved (round 4: the encoder's tensors) sources
         if constexpr (KH * KW == 9 || KH * KW == 1) {
             if (!cfg.fast) return NND_ERR_UNSUPPORTED;
-            if (a.ls.ci == 4) {
-                if (cfg.nu <= 2) return launch_split_kernel<KH, KW, NS, 2, 2, true, true, FAD, 768, 2>(a, grid, block, cfg.lds, stream);
-                return launch_split_kernel<KH, KW, NS, 2, 4, true, true, FAD, 768, 2>(a, grid, block, cfg.lds, stream);
-            }
-            if (cfg.nu <= 2) return launch_split_kernel<KH, KW, NS, 2, 2, true, false, FAD, 768, 2>(a, grid, block, cfg.lds, stream);
-            return launch_split_kernel<KH, KW, NS, 2, 4, true, false, FAD, 768, 2>(a, grid, block, cfg.lds, stream);
+            return src4 ? launch_split_nu<KH, KW, NS, true, true, 2>(a, cfg, stream) : launch_split_nu<KH, KW, NS, true, false, 2>(a, cfg, stream);
         } else {
             return NND_ERR_UNSUPPORTED;
         }
     }
-    if (!cfg.fast) {
-        if (cfg.nu <= 2) return launch_split_kernel<KH, KW, NS, 2, 2, false, false, 1, 768>(a, grid, block, cfg.lds, stream);
-        return launch_split_kernel<KH, KW, NS, 2, 4, false, false, 1, 768>(a, grid, block, cfg.lds, stream);
-    }
-    if (a.ls.ci == 4) {
-        if (cfg.nu <= 2) return launch_split_kernel<KH, KW, NS, 2, 2, true, true, FAD, 768>(a, grid, block, cfg.lds, stream);
-        return launch_split_kernel<KH, KW, NS, 2, 4, true, true, FAD, 768>(a, grid, block, cfg.lds, stream);
-    }
-    if (cfg.nu <= 2) return launch_split_kernel<KH, KW, NS, 2, 2, true, false, FAD, 768>(a, grid, block, cfg.lds, stream);
-    return launch_split_kernel<KH, KW, NS, 2, 4, true, false, FAD, 768>(a, grid, block, cfg.lds, stream);
+    if (!cfg.fast) return launch_split_nu<KH, KW, NS, false, false, 1>(a, cfg, stream);
+    return src4 ? launch_split_nu<KH, KW, NS, true, true, 1>(a, cfg, stream) : launch_split_nu<KH, KW, NS, true, false, 1>(a, cfg, stream);
 }
 
+// instantiated explicitly, NS = 2 in conv_split_ns2.hip and NS = 3 in conv_split_ns3.hip (conv_split.hip declares them extern)
 template <int NS>
-int launch_split_ns(const ConvArgs& a, const SplitCfg& cfg, int KH, int KW, dim3 grid, dim3 block, hipStream_t stream);
-
-#define NND_SPLIT_DEFINE_NS(NS)                                                                                                      \
-    template <>                                                                                                                      \
-    int launch_split_ns<NS>(const ConvArgs& a, const SplitCfg& cfg, int KH, int KW, dim3 grid, dim3 block, hipStream_t stream) {     \
-        if (KH == 3 && KW == 3) return launch_split_shape<3, 3, NS>(a, cfg, grid, block, stream);                                    \
-        if (KH == 1 && KW == 5) return launch_split_shape<1, 5, NS>(a, cfg, grid, block, stream);                                    \
-        if (KH == 5 && KW == 1) return launch_split_shape<5, 1, NS>(a, cfg, grid, block, stream);                                    \
-        if (KH == 1 && KW == 1) return launch_split_shape<1, 1, NS>(a, cfg, grid, block, stream);                                    \
-        return NND_ERR_UNSUPPORTED;                                                                                                  \
-    }
+int launch_split_ns(const ConvArgs& a, const SplitCfg& cfg, int KH, int KW, hipStream_t stream) {
+    if (KH == 3 && KW == 3) return launch_split_shape<3, 3, NS>(a, cfg, stream);
+    if (KH == 1 && KW == 5) return launch_split_shape<1, 5, NS>(a, cfg, stream);
+    if (KH == 5 && KW == 1) return launch_split_shape<5, 1, NS>(a, cfg, stream);
+    if (KH == 1 && KW == 1) return launch_split_shape<1, 1, NS>(a, cfg, stream);
+    return NND_ERR_UNSUPPORTED;
+}
 
 }  // namespace nnd

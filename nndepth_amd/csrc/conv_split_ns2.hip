@@ -2,7 +2,7 @@
 #include "conv_split_kernel.h"
 
 namespace nnd {
-NND_SPLIT_DEFINE_NS(2)
+template int launch_split_ns<2>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 #ifdef NND_DBG_STAMPS
 extern "C" int nnd_debug_read_split_stamps_ns2(unsigned long long* host, int n) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_split_stamps), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;

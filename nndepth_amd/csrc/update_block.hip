@@ -846,7 +846,7 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
     // launch: ConvIO::cout_need) and flow_head.conv2 + advance (the separate kernel, bit-identical to the folded one); the last
     // iteration runs the full schedule.  Bit-identity needs the merged layer's tile configuration (same split-K, P and K order) for
     // the flow-head channels; launch_conv keeps it and drops only the mask.0 waves / rows (or runs the whole layer where its staging
-    // plan cannot shrink: conv_split.hip restrict_split, conv_mfma.hip launch_conv).
+    // plan cannot shrink: conv_launch.h conv_restrict_cout, called by conv_split.hip plan_split and conv_mfma.hip plan_tile).
     // Rounds 1-2 ran the flow branch on a low-priority side stream beside lookup / convc2 (per-call fork/join events).
     // Measured on MI355X, same box, ms per 544x960 pair: side stream 11.79, in line 11.82 (KITTI batch 8 70.5 / 71.0,
     // CREStereo 39.8 / 39.9, IGEV batch 8 190.1 / 190.5): the overlap it bought (convc2 61 us beside the branch instead
@@ -963,8 +963,7 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
 
 static int conv2d_layer(int Cout, int Cin, int KH, int KW, int arithmetic, ConvLayer* L, int64_t* total) {
     NND_REQUIRE(Cout > 0 && Cin > 0, "conv2d: bad channel counts");
-    NND_REQUIRE((KH == 1 && KW == 1) || (KH == 3 && KW == 3) || (KH == 1 && KW == 5) || (KH == 5 && KW == 1),
-                "conv2d: kernel %dx%d not built (1x1, 3x3, 1x5, 5x1)", KH, KW);
+    NND_REQUIRE(conv_shape_built(KH, KW), "conv2d: kernel %dx%d not built (1x1, 3x3, 1x5, 5x1)", KH, KW);
     NND_REQUIRE(arithmetic == 0 || conv_split_supported(KH, KW, Cin, 1, arithmetic),
                 "conv2d: arithmetic %d not built for %dx%d with %d input channels (3 = bf16x3 split, Cin %% 16 == 0)", arithmetic, KH, KW, Cin);
     int64_t off = 0;

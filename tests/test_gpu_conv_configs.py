@@ -1,8 +1,9 @@
 """GPU: every tile configuration the conv pickers can choose, against float64.
 
-The two convolution kernels take a tile configuration from a host-side picker on every call, and the choice depends on the image
-size and batch: conv_split.hip pick_split -> (ny, ks, P), hence nu and FAST / generic; conv_mfma.hip pick_tile -> (wco, ks), hence
-NE and the LDS size.  The forcing switches (NND_SPLIT_CFG=ny,ks[,P], NND_CONV_CFG=p,ks,wco) reach every configuration; one that
+The two convolution kernels take a tile configuration from a host-side plan on every call, and the choice depends on the image
+size and batch: conv_split.hip plan_split (pick_split, then restrict_split) -> (ny, ks, P), hence nu and FAST / generic;
+conv_mfma.hip plan_tile (pick_tile) -> (wco, ks), hence NE and the LDS size; each prints its plan as one NND_CONV_VERBOSE line
+(print_split_plan, print_tile_plan).  The forcing switches (NND_SPLIT_CFG=ny,ks[,P], NND_CONV_CFG=p,ks,wco) reach every configuration; one that
 does not exist is refused by the picker before any launch (NndError, no verbose line).  This file sweeps them:
 
 1. split kernel, stride 1, ops.Conv2d: every NND_SPLIT_CFG=ny,ks,2 (ny | ncb, ks in 1 / 2 / 4), the picker's own choice and
