@@ -532,6 +532,34 @@ int64_t nnd_epe_metrics_workspace_bytes(void);
 int nnd_epe_metrics(const float* disp_gt, const float* disp_pred, const unsigned char* valid_mask, int B, int C, int H, int W,
                     float max_flow, const float* thresholds_host, int num_thresholds, void* workspace, float* out, void* stream);
 
+/* ------------------------------------------------------------- monocular evaluation criterion on the device (additions within 104)
+ * nnd_depth_eval : DepthEvalCriterion.__call__  nndepth/models/midas/scripts/evaluate.py:48-211 with scale_shift_estimation,
+ *     ssi_depth and normalize_01_depth  nndepth/models/midas/loss.py:6-59.  pred, gt: (B,1,H,W) fp32; valid_mask: (B,1,H,W) bytes
+ *     or NULL (every pixel); B*H*W < 2^31.  In the reference's order, everything after the load in double:
+ *       1 per sample with more than 100 pixels in valid_mask: scale, shift = least squares of pred * scale + shift ~ gt over
+ *         valid_mask (centred sums; a constant prediction c takes the minimum-norm solution scale = c gm / (c^2 + 1), shift =
+ *         gm / (c^2 + 1), gm the mean of gt, as torch.linalg.lstsq returns on the CPU); aligned = pred * scale + shift,
+ *         else aligned = pred;
+ *       2 metric mask = valid_mask & gt > 0.1f & gt < max_depth (both strict, compared as fp32); no pixel in it: out = inf for
+ *         the six errors, 0 for the three deltas (_empty_metrics);
+ *       3 over the metric mask of the whole batch: abs_rel, sq_rel, rmse, rmse_log, delta1..3 (max(a/g, g/a) < 1.25^k); a
+ *         non-positive aligned value makes rmse_log NaN;
+ *       4 x_n = (x - min) / (max - min + 1e-6) for gt and for aligned with the batch's min / max over the metric mask; per
+ *         sample shift = lower median (sorted position (n - 1) / 2, torch.median) and scale = mean |x_n - shift| over its
+ *         pixels of the metric mask, a scale of exactly 0 becomes 1; ssi = (x_n - shift) / scale; ssi_mae, ssi_rmse over the
+ *         metric mask (a sample without a pixel in it contributes nothing).
+ *     out (device, 10 doubles) = abs_rel, sq_rel, rmse, rmse_log, delta1, delta2, delta3, ssi_mae, ssi_rmse, number of pixels in
+ *     the metric mask.  `workspace` = nnd_depth_eval_workspace_bytes(B) device bytes (8-byte aligned; B <= 65535), checked against
+ *     workspace_bytes.  Seven small launches on `stream`, no host synchronisation, no floating-point atomics: the same bits
+ *     run to run.  Non-finite inputs inside the mask, and a prediction that is constant only up to rounding, are outside the
+ *     contract.
+ * nnd_depth_eval_accumulate : the dataset mean's bookkeeping  nndepth/models/midas/scripts/evaluate.py:300-302
+ *     for i < 9: if metrics[i] is finite, sums[i] += metrics[i] and counts[i] += 1 (all device doubles).                       */
+int64_t nnd_depth_eval_workspace_bytes(int B);
+int nnd_depth_eval(const float* pred, const float* gt, const unsigned char* valid_mask, int B, int H, int W, float max_depth,
+                   void* workspace, int64_t workspace_bytes, double* out, void* stream);
+int nnd_depth_eval_accumulate(const double* metrics, double* sums, double* counts, void* stream);
+
 /* ------------------------------------------------------------- scene types on the device (additions within 104)
  * Disparity / Depth / Frame of nndepth/scene: get_view (disparity.py:187-233, depth.py:166-216) and resize
  * (disparity.py:9-75,113-185, depth.py:9-63,85-146, frame.py:47-99).  Masks are bytes (torch.bool or torch.uint8) of the map's shape.

@@ -1,13 +1,14 @@
 """Device-side pre- and post-processing: drop-ins for `preprocess_frame`
 (nndepth/models/raft_stereo/scripts/inference.py:55-60), `Padder` (nndepth/data/dataloaders/utils.py:5-21) and
-`EvalCriterion` (nndepth/models/raft_stereo/scripts/evaluate.py:29-83) that keep the frames and the disparity on the GPU."""
+`EvalCriterion` (nndepth/models/raft_stereo/scripts/evaluate.py:29-83) that keep the frames and the disparity on the GPU, and
+for `DepthEvalCriterion` with its dataset mean (nndepth/models/midas/scripts/evaluate.py:38-211, 300-312) on the monocular side."""
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import torch
 
 from ._lib import NndError, check, lib
-from .ops import _dev, _p, _stream
+from .ops import _dev, _mask_bytes, _p, _stream
 
 
 def preprocess_frame(frame: torch.Tensor, HW: Tuple[int, int]) -> torch.Tensor:
@@ -100,3 +101,79 @@ class EvalCriterion:
         for i, k in enumerate(keys):
             metrics[k] = vals[2 + i]
         return metrics
+
+
+DEPTH_METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "delta3", "ssi_mae", "ssi_rmse")
+_DEPTH_EVAL_WS: Dict[str, torch.Tensor] = {}  # per device, grown to the largest batch seen
+
+
+def _depth_eval_workspace(device: torch.device, B: int) -> torch.Tensor:
+    n = int(lib.nnd_depth_eval_workspace_bytes(B))
+    if n <= 0:
+        check(n, "depth_eval_workspace_bytes")
+    ws = _DEPTH_EVAL_WS.get(str(device))
+    if ws is None or ws.numel() * 8 < n:
+        ws = _DEPTH_EVAL_WS[str(device)] = torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+class DepthEvalCriterion:
+    """The monocular evaluation criterion computed on the device: scale / shift alignment per sample, abs_rel, sq_rel, rmse,
+    rmse_log, delta1..3 and the two scale-and-shift-invariant errors, in float64 (nnd_depth_eval states every step).  Returns
+    the reference's dict of floats, same keys in the same order; the maps stay on the GPU and ten doubles come back."""
+
+    def __init__(self, max_depth: float = 80.0):
+        self.max_depth = max_depth
+
+    def metrics_tensor(self, depth_pred: torch.Tensor, depth_gt: torch.Tensor, valid_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(10,) float64 on the device: the nine metrics in the dict's order, then the number of pixels they were taken over.
+        No host synchronisation, allocations through PyTorch only: it can be captured into a HIP graph (call once before the
+        capture, so that the device's workspace exists)."""
+        what = "DepthEvalCriterion"
+        if not (torch.is_tensor(depth_pred) and torch.is_tensor(depth_gt)):
+            raise NndError(f"{what}: depth_pred and depth_gt are tensors on the HIP device")
+        if valid_mask is not None and valid_mask.dtype not in (torch.bool, torch.uint8):
+            raise NndError(f"{what}: valid_mask is torch.bool or torch.uint8; got {valid_mask.dtype}")
+        if depth_pred.dim() != 4 or depth_pred.shape[1] != 1:
+            raise NndError(f"{what}: depth maps are (B,1,H,W); got depth_pred {tuple(depth_pred.shape)}")
+        if depth_gt.shape != depth_pred.shape or (valid_mask is not None and valid_mask.shape != depth_pred.shape):
+            raise NndError(f"{what}: depth_pred {tuple(depth_pred.shape)}, depth_gt {tuple(depth_gt.shape)}"
+                           + (f", valid_mask {tuple(valid_mask.shape)}" if valid_mask is not None else "") + " must have one shape")
+        d = _dev(depth_pred, depth_gt)
+        pred, gt = depth_pred.contiguous(), depth_gt.contiguous()
+        mask = _mask_bytes(valid_mask, pred, what)
+        B, _, H, W = pred.shape
+        ws = _depth_eval_workspace(d, B)
+        out = torch.empty(10, dtype=torch.float64, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_depth_eval(_p(pred), _p(gt), _p(mask), B, H, W, float(self.max_depth), _p(ws), ws.numel() * 8, _p(out),
+                                     _stream(d)), "depth_eval")
+        return out
+
+    def __call__(self, depth_pred: torch.Tensor, depth_gt: torch.Tensor, valid_mask: Optional[torch.Tensor] = None) -> Dict[str, float]:
+        vals = self.metrics_tensor(depth_pred, depth_gt, valid_mask).cpu().tolist()
+        return dict(zip(DEPTH_METRICS, vals[:9]))
+
+
+class DepthEvalMean:
+    """The evaluation loop's mean over batches (evaluate.py:300-312) kept on the device: `update` only enqueues the batch's
+    criterion and adds its finite metrics to running sums; `result` copies the sums once.  A metric that was never finite comes
+    back as the reference's inf (0.0 for the deltas)."""
+
+    def __init__(self, max_depth: float = 80.0):
+        self.criterion = DepthEvalCriterion(max_depth)
+        self._acc: Optional[torch.Tensor] = None  # (2, 9) float64: sums, counts
+
+    def update(self, depth_pred: torch.Tensor, depth_gt: torch.Tensor, valid_mask: Optional[torch.Tensor] = None) -> None:
+        m = self.criterion.metrics_tensor(depth_pred, depth_gt, valid_mask)
+        if self._acc is None:
+            self._acc = torch.zeros((2, 9), dtype=torch.float64, device=m.device)
+        elif self._acc.device != m.device:
+            raise NndError(f"DepthEvalMean: batches on {self._acc.device} and on {m.device}")
+        with torch.cuda.device(m.device):
+            check(lib.nnd_depth_eval_accumulate(_p(m), _p(self._acc[0]), _p(self._acc[1]), _stream(m.device)), "depth_eval_accumulate")
+
+    def result(self) -> Dict[str, float]:
+        sums, counts = self._acc.cpu().tolist() if self._acc is not None else ([0.0] * 9, [0.0] * 9)
+        return {k: (s / c if c > 0 else (0.0 if k.startswith("delta") else float("inf")))
+                for k, s, c in zip(DEPTH_METRICS, sums, counts)}
