@@ -11,6 +11,8 @@
  *     parameter says "host";
  *   - the caller owns every buffer including workspaces — the library never allocates or
  *     frees device memory and never synchronises;
+ *   - workspaces, scratch buffers and output buffers may hold anything on entry, NaN and inf included (fresh hipMalloc memory, the
+ *     leftovers of an earlier call at another shape): no result depends on it (tests/test_gpu_history.py);
  *   - all work is enqueued on the caller-supplied hipStream_t (`stream`, may be NULL);
  *   - return value: 0 on success, negative nnd_status on failure (never throws);
  *     nnd_last_error() gives a thread-local message for the last failure;

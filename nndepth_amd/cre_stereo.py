@@ -176,6 +176,8 @@ class CREStereoBase(AutoCalibrate, nn.Module):
                 outs.extend({"up_disp": up[i]} for i in range(n_iters))
             return net, flow, up[-1]
         up = None
+        if flow is None:
+            flow = torch.zeros(net.shape[0], 2, *net.shape[2:], dtype=torch.float32, device=net.device)
         for itr in range(n_iters):
             corr = corr_fn(flow, offset, small_patch=(itr % 2 == 1), iter_mode=iter_mode)
             net, mask, delta = self.update_block(net, inp, corr, flow)
@@ -212,12 +214,11 @@ class CREStereoBase(AutoCalibrate, nn.Module):
             conv16, conv8 = self._offset_convs(fmap1.device)
             # 1/(4*ds): attention-refined features, learned offsets, cross attention inside every AGCL call
             off16 = ops.conv2d_offset(conv16, f1_16, self.range_16)  # range * (sigmoid(conv) - 0.5) * 2 in the conv epilogue
-            n, c, h16, w16 = f1_16.shape
             # x + PositionEncodingSine (pos_enc.py:22-42, model.py:180-196): one kernel for both maps, the table generated on the fly
             f1_pe, f2_pe = ops.pos_enc_sine_add(f1_16, f2_16)
             f1_16, f2_16 = self.self_att_fn.forward_maps(f1_pe, f2_pe)
-            flow16 = torch.zeros(n, 2, h16, w16, dtype=torch.float32, device=fmap1.device)
-            _, _, up = self._stage(self.corr_cls(f1_16, f2_16, att=self.cross_att_fn), net16, inp16, flow16, off16,
+            # zero initial flow: None, not a zero tensor (the fused stage has the library clear it on the stream)
+            _, _, up = self._stage(self.corr_cls(f1_16, f2_16, att=self.cross_att_fn), net16, inp16, None, off16,
                                    self.iters // 2, False, outs, last)
             # 1/(2*ds): learned offsets, no attention
             off8 = ops.conv2d_offset(conv8, f1_8, self.range_8)

@@ -436,7 +436,7 @@ class UpdateBlockEngine:
         if n <= 0:
             check(n, "update_block_workspace_floats")
         if self._ws is None or self._ws.numel() < n or self._ws.device != torch.device(device):
-            self._ws = torch.zeros(n, dtype=torch.float32, device=device)
+            self._ws = torch.empty(n, dtype=torch.float32, device=device)
         return self._ws
 
     def _check_state(self, what: str, net, inp, init, init_channels: int):
@@ -549,7 +549,9 @@ class UpdateBlockEngine:
     def refine_cre(self, fmap1, fmap2, net, inp, rate: int, iters: int, flow_init=None, extra_offset=None,
                    scratch=None, keep_all: Optional[bool] = None, last_only: bool = False):
         """One CREStereo cascade stage (AGCL -> update block -> flow += delta -> 2-channel upsample, `iters` times)
-        -> (up (iters or 1, B,2,rate*H,rate*W), flow (B,2,H,W), net).  extra_offset=None: iter mode."""
+        -> (up (iters or 1, B,2,rate*H,rate*W), flow (B,2,H,W), net).  extra_offset=None: iter mode.
+        scratch: optional caller-owned buffer, handed to the library as it is when it holds at least B*C*H*W floats (offset mode:
+        below 2*B*C*H*W floats the library then takes the planar kernel); None: allocated here, 2*B*C*H*W floats in offset mode."""
         c = self._refine_call("refine_cre", (fmap1, fmap2), net, inp, flow_init, 2, rate, iters, keep_all, last_only)
         B, H, W = c.B, c.H, c.W
         fmap1, fmap2 = fmap1.contiguous(), fmap2.contiguous()
@@ -558,12 +560,16 @@ class UpdateBlockEngine:
             raise NndError(f"refine_cre: shapes fmap {tuple(fmap1.shape)} / {tuple(fmap2.shape)}, net {tuple(net.shape)}")
         if extra_offset is not None and extra_offset.numel() != B * 18 * H * W:
             raise NndError(f"refine_cre: extra_offset shape {tuple(extra_offset.shape)} != {(B, 18, H, W)}")
-        need = fmap2.numel() if extra_offset is None else 2 * fmap2.numel()  # warped map / the two channels-last copies
         if extra_offset is not None:
             extra_offset = extra_offset.contiguous()
             _dev(extra_offset)
-        if scratch is None or scratch.numel() < need:
+        if scratch is None or scratch.numel() < fmap2.numel():
+            need = fmap2.numel() if extra_offset is None else 2 * fmap2.numel()  # warped map / the two channels-last copies
             scratch = torch.empty(need, dtype=torch.float32, device=c.d)
+        else:
+            _dev(fmap2, scratch)
+            if not scratch.is_contiguous():
+                raise NndError("refine_cre: `scratch` must be contiguous")
         with torch.cuda.device(c.d):
             check(lib.nnd_cre_stereo_refine(C.byref(c.desc), _p(self.packed), _p(fmap1), _p(fmap2), Cf, _p(extra_offset),
                                             _p(scratch), scratch.numel(), _p(c.net), _p(c.inp), _p(c.init), _p(c.up), c.stride,

@@ -1,6 +1,8 @@
-"""Uninitialised-read detector: the same RAFT-Stereo forward with every torch.empty() of the package (outputs, workspaces) replaced
-by a NaN-filled / 1e30-filled / zero-filled tensor.  A kernel that reads memory it (or an earlier kernel of the forward) did not
-write shows up as a changed or non-finite output.   python scripts/poison_empty.py [arithmetic]"""
+"""Uninitialised-read detector by hand, for one model at one shape: the same RAFT-Stereo forward with every torch.empty() and
+torch.zeros() of the package (outputs, workspaces) replaced by a NaN-filled / 1e30-filled / zero-filled tensor.  A kernel that reads
+memory it (or an earlier kernel of the forward) did not write shows up as a changed or non-finite output.  The suite holds the
+property for every engine and model, at ragged shapes and across shape changes: tests/test_gpu_history.py (patterns and allocator
+replacements: tests/history_util.py).   python scripts/poison_empty.py [arithmetic]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,13 +21,16 @@ def poisoned_empty(*a, **k):
     return t
 
 
-def poisoned_zeros(*a, **k):  # the update-block workspace: zero only where the library says it must be
-    return real_zeros(*a, **k)
+def poisoned_zeros(*a, **k):  # no exemption: the library asks for no zero-filled buffer (include/nndepth_amd.h, conventions)
+    t = real_zeros(*a, **k)
+    if fill[0] is not None and t.is_floating_point() and t.device.type == "cuda":
+        t.fill_(fill[0])
+    return t
 
 
 def run(f):
     fill[0] = f
-    torch.empty = poisoned_empty
+    torch.empty, torch.zeros = poisoned_empty, poisoned_zeros
     try:
         m = BaseRAFTStereo(iters=6, context_dim=64, arithmetic=ar)
         weightgen.fill_module_(m)
@@ -34,7 +39,7 @@ def run(f):
         outs = [m(*fr) for _ in range(2)]
         return [o["up_disp"].clone() for o in outs[-1]]
     finally:
-        torch.empty = real_empty
+        torch.empty, torch.zeros = real_empty, real_zeros
 
 
 base = run(None)
