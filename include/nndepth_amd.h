@@ -196,7 +196,8 @@ int nnd_convex_upsample(const float* flow, const float* mask, float* out,
  *   - after a calibration — one or more forwards with NND_FLAG_CALIBRATE on representative inputs, then
  *     nnd_*_calibration_finish — each layer has xs = 11 - ceil(log2(M)), M = the largest |activation| that layer staged
  *     during those forwards: all 22 bits for M * 2^-13 <= |x| <= M, absolute error <= M * 2^-36 below, valid (finite) up to
- *     |x| < 32 * M, inf / NaN in the output beyond;
+ *     |x| < 32 * M, inf / NaN in the output beyond — at every output that reads the activation, through the ReLU / sigmoid /
+ *     tanh epilogues and the layers behind them (nnd_update_block_forward: and at no output outside the reach of its convs);
  *   - nnd_update_block_scale_slots gives the float offsets of the layers' slots in the blob: slot[1] = 2^xs, so the valid range
  *     of layer i is |x| < 65504 / slot[1] (the Python engines expose it as `activation_ranges()`).
  * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once).                              */
@@ -741,6 +742,8 @@ int nnd_profile_mfma_peak(int waves_per_simd, int iters, void* stream, float* sc
  * this box and the shader clock it settles at (nominal: 2500 TFLOP/s at 2.4 GHz).  clk_dev: device buffer of >= 512 64-bit words. */
 int nnd_profile_mfma16_peak(int bf16, int waves_per_simd, float target_ms, void* stream, float* scratch_dev,
                             unsigned long long* clk_dev, float* tflops_out, float* ghz_out);
+/* nnd_num_convs: the loop's launches, `which` of the profiling calls.  nnd_conv_name names those and, behind them, the other
+ * convolutions that nnd_update_block_scale_slots lists (the single-call GRU convs, the per-pair context terms); "" beyond. */
 int nnd_num_convs(const nnd_update_block_desc* desc);
 const char* nnd_conv_name(const nnd_update_block_desc* desc, int which);
 

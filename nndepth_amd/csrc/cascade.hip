@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(256) split_tanh_relu_kernel(const float* __res
     const long b = idx / per, rem = idx - b * per;
     const float v = x[idx];
     if (rem < (long)Cn * HW) net[b * Cn * HW + rem] = tanhf_(v);
-    else inp[b * Ci * HW + (rem - (long)Cn * HW)] = fmaxf(v, 0.f);
+    else inp[b * Ci * HW + (rem - (long)Cn * HW)] = relu_nan(v);
 }
 
 // thread = one 4x4-pooled output pixel (or a 2x2-pooled one past the last full 4x4 block); window sums in row-major order

@@ -119,6 +119,17 @@ int calib_finish(float* blob, const int64_t* tail_offs, int n, int32_t* status_d
 // established is that the scalar form never failed, and this makes it a property of the source instead of a compiler flag.
 #ifdef __HIPCC__
 __device__ __forceinline__ void fmac_scalar(float& acc, float a, float b) { asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b)); }
+
+// ReLU that lets NaN through.  An fp16x2 layer that stages an activation beyond its range accumulates inf - inf = NaN
+// (split_arith.h), and that NaN is the only sign of it: fmaxf(NaN, 0) = 0 would turn it into a finite, wrong result.  Every ReLU
+// on a path that may carry an fp16x2 result goes through this.  IEEE 754-2019 maximum = one v_maximum3_f32 on gfx950 (fmaxf
+// took a v_max_f32 and, where the compiler could not prove its operand canonical, a second one): the same bits as fmaxf(v, 0.f)
+// for every value but NaN.  The select `v < 0.f ? 0.f : v` says the same in two instructions.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// clamp to [lo, hi] that lets NaN through (v_maximum3_f32, v_minimum3_f32)
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, lo), hi);
+}
 #endif
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

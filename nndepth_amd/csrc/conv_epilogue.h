@@ -41,7 +41,7 @@ struct ConvArgs {
 // exact residual r (fma), so exp(x) = exp2(t) * 2^r ~= exp2(t) * (1 + r*ln2); v_exp_f32 itself is ~1 ulp.
 __device__ __forceinline__ float exp_acc(float x) {
     const float L2E = 1.44269504088896341f;
-    x = fminf(fmaxf(x, -87.0f), 88.0f);
+    x = clamp_nan(x, -87.0f, 88.0f);  // not fminf / fmaxf: NaN stays NaN through sigmoidf_ / tanhf_ (common.h)
     const float t = x * L2E;
     const float r = fmaf(x, 1.92596299e-8f, fmaf(x, L2E, -t));  // + x * (log2e - (float)log2e); explicit fma: no context-dependent contraction
     const float e = __builtin_amdgcn_exp2f(t);
@@ -126,7 +126,7 @@ __device__ __forceinline__ void conv_epilogue_planar(const ConvArgs& a, const f3
             if (co >= a.Cout) continue;
             const float v = acc[pp][reg] + bias_r[reg];
             if (epi == EPI_RELU) {
-                a.out0[b * a.obs0 + co * DP + pix] = fmaxf(v, 0.f);
+                a.out0[b * a.obs0 + co * DP + pix] = relu_nan(v);
             } else if (epi == EPI_LINEAR) {
                 a.out0[b * a.obs0 + co * DP + pix] = v;
             } else if (epi == EPI_SCALE) {
@@ -140,9 +140,9 @@ __device__ __forceinline__ void conv_epilogue_planar(const ConvArgs& a, const f3
             } else if (epi == EPI_AFFINE) {  // folded norm: y = acc*scale + shift; optional ReLU, residual add, ReLU
                 float y2 = fmaf(acc[pp][reg], z_r[reg], bias_r[reg]);
                 if (a.flags & 4) y2 = y2 > 0.f ? y2 : a.scale * y2;  // LeakyReLU (slope in `scale`), Conv3d path
-                if (a.flags & 1) y2 = fmaxf(y2, 0.f);
+                if (a.flags & 1) y2 = relu_nan(y2);
                 if (a.aux0) y2 = h_r[reg] + y2;
-                if (a.flags & 2) y2 = fmaxf(y2, 0.f);
+                if (a.flags & 2) y2 = relu_nan(y2);
                 a.out0[b * a.obs0 + co * DP + pix] = y2;
             } else if (epi == EPI_GRU_ZR) {
                 const float sg = sigmoidf_(v);
@@ -224,15 +224,15 @@ __device__ __forceinline__ void conv_epilogue_c4(const ConvArgs& a, const f32x16
                 const float ac = acc[pp][4 * q + i];
                 const float v = ac + get(bm[q], i);
                 float o0 = v, o1 = 0.f;
-                if (epi == EPI_RELU) o0 = fmaxf(v, 0.f);
+                if (epi == EPI_RELU) o0 = relu_nan(v);
                 else if (epi == EPI_SCALE) o0 = a.scale * v;
                 else if (epi == EPI_SIGMOID_RANGE) o0 = a.scale * (sigmoidf_(v) - 0.5f) * 2.0f;
                 else if (epi == EPI_AFFINE) {
                     float y2 = fmaf(ac, get(scale4[q], i), get(bm[q], i));
                     if (a.flags & 4) y2 = y2 > 0.f ? y2 : a.scale * y2;
-                    if (a.flags & 1) y2 = fmaxf(y2, 0.f);
+                    if (a.flags & 1) y2 = relu_nan(y2);
                     if (a.aux0) y2 = get(hv[q], i) + y2;
-                    if (a.flags & 2) y2 = fmaxf(y2, 0.f);
+                    if (a.flags & 2) y2 = relu_nan(y2);
                     o0 = y2;
                 } else if (epi == EPI_GRU_ZR) {
                     const float sg = sigmoidf_(v);
@@ -351,15 +351,15 @@ __device__ __forceinline__ void epi_c4_store(const ConvArgs& a, const float4 (&c
                 const float ac = get(cacc[pp][j], i);
                 const float v = ac + get(e.bm[pp][j], i);
                 float o0 = v, o1 = 0.f;
-                if (epi == EPI_RELU) o0 = fmaxf(v, 0.f);
+                if (epi == EPI_RELU) o0 = relu_nan(v);
                 else if (epi == EPI_SCALE) o0 = a.scale * v;
                 else if (epi == EPI_SIGMOID_RANGE) o0 = a.scale * (sigmoidf_(v) - 0.5f) * 2.0f;
                 else if (epi == EPI_AFFINE) {
                     float y2 = fmaf(ac, get(e.scale4[j], i), get(e.bm[pp][j], i));
                     if (a.flags & 4) y2 = y2 > 0.f ? y2 : a.scale * y2;
-                    if (a.flags & 1) y2 = fmaxf(y2, 0.f);
+                    if (a.flags & 1) y2 = relu_nan(y2);
                     if (a.aux0) y2 = get(e.hv[pp][j], i) + y2;
-                    if (a.flags & 2) y2 = fmaxf(y2, 0.f);
+                    if (a.flags & 2) y2 = relu_nan(y2);
                     o0 = y2;
                 } else if (epi == EPI_GRU_ZR) {
                     const float sg = sigmoidf_(v);

@@ -399,12 +399,12 @@ __global__ void __launch_bounds__(256) conv1x1_stream_kernel(ConvArgs a, int nti
                     if (epi == EPI_AFFINE) {
                         v = fmaf(acc[reg], sc_r[reg], bias_r[reg]);
                         if (a.flags & 4) v = v > 0.f ? v : a.scale * v;
-                        if (a.flags & 1) v = fmaxf(v, 0.f);
+                        if (a.flags & 1) v = relu_nan(v);
                         if (a.aux0) v = rr[i] + v;
-                        if (a.flags & 2) v = fmaxf(v, 0.f);
+                        if (a.flags & 2) v = relu_nan(v);
                     } else {
                         v = acc[reg] + bias_r[reg];
-                        if (epi == EPI_RELU) v = fmaxf(v, 0.f);
+                        if (epi == EPI_RELU) v = relu_nan(v);
                         else if (epi == EPI_SCALE) v = a.scale * v;
                     }
                     o[i] = v;
@@ -429,12 +429,12 @@ __global__ void __launch_bounds__(256) conv1x1_stream_kernel(ConvArgs a, int nti
             if (epi == EPI_AFFINE) {
                 v = fmaf(acc[reg], sc_r[reg], bias_r[reg]);
                 if (a.flags & 4) v = v > 0.f ? v : a.scale * v;
-                if (a.flags & 1) v = fmaxf(v, 0.f);
+                if (a.flags & 1) v = relu_nan(v);
                 if (a.aux0) v = res[reg] + v;
-                if (a.flags & 2) v = fmaxf(v, 0.f);
+                if (a.flags & 2) v = relu_nan(v);
             } else {
                 v = acc[reg] + bias_r[reg];
-                if (epi == EPI_RELU) v = fmaxf(v, 0.f);
+                if (epi == EPI_RELU) v = relu_nan(v);
                 else if (epi == EPI_SCALE) v = a.scale * v;
             }
             a.out0[b * a.obs0 + co * DP + pix] = v;

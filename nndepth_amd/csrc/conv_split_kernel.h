@@ -223,6 +223,11 @@ __global__ void __launch_bounds__(MAXT) conv_split_kernel(ConvArgs a) {
         loff[i] = (oct >> 1) * (P * SUBB) + pp * SUBB + lpos + (oct & 1) * 16;
         cho[i] = oct * 8;
         if constexpr (FAST) goff[i] = inimg[i] ? cho[i] * (int)SP + goff[i] : 0;  // whole offset inside the super-chunk
+        // PIPE zeroes a position outside the image through the scale (micro): 0 * what the load returned.  It therefore reads
+        // the NEAREST pixel inside the image, not element 0: that pixel lies in the window of every output that reads the
+        // position, so if it holds inf / NaN (an overflow upstream) those outputs are non-finite anyway and no other one becomes
+        // so; a finite value gives the same zero as before.  (An absent sub-tile reads the last row: never stored.)
+        if constexpr (PIPE) goff[i] = cho[i] * (int)SP + (int)pix_off(a.ls, min(max(gy, 0), Hin - 1), min(max(gx, 0), Win - 1));
     }
 
     NND_PSTAMP(5);
@@ -263,7 +268,7 @@ __global__ void __launch_bounds__(MAXT) conv_split_kernel(ConvArgs a) {
         if constexpr (FAST && SRC4) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                const float4 t = *reinterpret_cast<const float4*>(src + (unsigned)(goff[i] + (inimg[i] ? 4 * g * (int)SP : 0)));
+                const float4 t = *reinterpret_cast<const float4*>(src + (unsigned)(goff[i] + ((PIPE || inimg[i]) ? 4 * g * (int)SP : 0)));
                 stage[i][4 * g] = t.x; stage[i][4 * g + 1] = t.y; stage[i][4 * g + 2] = t.z; stage[i][4 * g + 3] = t.w;
             }
         } else if constexpr (FAST) {  // planar tile-major source: 8 channel planes, one 4-B load each
@@ -364,7 +369,8 @@ __global__ void __launch_bounds__(MAXT) conv_split_kernel(ConvArgs a) {
                 // lo = rn_f16(s * x - hi) reading hi's halves as the fp16 addend (v_fma_mix*: fp32 FMA with fp16 operands / result;
                 // s * x and s * x - hi are exact in fp32, so each piece is rounded once — the values of split_pieces_n).  The
                 // compiler's own selection for the C++ form below took 9 (it formed every hi piece twice).  Positions outside the
-                // image are zeroed through the scale (the clamped load returned a finite value), no per-element select.
+                // image are zeroed through the scale, no per-element select: the clamped load returned the nearest pixel inside the
+                // image (goff above), and where that is inf / NaN the product is NaN — in outputs that read the pixel itself.
                 const float sc = inimg[i] ? xscale : 0.f;
                 uint32_t hi, lo;
                 asm("v_fma_mixlo_f16 %0, %2, %3, 0\n\t"

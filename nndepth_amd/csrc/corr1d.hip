@@ -601,15 +601,15 @@ __device__ __forceinline__ void store_c1(float* __restrict__ out_b, const Lay& l
         for (int q = 0; q < 4; ++q) {
             const int co0 = cb * 32 + 8 * q + 4 * h2;
             *reinterpret_cast<float4*>(out_b + (long)co0 * lay.plane + po * 4) =
-                make_float4(fmaxf(acc[4 * q] + br[4 * q], 0.f), fmaxf(acc[4 * q + 1] + br[4 * q + 1], 0.f),
-                            fmaxf(acc[4 * q + 2] + br[4 * q + 2], 0.f), fmaxf(acc[4 * q + 3] + br[4 * q + 3], 0.f));
+                make_float4(relu_nan(acc[4 * q] + br[4 * q]), relu_nan(acc[4 * q + 1] + br[4 * q + 1]),
+                            relu_nan(acc[4 * q + 2] + br[4 * q + 2]), relu_nan(acc[4 * q + 3] + br[4 * q + 3]));
         }
     } else {
         float* o = out_b + po;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int co = cb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h2;
-            o[(long)co * lay.plane] = fmaxf(acc[reg] + br[reg], 0.f);
+            o[(long)co * lay.plane] = relu_nan(acc[reg] + br[reg]);
         }
     }
 }

@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const float* __restrict__ x, 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float t = fmaf(acc[i][j][4 * q + e], scale[co0 + e], shift[co0 + e]);
-                        v[e] = relu ? fmaxf(t, 0.f) : t;
+                        v[e] = relu ? relu_nan(t) : t;
                     }
                     *reinterpret_cast<float4*>(o + (long)co0 * lay.plane) = make_float4(v[0], v[1], v[2], v[3]);
                 }
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const float* __restrict__ x, 
             for (int reg = 0; reg < 16; ++reg) {
                 const int co = j * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h2;
                 const float v = fmaf(acc[i][j][reg], scale[co], shift[co]);
-                o[(long)co * lay.plane] = relu ? fmaxf(v, 0.f) : v;
+                o[(long)co * lay.plane] = relu ? relu_nan(v) : v;
             }
     }
 }
@@ -321,8 +321,8 @@ __global__ void __launch_bounds__(256) in_apply_kernel(float* __restrict__ x, lo
 #pragma unroll
     for (int k = 0; k < V; ++k) {
         float r = fmaf(v[k], a, b);
-        if (relu) r = fmaxf(r, 0.f);
-        if (sc) r = fmaxf(fmaf(sv[k], as, bsft) + r, 0.f);
+        if (relu) r = relu_nan(r);
+        if (sc) r = relu_nan(fmaf(sv[k], as, bsft) + r);
         v[k] = r;
     }
     if (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]);
@@ -353,8 +353,8 @@ __global__ void __launch_bounds__(256) in_apply_c4_kernel(float* __restrict__ x,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float r = fmaf(v[k], a[k], b[k]);
-        if (relu) r = fmaxf(r, 0.f);
-        if (sc) r = fmaxf(fmaf(sv[k], as[k], bsft[k]) + r, 0.f);
+        if (relu) r = relu_nan(r);
+        if (sc) r = relu_nan(fmaf(sv[k], as[k], bsft[k]) + r);
         v[k] = r;
     }
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);

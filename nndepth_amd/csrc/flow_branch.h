@@ -128,7 +128,7 @@ __device__ __forceinline__ void flow_branch_body(const FlowBranchArgs& a, unsign
                 const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
                 float val[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) val[j] = in ? fmaxf(acc[p][j] + b7l[g * 16 + 8 * h + j], 0.f) : 0.f;
+                for (int j = 0; j < 8; ++j) val[j] = in ? relu_nan(acc[p][j] + b7l[g * 16 + 8 * h + j]) : 0.f;
                 uint4 pieces[NS];
                 split_pieces<NS>(val, pieces, xscale);
 #pragma unroll
@@ -194,17 +194,17 @@ __device__ __forceinline__ void flow_branch_body(const FlowBranchArgs& a, unsign
             for (int q = 0; q < 4; ++q) {
                 const int co0 = cbi * 32 + 8 * q + 4 * h2;
                 float4 v4;
-                v4.x = fmaxf(acc[0][4 * q] + bias_r[4 * q], 0.f);
-                v4.y = fmaxf(acc[0][4 * q + 1] + bias_r[4 * q + 1], 0.f);
-                v4.z = fmaxf(acc[0][4 * q + 2] + bias_r[4 * q + 2], 0.f);
-                v4.w = fmaxf(acc[0][4 * q + 3] + bias_r[4 * q + 3], 0.f);
+                v4.x = relu_nan(acc[0][4 * q] + bias_r[4 * q]);
+                v4.y = relu_nan(acc[0][4 * q + 1] + bias_r[4 * q + 1]);
+                v4.z = relu_nan(acc[0][4 * q + 2] + bias_r[4 * q + 2]);
+                v4.w = relu_nan(acc[0][4 * q + 3] + bias_r[4 * q + 3]);
                 *reinterpret_cast<float4*>(o + (long)co0 * DP) = v4;
             }
         } else {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int co = cbi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h2;
-                o[(long)co * DP] = fmaxf(acc[0][reg] + bias_r[reg], 0.f);
+                o[(long)co * DP] = relu_nan(acc[0][reg] + bias_r[reg]);
             }
         }
     }

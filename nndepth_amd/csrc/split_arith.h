@@ -14,7 +14,9 @@
 //                      that its ABSOLUTE error is <= 2^-25 in scaled units = 2^-36 of the calibrated maximum (negligible against
 //                      the fp32 accumulation rounding of the terms that dominate the dot product).  Valid while
 //                      |x| < 65504 / 2^xs, i.e. up to 32 x the calibrated maximum (uncalibrated: 16376); beyond that the
-//                      conversion gives inf and the output is NaN/inf (visible, never silently wrong).  Per-op error vs
+//                      conversion gives inf and the output is NaN/inf (visible, never silently wrong: the pieces are +inf and
+//                      -inf, the accumulator NaN, and the activations behind a layer let NaN through — common.h relu_nan,
+//                      conv_epilogue.h exp_acc; tests/test_gpu_calib.py).  Per-op error vs
 //                      float64: representation 5.6e-8 rms at |y| <= 4 on the convc2 shape, 20-30x below the fp32 accumulation
 //                      rounding both arithmetics share (scripts/study/).
 // Every product of two pieces is an exact fp32 number (8 x 8 or 11 x 11 significand bits) and the MFMA accumulates in fp32.

@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) convf1_kernel(const float* __restrict__ f
 #pragma unroll
         for (int i = 0; i < FC * 49; ++i) acc = fmaf(wc[i], v[i], acc);
         acc += bias[co0 + cc];
-        if (ok) out[b * obs + (co0 + cc) * HW + pix_off(lay, y, x)] = fmaxf(acc, 0.f);
+        if (ok) out[b * obs + (co0 + cc) * HW + pix_off(lay, y, x)] = relu_nan(acc);
     }
 }
 
@@ -1105,7 +1105,9 @@ int nnd_num_convs(const nnd_update_block_desc* desc) {
 
 const char* nnd_conv_name(const nnd_update_block_desc* desc, int which) {
     (void)desc;
-    return (which >= 0 && which < C_LOOP_COUNT) ? kConvNames[which] : "";
+    // [0, nnd_num_convs) are the loop's launches; the names behind them belong to the other scale slots of
+    // nnd_update_block_scale_slots (the single-call GRU convs and the per-pair context terms)
+    return (which >= 0 && which < C_COUNT) ? kConvNames[which] : "";
 }
 
 int nnd_profile_conv(const nnd_update_block_desc* desc, const float* packed, float* workspace, int B, int H, int W, int which,

@@ -427,6 +427,8 @@ class UpdateBlockEngine:
         for i in range(n):
             if offs[i] >= 0 and blob is not None:
                 name = lib.nnd_conv_name(C.byref(self.desc), i).decode()
+                if self.gru != "sep_conv" and ("convz2+convr2" in name or "convq2" in name):
+                    continue  # conv_gru has one pass: these slots alias the layers of pass 1
                 out[name or f"conv{i}"] = 65504.0 / float(blob[offs[i] + 1])
         return out
 

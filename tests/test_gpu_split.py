@@ -122,6 +122,8 @@ def test_fp16x2_out_of_range_activations_are_visible():
     touched[:, :, 5:8, 6:9] = True  # the 3x3 outputs that read the pixel
     assert not torch.isfinite(y[touched]).any(), "an overflowing activation must poison every output that reads it"
     assert torch.allclose(y[~touched], ref[~touched], atol=2e-5)
+    yr = conv(x.to(DEV), relu=True).cpu()  # ... through the ReLU epilogue too: max(NaN, 0) must not be 0
+    assert not torch.isfinite(yr[touched]).any() and torch.allclose(yr[~touched], ref.clamp_min(0)[~touched], atol=2e-5)
     conv.calibrate(x.to(DEV))  # M = 20000 -> valid up to 65504 / 2^-4 = 1.05e6
     assert 32 * 20000.0 <= 2 * conv.activation_range() and conv.activation_range() >= 20000.0 * 16
     y = conv(x.to(DEV)).cpu()
@@ -129,6 +131,7 @@ def test_fp16x2_out_of_range_activations_are_visible():
     assert torch.isfinite(conv((x * 16).to(DEV))).all()
     y64 = conv((x * 64).to(DEV)).cpu()
     assert not torch.isfinite(y64[touched]).any()
+    assert not torch.isfinite(conv((x * 64).to(DEV), relu=True).cpu()[touched]).any()
 
 
 @pytest.mark.parametrize("k", [-12, -6, 0, 6, 12], ids=lambda k: f"2^{k}")
@@ -154,6 +157,11 @@ def test_update_block_over_input_scales(gold, arith, k):
         ub = ub.to(DEV)
         dev_ins = [i.to(DEV) for i in ins]
         if a == "fp16x2":
+            # as the model classes calibrate: again while a layer saw inf / NaN at the scale it had (status bit 0).  At 2^12 the inputs
+            # overflow the default scale of the first layers, and the NaN they then produce reaches the records behind them (it used
+            # to end as 0 in the ReLU epilogues, and those records were taken over wrong activations); the second pass is clean
+            from nndepth_amd.raft_stereo import calibration_passes
+            calibration_passes(lambda: ub(*dev_ins), 4, "update block: activations still overflow fp16 after 4 passes")
             with ops.calibration() as c:
                 ub(*dev_ins)
             assert not (c.status & 1)
