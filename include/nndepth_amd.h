@@ -203,8 +203,8 @@ int nnd_convex_upsample(const float* flow, const float* mask, float* out,
  * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once).                              */
 typedef struct {
     int32_t struct_size;   /* sizeof(nnd_update_block_desc) */
-    int32_t hidden_dim;    /* 128 */
-    int32_t context_dim;   /* 64 (YAML) or 128 (class default) */
+    int32_t hidden_dim;    /* 128; a multiple of 32, at most 192 (160 with 2 flow channels): flow_head.conv2 stages them all in LDS */
+    int32_t context_dim;   /* 64 (YAML) or 128 (class default); a multiple of 8 */
     int32_t cor_planes;    /* num_levels*(2r+1) = 36; 576 for IGEV */
     int32_t flow_channels; /* 1 (RAFT/IGEV) or 2 (CRE) */
     int32_t mask_channels; /* 9*rate*rate: 576 (/8) or 144 (/4) */

@@ -50,12 +50,20 @@ static ConvLayer mk(int KH, int KW, int Cin, int Cout, int64_t* off, int arith =
     return make_conv_layer(KH, KW, Cin, Cout, 1, arith, 0, false, off);
 }
 
+// LDS of flow_head.conv2 (flow_head2_kernel): the 6x10 halo patch of all `hid` channels, its weights, 16 partial sums per pixel
+static size_t fc2_lds_bytes(int hid, int fc) { return (size_t)(hid * 64 + fc * hid * 9 + 16 * fc * 32) * sizeof(float); }
+
 static int make_plan(const nnd_update_block_desc* d, Plan* p) {
     if (int rc = check_desc(d, NND_FLAG_CALIBRATE | NND_FLAG_LAST_UPSAMPLE_ONLY, "update_block")) return rc;
     const int hid = d->hidden_dim, ctx = d->context_dim, cp = d->cor_planes, fc = d->flow_channels, mc = d->mask_channels;
     NND_REQUIRE(hid > 0 && hid % 32 == 0, "update_block: hidden_dim %d must be a positive multiple of 32", hid);
     NND_REQUIRE(ctx > 0 && ctx % 8 == 0, "update_block: context_dim %d must be a positive multiple of 8", ctx);
     NND_REQUIRE(cp > 0 && (fc == 1 || fc == 2) && mc > 0 && mc % 9 == 0, "update_block: bad cor_planes/flow_channels/mask_channels");
+    // refused here, where the engine is built, not by flow_head.conv2's launch in the middle of a loop (hidden_dim <= 192 with one flow
+    // channel, <= 160 with two)
+    NND_REQUIRE(fc2_lds_bytes(hid, fc) <= 64 * 1024,
+                "update_block: hidden_dim %d with %d flow channel(s) is not supported: flow_head.conv2 would stage %zu bytes of LDS (at most 65536)",
+                hid, fc, fc2_lds_bytes(hid, fc));
     NND_REQUIRE(d->gru_kind == 0 || d->gru_kind == 1, "update_block: gru_kind must be 0 (sep_conv) or 1 (conv_gru)");
     NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2,
                 "update_block: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3 split) or 2 (fp16x2 split)");
@@ -495,8 +503,8 @@ static int run_fc2(const Plan& p, const float* blob, const Bufs& w, float* delta
     const int64_t n = lay.plane;
     const int tiles_x = cdiv(W, 8);
     dim3 grid(tiles_x * cdiv(H, 4), 1, B), block(512);
-    const size_t lds = (size_t)(hid * 64 + fc * hid * 9 + 16 * fc * 32) * sizeof(float);
-    NND_REQUIRE(hid % 16 == 0 && lds <= 64 * 1024, "flow_head.conv2: hidden_dim %d not supported", hid);
+    const size_t lds = fc2_lds_bytes(hid, fc);
+    NND_REQUIRE(hid % 16 == 0 && lds <= 64 * 1024, "flow_head.conv2: hidden_dim %d not supported", hid);  // (make_plan refuses these)
     NND_REQUIRE(advance != 1 || fc == 1, "flow_head.conv2: the coordinate advance needs flow_channels == 1");
     float* hx_flow = w.hx + ws_chan(hxC - fc, n);
     const int hx_cs = (int)(ws_chan(hxC - fc + 1, n) - ws_chan(hxC - fc, n));  // floats between the flow channels inside hx
