@@ -563,6 +563,62 @@ int nnd_depth_eval(const float* pred, const float* gt, const unsigned char* vali
                    void* workspace, int64_t workspace_bytes, double* out, void* stream);
 int nnd_depth_eval_accumulate(const double* metrics, double* sums, double* counts, void* stream);
 
+/* ------------------------------------------------------------- stereo evaluation of a whole forward on the device (additions within 104)
+ * nnd_stereo_eval : EvalCriterion.__call__  nndepth/models/raft_stereo/scripts/evaluate.py:48-83 (likewise igev_stereo/ and
+ *     cre_stereo/scripts/evaluate.py) for EVERY output of a forward in one call, with the per-output term and the value of the
+ *     sequence loss, RAFTLoss / CREStereoLoss  nndepth/models/raft_stereo/loss.py:15-52, cre_stereo/loss.py.
+ *     Ground truth (B,Cg,H,W) fp32, contiguous.  Output i: (B,C_i,h_i,w_i) fp32 read through its own batch / channel / row strides
+ *     (in elements, >= 0; the innermost stride is 1), so a cropped view or a slice of a stacked tensor is read where it lies.
+ *     Cg == C_i, or Cg == 1: the one channel then serves every output channel, which is what the reference's broadcasting does
+ *     when cre_stereo/scripts/evaluate.py:144-151 hands it the 2-channel up_disp and a 1-channel ground truth (a quirk, kept).
+ *     Per output, every fp32 step as the reference takes it, everything after the per-pixel values in double:
+ *       g     = the ground truth at the output's size: itself at equal size; otherwise s = W // w_i (0: refused) and
+ *               g = -max_pool2d(-gt, s) / (float)s read through the source pixel F.interpolate(., size=(h_i,w_i)) (nearest) picks
+ *               (evaluate.py:63-66, loss.py:23-26), computed on the fly, never written;
+ *       epe   = sqrtf(sum_c (p_c - g_c)^2), valid = sqrtf(sum_{c<Cg} g_c^2) < max_flow, and mask != 0 where a mask is given
+ *               (bytes, (B,mask_h,mask_w); every output of the call must then have that size);
+ *       columns (K = 3 + n_above + n_below doubles):  epe = mean of epe over valid pixels (none: NaN);  count = valid pixels;
+ *               l1 = sum of valid * |p_c - g_c| over all B*C_i*h_i*w_i elements / that number (loss.py:30-33);
+ *               above[k]: fraction of valid pixels with epe > above[k] (evaluate.py:82);  below[k]: with epe < below[k]
+ *               (loss.py:47-50); both strict, fp32 against fp32; a fraction is (double)count_k / (double)count.
+ *     out (device, N*K + 1 doubles) = the N rows, then sum_i gamma^(N-1-i) * l1_i added in output order (loss.py:20-33).
+ *     Outputs of one (C,h,w) share one launch, one more launch reduces everything: the number of launches is 1 + the number of
+ *     distinct sizes.  `workspace` = nnd_stereo_eval_workspace_bytes(num_outputs) device bytes, 8-byte aligned, checked against
+ *     workspace_bytes.  Integer counts, partial sums added in index order, no floating-point atomics: the same bits run to run,
+ *     and a row does not depend on the other outputs of the call.  Every argument check answers before anything is launched.
+ * nnd_stereo_eval_accumulate : sums[j] += metrics[j], j < n (device doubles): the per-pair lists of evaluate.py:141-169 as
+ *     running sums; NaN propagates as np.mean over those lists does.
+ * nnd_min_pool_nearest : dst (B,C,h,w) = F.interpolate(-F.max_pool2d(-gt, s) / s, size=(h,w)), s = W // w: the three lines of
+ *     evaluate.py:63-66 as a map of their own (nnd_stereo_eval's g, bit for bit).                                               */
+#define NND_STEREO_EVAL_MAX_OUTPUTS 64
+#define NND_STEREO_EVAL_MAX_THRESHOLDS 8
+typedef struct nnd_stereo_eval_output {
+    const float* data;
+    int32_t C, h, w;
+    int32_t reserved;                       /* 0 */
+    int64_t stride_b, stride_c, stride_row; /* in elements */
+} nnd_stereo_eval_output;
+typedef struct nnd_stereo_eval_desc {
+    int32_t struct_size; /* sizeof(nnd_stereo_eval_desc) */
+    int32_t flags;       /* 0 */
+    const float* gt;     /* (B,Cg,H,W) */
+    int32_t B, Cg, H, W;
+    const unsigned char* mask; /* (B,mask_h,mask_w) bytes, or NULL: every pixel */
+    int32_t mask_h, mask_w;
+    double gamma;   /* the sequence loss's weight base, as the reference's Python float */
+    float max_flow; /* compared as fp32, like the thresholds */
+    int32_t n_above;
+    float above[NND_STEREO_EVAL_MAX_THRESHOLDS];
+    int32_t n_below;
+    float below[NND_STEREO_EVAL_MAX_THRESHOLDS];
+    int32_t num_outputs;
+    nnd_stereo_eval_output outputs[NND_STEREO_EVAL_MAX_OUTPUTS];
+} nnd_stereo_eval_desc;
+int64_t nnd_stereo_eval_workspace_bytes(int num_outputs);
+int nnd_stereo_eval(const nnd_stereo_eval_desc* desc, void* workspace, int64_t workspace_bytes, double* out, void* stream);
+int nnd_stereo_eval_accumulate(const double* metrics, int n, double* sums, void* stream);
+int nnd_min_pool_nearest(const float* gt, float* dst, int B, int C, int H, int W, int h, int w, void* stream);
+
 /* ------------------------------------------------------------- scene types on the device (additions within 104)
  * Disparity / Depth / Frame of nndepth/scene: get_view (disparity.py:187-233, depth.py:166-216) and resize
  * (disparity.py:9-75,113-185, depth.py:9-63,85-146, frame.py:47-99).  Masks are bytes (torch.bool or torch.uint8) of the map's shape.

@@ -63,6 +63,24 @@ class MidasDesc(_SizedDesc):
     _fields_ = [("struct_size", C.c_int32), ("feature_channels", C.c_int32), ("flags", C.c_int32)]
 
 
+NND_STEREO_EVAL_MAX_OUTPUTS = 64
+NND_STEREO_EVAL_MAX_THRESHOLDS = 8
+
+
+class StereoEvalOutput(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("reserved", C.c_int32),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_row", C.c_int64)]
+
+
+class StereoEvalDesc(_SizedDesc):
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("gt", C.c_void_p), ("B", C.c_int32), ("Cg", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("mask", C.c_void_p), ("mask_h", C.c_int32), ("mask_w", C.c_int32),
+                ("gamma", C.c_double), ("max_flow", C.c_float), ("n_above", C.c_int32),
+                ("above", C.c_float * NND_STEREO_EVAL_MAX_THRESHOLDS), ("n_below", C.c_int32),
+                ("below", C.c_float * NND_STEREO_EVAL_MAX_THRESHOLDS), ("num_outputs", C.c_int32),
+                ("outputs", StereoEvalOutput * NND_STEREO_EVAL_MAX_OUTPUTS)]
+
+
 # name -> (restype, argtypes); mirrors include/nndepth_amd.h one to one
 _P = C.c_void_p
 _I = C.c_int
@@ -175,6 +193,10 @@ SIGNATURES = {
     "nnd_depth_eval_workspace_bytes": (C.c_int64, [_I]),
     "nnd_depth_eval": (_I, [_P, _P, _P, _I, _I, _I, C.c_float, _P, C.c_int64, _P, _P]),
     "nnd_depth_eval_accumulate": (_I, [_P, _P, _P, _P]),
+    "nnd_stereo_eval_workspace_bytes": (C.c_int64, [_I]),
+    "nnd_stereo_eval": (_I, [C.POINTER(StereoEvalDesc), _P, C.c_int64, _P, _P]),
+    "nnd_stereo_eval_accumulate": (_I, [_P, _I, _P, _P]),
+    "nnd_min_pool_nearest": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_view_range_workspace_bytes": (C.c_int64, [_I]),
     "nnd_view_range": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "nnd_colorize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, C.c_double, _I, C.c_double, _I, _P, _I, _P, _P]),

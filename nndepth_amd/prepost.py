@@ -1,13 +1,15 @@
 """Device-side pre- and post-processing: drop-ins for `preprocess_frame`
 (nndepth/models/raft_stereo/scripts/inference.py:55-60), `Padder` (nndepth/data/dataloaders/utils.py:5-21) and
-`EvalCriterion` (nndepth/models/raft_stereo/scripts/evaluate.py:29-83) that keep the frames and the disparity on the GPU, and
-for `DepthEvalCriterion` with its dataset mean (nndepth/models/midas/scripts/evaluate.py:38-211, 300-312) on the monocular side."""
+`EvalCriterion` (nndepth/models/raft_stereo/scripts/evaluate.py:29-83) that keep the frames and the disparity on the GPU, for
+the stereo scripts' criterion, sequence loss and dataset mean over every output of a forward (`StereoEvalCriterion`,
+`StereoEvalMean`: evaluate.py:48-83, 141-169, loss.py:15-52), and for `DepthEvalCriterion` with its dataset mean
+(nndepth/models/midas/scripts/evaluate.py:38-211, 300-312) on the monocular side."""
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from ._lib import NndError, check, lib
+from ._lib import NND_STEREO_EVAL_MAX_OUTPUTS, NND_STEREO_EVAL_MAX_THRESHOLDS, NndError, StereoEvalDesc, check, lib
 from .ops import _dev, _mask_bytes, _p, _stream
 
 
@@ -63,10 +65,25 @@ class Padder:
         return replicate_pad(x, [-self._pad[0], -self._pad[1], -self._pad[2], -self._pad[3]])
 
 
+def downsample_gt(disp_gt: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """The ground truth at a coarse output's size, as the reference's criterion and losses make it (evaluate.py:63-66):
+    scale = W // size[1]; F.interpolate(-F.max_pool2d(-disp_gt, scale) / scale, size=size), bit for bit, in one kernel."""
+    d = _dev(disp_gt)
+    if disp_gt.dim() != 4:
+        raise NndError(f"downsample_gt: the ground truth is (B,C,H,W); got {tuple(disp_gt.shape)}")
+    gt = disp_gt.contiguous()
+    B, Cc, H, W = gt.shape
+    h, w = int(size[0]), int(size[1])
+    out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_min_pool_nearest(_p(gt), _p(out), B, Cc, H, W, h, w, _stream(d)), "min_pool_nearest")
+    return out
+
+
 class EvalCriterion:
     """EPE and dX metrics computed on the device; returns the same dict of floats as the reference (one D2H of a few
     floats instead of the disparity maps).  Inputs of different sizes are first brought to the prediction's size the way
-    the reference does it (max-pool of the negated GT, nearest resize) with PyTorch ops on the device."""
+    the reference does it (max-pool of the negated GT, nearest resize) by `downsample_gt`."""
 
     def __init__(self, d_threshold: Optional[Dict[str, float]] = None, max_flow: int = 1000):
         self.d_threshold = d_threshold
@@ -75,9 +92,7 @@ class EvalCriterion:
     def __call__(self, disp_gt: torch.Tensor, disp_pred: torch.Tensor, valid_mask: Optional[torch.Tensor] = None):
         d = _dev(disp_gt, disp_pred)
         if disp_pred.shape[-2:] != disp_gt.shape[-2:]:
-            scale = disp_gt.shape[-1] // disp_pred.shape[-1]
-            gt = -torch.nn.functional.max_pool2d(-disp_gt, kernel_size=scale) / scale
-            gt = torch.nn.functional.interpolate(gt, size=disp_pred.shape[-2:])
+            gt = downsample_gt(disp_gt, disp_pred.shape[-2:])
         else:
             gt = disp_gt
         gt, pred = gt.contiguous(), disp_pred.contiguous()
@@ -101,6 +116,181 @@ class EvalCriterion:
         for i, k in enumerate(keys):
             metrics[k] = vals[2 + i]
         return metrics
+
+
+_STEREO_EVAL_WS: Dict[str, torch.Tensor] = {}  # per device, grown to the largest number of outputs seen
+
+
+def _stereo_eval_workspace(device: torch.device, n_outputs: int) -> torch.Tensor:
+    n = int(lib.nnd_stereo_eval_workspace_bytes(n_outputs))
+    if n <= 0:
+        check(n, "stereo_eval_workspace_bytes")
+    ws = _STEREO_EVAL_WS.get(str(device))
+    if ws is None or ws.numel() * 8 < n:
+        ws = _STEREO_EVAL_WS[str(device)] = torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def _threshold_dict(d: Optional[Dict[str, float]], what: str) -> Dict[str, float]:
+    d = dict(d) if d else {}
+    if len(d) > NND_STEREO_EVAL_MAX_THRESHOLDS:
+        raise NndError(f"StereoEvalCriterion: at most {NND_STEREO_EVAL_MAX_THRESHOLDS} {what} thresholds; got {len(d)}")
+    return {str(k): float(v) for k, v in d.items()}
+
+
+StereoOutputs = Union[torch.Tensor, Sequence[torch.Tensor], Sequence[Dict[str, torch.Tensor]]]
+
+
+class StereoEvalCriterion:
+    """The stereo scripts' criterion for every output of a forward in one call on the device (nnd_stereo_eval states every step):
+    per output the EPE, the number of valid pixels, the sequence loss's L1 term, the fraction of valid pixels with epe > each
+    `d_threshold` (evaluate.py:82) and with epe < each `below` (loss.py:47-50), in float64; and the value of the sequence loss,
+    sum_i gamma^(N-1-i) l1_i.  A coarse output is scored against the ground truth brought to its size the reference's way; a
+    1-channel ground truth serves every channel of an output (the reference's broadcasting in cre_stereo/scripts/evaluate.py)."""
+
+    def __init__(self, d_threshold: Optional[Dict[str, float]] = None, below: Optional[Dict[str, float]] = None, max_flow: float = 1000,
+                 gamma: float = 0.8):
+        self.d_threshold = _threshold_dict(d_threshold, "d_threshold")
+        self.below = _threshold_dict(below, "below")
+        self.max_flow = max_flow
+        self.gamma = gamma
+        self.columns: Tuple[str, ...] = ("epe", "count", "l1") + tuple(self.d_threshold) + tuple(self.below)
+        if len(set(self.columns)) != len(self.columns):
+            raise NndError(f"StereoEvalCriterion: the column names {self.columns} are not distinct")
+
+    @staticmethod
+    def _maps(outputs: StereoOutputs) -> List[torch.Tensor]:
+        what = "StereoEvalCriterion"
+        if torch.is_tensor(outputs):
+            outputs = [outputs]
+        maps = [o["up_disp"] if isinstance(o, dict) else o for o in outputs]
+        if not 0 < len(maps) <= NND_STEREO_EVAL_MAX_OUTPUTS:
+            raise NndError(f"{what}: 1 .. {NND_STEREO_EVAL_MAX_OUTPUTS} outputs per call; got {len(maps)}")
+        for i, t in enumerate(maps):
+            if not torch.is_tensor(t) or t.dim() != 4:
+                raise NndError(f"{what}: output {i} is not a (B,C,h,w) tensor")
+        return maps
+
+    def describe(self, disp_gt: torch.Tensor, outputs: StereoOutputs, valid_mask: Optional[torch.Tensor] = None):
+        """(the call's nnd_stereo_eval_desc, its device, the tensors the descriptor points into: keep them until the call is
+        enqueued).  Every refusal of the Python seam happens here."""
+        what = "StereoEvalCriterion"
+        maps = self._maps(outputs)
+        if not torch.is_tensor(disp_gt) or disp_gt.dim() != 4:
+            raise NndError(f"{what}: disp_gt is a (B,C,H,W) tensor on the HIP device")
+        B, Cg, H, W = disp_gt.shape
+        for t in [disp_gt] + maps:
+            if t.dtype != torch.float32:
+                raise NndError(f"{what}: the maps are fp32; got {t.dtype}")
+        for i, t in enumerate(maps):
+            if t.shape[0] != B:
+                raise NndError(f"{what}: output {i} has batch size {t.shape[0]}, the ground truth {B}")
+            if Cg != 1 and Cg != t.shape[1]:
+                raise NndError(f"{what}: output {i} has {t.shape[1]} channels, the ground truth {Cg} (equal, or 1 to broadcast)")
+        mask = None
+        if valid_mask is not None:
+            if valid_mask.dtype not in (torch.bool, torch.uint8):
+                raise NndError(f"{what}: valid_mask is torch.bool or torch.uint8; got {valid_mask.dtype}")
+            ms = tuple(valid_mask.shape)
+            if not ((len(ms) == 4 and ms[1] == 1) or len(ms) == 3) or ms[0] != B:
+                raise NndError(f"{what}: valid_mask is (B,1,h,w) or (B,h,w) with B = {B}; got {ms}")
+            for i, t in enumerate(maps):
+                if tuple(t.shape[-2:]) != ms[-2:]:
+                    raise NndError(f"{what}: valid_mask is {ms[-2]}x{ms[-1]} but output {i} is {t.shape[-2]}x{t.shape[-1]}: a mask needs "
+                                   "every output of the call at its size")
+        d = _dev(disp_gt, *maps)  # the shapes are judged first: those refusals read the same wherever the tensors live
+        if valid_mask is not None:
+            if valid_mask.device != d:
+                raise NndError(f"{what}: valid_mask is on {valid_mask.device}, the maps on {d} (no CPU fallback exists)")
+            mask = valid_mask.contiguous()
+            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        gt = disp_gt.contiguous()
+        maps = [t if (t.stride(3) == 1 or t.shape[3] == 1) else t.contiguous() for t in maps]  # kept alive across the call
+        desc = StereoEvalDesc()
+        desc.gt, desc.B, desc.Cg, desc.H, desc.W = gt.data_ptr(), B, Cg, H, W
+        if mask is not None:
+            desc.mask, desc.mask_h, desc.mask_w = mask.data_ptr(), mask.shape[-2], mask.shape[-1]
+        desc.gamma, desc.max_flow = float(self.gamma), float(self.max_flow)
+        desc.n_above, desc.n_below = len(self.d_threshold), len(self.below)
+        for k, v in enumerate(self.d_threshold.values()):
+            desc.above[k] = v
+        for k, v in enumerate(self.below.values()):
+            desc.below[k] = v
+        desc.num_outputs = len(maps)
+        for i, t in enumerate(maps):
+            o = desc.outputs[i]
+            o.data, o.C, o.h, o.w = t.data_ptr(), t.shape[1], t.shape[2], t.shape[3]
+            o.stride_b, o.stride_c, o.stride_row = t.stride(0), t.stride(1), t.stride(2)
+        return desc, d, (gt, maps, mask)
+
+    def _run(self, disp_gt: torch.Tensor, outputs: StereoOutputs, valid_mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int]:
+        """The N*K + 1 doubles of nnd_stereo_eval on the device, and N."""
+        desc, d, keep = self.describe(disp_gt, outputs, valid_mask)
+        n = desc.num_outputs
+        ws = _stereo_eval_workspace(d, n)
+        out = torch.empty(n * len(self.columns) + 1, dtype=torch.float64, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_stereo_eval(C.byref(desc), _p(ws), ws.numel() * 8, _p(out), _stream(d)), "stereo_eval")
+        del keep
+        return out, n
+
+    def metrics_tensor(self, disp_gt: torch.Tensor, outputs: StereoOutputs,
+                       valid_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """((N,K) float64 in the order of `columns`, () float64: the sequence loss), both on the device.  `outputs`: one tensor, a
+        list of tensors, or the list of {"up_disp": t} dicts a model's forward() returns; slices of a stacked tensor and cropped
+        views are read where they lie.  No host synchronisation: 1 + (number of distinct output sizes) launches."""
+        out, n = self._run(disp_gt, outputs, valid_mask)
+        return out[:-1].view(n, len(self.columns)), out[-1]
+
+    def __call__(self, disp_gt: torch.Tensor, outputs: StereoOutputs, valid_mask: Optional[torch.Tensor] = None) -> List[Dict[str, float]]:
+        """One dict of floats per output, keys = `columns`; one device-to-host copy."""
+        out, n = self._run(disp_gt, outputs, valid_mask)
+        vals = out.cpu().tolist()
+        K = len(self.columns)
+        return [dict(zip(self.columns, vals[i * K:(i + 1) * K])) for i in range(n)]
+
+
+class StereoEvalMean:
+    """The stereo evaluation loop's mean over the dataset (evaluate.py:141-169) kept on the device: `update` enqueues the pair's
+    criterion and adds its doubles to running sums; `result` / `curve` copy the sums once and divide by the number of updates,
+    which is np.mean of the per-pair values: a NaN (a pair without a valid pixel) propagates, as it does in the reference."""
+
+    def __init__(self, d_threshold: Optional[Dict[str, float]] = None, below: Optional[Dict[str, float]] = None, max_flow: float = 1000,
+                 gamma: float = 0.8):
+        self.criterion = StereoEvalCriterion(d_threshold, below, max_flow, gamma)
+        self._sums: Optional[torch.Tensor] = None  # (N*K + 1,) float64
+        self._sizes: Optional[List[Tuple[int, ...]]] = None
+        self._updates = 0
+
+    def update(self, disp_gt: torch.Tensor, outputs: StereoOutputs, valid_mask: Optional[torch.Tensor] = None) -> None:
+        sizes = [tuple(t.shape[1:]) for t in self.criterion._maps(outputs)]
+        if self._sizes is not None and sizes != self._sizes:
+            raise NndError(f"StereoEvalMean: this update has {len(sizes)} outputs of sizes {sizes}, the first had {len(self._sizes)} of "
+                           f"sizes {self._sizes}")
+        m, _ = self.criterion._run(disp_gt, outputs, valid_mask)
+        if self._sums is None:
+            self._sums, self._sizes = torch.zeros(m.numel(), dtype=torch.float64, device=m.device), sizes
+        elif self._sums.device != m.device:
+            raise NndError(f"StereoEvalMean: pairs on {self._sums.device} and on {m.device}")
+        with torch.cuda.device(m.device):
+            check(lib.nnd_stereo_eval_accumulate(_p(m), m.numel(), _p(self._sums), _stream(m.device)), "stereo_eval_accumulate")
+        self._updates += 1
+
+    def curve(self) -> List[Dict[str, float]]:
+        """The dataset mean of every column, per output index."""
+        if self._sums is None:
+            return []
+        vals = (self._sums.cpu().numpy() / self._updates).tolist()
+        cols = self.criterion.columns
+        return [dict(zip(cols, vals[i * len(cols):(i + 1) * len(cols)])) for i in range(len(self._sizes))]
+
+    def result(self) -> Dict[str, float]:
+        """The reference script's table for the last output: epe and the threshold metrics, each the mean of the per-pair values."""
+        keys = ("epe",) + self.criterion.columns[3:]
+        if self._sums is None:
+            return {k: float("nan") for k in keys}  # np.mean of an empty list
+        last = self.curve()[-1]
+        return {k: last[k] for k in keys}
 
 
 DEPTH_METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "delta3", "ssi_mae", "ssi_rmse")
