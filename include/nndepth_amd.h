@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define NND_VERSION 104 /* 0.1.4: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning) */
+#define NND_VERSION 105 /* 0.1.5: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning); 105 the single-output EPE criterion's two symbols (the entry point and its workspace query) are removed: nnd_stereo_eval with one output is that criterion */
 
 /* Descriptors start with `struct_size` = sizeof(the descriptor type) of the header the caller was compiled against; every entry
  * point that takes one refuses another size (NND_ERR_INVALID), so a caller and a library of different versions cannot
@@ -522,18 +522,11 @@ int nnd_midas_conv_add(int Cout, int Cin, int k, const float* packed_dev, const 
  *     src is float (B,C,h,w), or — src_is_u8_hwc != 0 — the decoded image itself, uint8 (B,h,w,C).
  * nnd_replicate_pad    : Padder.pad / unpad  nndepth/data/dataloaders/utils.py:5-21
  *     dst (B,C,H+top+bottom,W+left+right) = F.pad(src, (left,right,top,bottom), mode="replicate"); negative values crop.
- * nnd_epe_metrics      : EvalCriterion.__call__  nndepth/models/raft_stereo/scripts/evaluate.py:48-83 (equal-size inputs)
- *     epe = sqrt(sum_c (pred-gt)^2); valid = sqrt(sum_c gt^2) < max_flow (and valid_mask != 0 if given, (B,H,W) bytes);
- *     out[0] = mean epe over valid, out[1] = number of valid pixels, out[2+k] = fraction of valid pixels with
- *     epe > thresholds[k].  `thresholds` is a HOST array (<= 4 entries); `workspace` = nnd_epe_metrics_workspace_bytes()
- *     device bytes; `out` = 2 + num_thresholds device floats.  Deterministic (two-stage double-precision reduction).   */
+ *   (EvalCriterion.__call__ of raft_stereo/scripts/evaluate.py:48-83 is nnd_stereo_eval with one output, below.)        */
 int nnd_resize_normalize(const void* src, int src_is_u8_hwc, float* dst, int B, int C, int h, int w, int H, int W,
                          float sub, float div, void* stream);
 int nnd_replicate_pad(const float* src, float* dst, int B, int C, int H, int W, int left, int right, int top, int bottom,
                       void* stream);
-int64_t nnd_epe_metrics_workspace_bytes(void);
-int nnd_epe_metrics(const float* disp_gt, const float* disp_pred, const unsigned char* valid_mask, int B, int C, int H, int W,
-                    float max_flow, const float* thresholds_host, int num_thresholds, void* workspace, float* out, void* stream);
 
 /* ------------------------------------------------------------- monocular evaluation criterion on the device (additions within 104)
  * nnd_depth_eval : DepthEvalCriterion.__call__  nndepth/models/midas/scripts/evaluate.py:48-211 with scale_shift_estimation,

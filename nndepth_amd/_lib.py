@@ -188,8 +188,6 @@ SIGNATURES = {
     "nnd_midas_conv_add": (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "nnd_resize_normalize": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_replicate_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "nnd_epe_metrics_workspace_bytes": (C.c_int64, []),
-    "nnd_epe_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_float, C.POINTER(C.c_float), _I, _P, _P, _P]),
     "nnd_depth_eval_workspace_bytes": (C.c_int64, [_I]),
     "nnd_depth_eval": (_I, [_P, _P, _P, _I, _I, _I, C.c_float, _P, C.c_int64, _P, _P]),
     "nnd_depth_eval_accumulate": (_I, [_P, _P, _P, _P]),

@@ -7,7 +7,7 @@
 //
 // The criterion is a chain of masked reductions in which each needs the one before it, so it is a chain of small launches
 // (grid = (G blocks, B samples) unless said otherwise), every one a per-block partial in double that the NEXT launch adds up in
-// index order (every block redundantly, G <= 64 values), as epe_partial_kernel / epe_final_kernel of prepost.hip do:
+// index order (every block redundantly, G <= 64 values), as se_partial_kernel / se_final_kernel of stereo_eval.hip do:
 //
 //   1 fit_mean    n, sum p, sum g over the ORIGINAL mask                                  -> P1[b][blk][3]
 //   2 fit_moment  means from P1; sum (p-pm)^2, sum (p-pm)(g-gm)                           -> P2[b][blk][2]

@@ -1,14 +1,11 @@
-// Pre- / post-processing of the inference and evaluation scripts on the device: no host round trip
-// between decoding a frame and the first convolution, or between the last upsample and the metric.
+// Pre- / post-processing of the inference scripts on the device: no host round trip between decoding a
+// frame and the first convolution.
 //
 //   resize_normalize : preprocess_frame  nndepth/models/raft_stereo/scripts/inference.py:55-60
 //                      F.interpolate(frame, HW, mode="bilinear") (align_corners=False, no antialias) then (x - 127.5) / 127.5;
 //                      source either float NCHW or the decoded uint8 HWC image itself
 //   replicate_pad    : Padder.pad / unpad   nndepth/data/dataloaders/utils.py:5-21 (F.pad mode="replicate"; crop)
-//   epe_metrics      : EvalCriterion.__call__  nndepth/models/raft_stereo/scripts/evaluate.py:48-83
-//                      epe = sqrt(sum_c (pred - gt)^2), valid = |gt| < max_flow (& mask), mean EPE and fraction of
-//                      valid pixels with epe > threshold_k
-// All HBM-bound element-wise / reduction kernels.  Compiled with -ffp-contract=off (the bilinear weights follow
+// Both HBM-bound element-wise kernels.  Compiled with -ffp-contract=off (the bilinear weights follow
 // ATen's compute_source_index_and_lambda step by step).
 #include "common.h"
 #include "bilinear.h"
@@ -60,65 +57,6 @@ __global__ void __launch_bounds__(256) replicate_pad_kernel(const float* __restr
     dst[(long)blockIdx.y * Ho * Wo + idx] = src[(long)blockIdx.y * H * W + (long)sy * W + sx];
 }
 
-constexpr int MAX_THR = 4;
-struct EpeArgs {
-    float thr[MAX_THR];
-    int nthr;
-    float max_flow;
-};
-
-// pass 1: per-block partial sums (double) of [epe, count, count(epe > thr_k)...]; pass 2: one block adds them in index order
-__global__ void __launch_bounds__(256) epe_partial_kernel(const float* __restrict__ gt, const float* __restrict__ pred,
-                                                          const unsigned char* __restrict__ mask, int C, long HW, long total,
-                                                          EpeArgs a, double* __restrict__ partial) {
-    __shared__ double sh[256][2 + MAX_THR];
-    double acc[2 + MAX_THR];
-#pragma unroll
-    for (int i = 0; i < 2 + MAX_THR; ++i) acc[i] = 0.0;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long b = idx / HW, p = idx - b * HW;
-        float se = 0.f, sg = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float g = gt[(b * C + c) * HW + p], d = pred[(b * C + c) * HW + p] - g;
-            se += d * d;
-            sg += g * g;
-        }
-        const float epe = sqrtf(se);
-        bool valid = sqrtf(sg) < a.max_flow;
-        if (mask) valid = valid && mask[idx] != 0;
-        if (valid) {
-            acc[0] += (double)epe;
-            acc[1] += 1.0;
-            for (int k = 0; k < a.nthr; ++k) acc[2 + k] += epe > a.thr[k] ? 1.0 : 0.0;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2 + MAX_THR; ++i) sh[threadIdx.x][i] = acc[i];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-#pragma unroll
-            for (int i = 0; i < 2 + MAX_THR; ++i) sh[threadIdx.x][i] += sh[threadIdx.x + s][i];
-        __syncthreads();
-    }
-    if (threadIdx.x < 2 + MAX_THR) partial[(long)blockIdx.x * (2 + MAX_THR) + threadIdx.x] = sh[0][threadIdx.x];
-}
-
-__global__ void epe_final_kernel(const double* __restrict__ partial, int nblocks, int nthr, float* __restrict__ out) {
-    const int i = threadIdx.x;  // 0: epe sum, 1: count, 2..: exceed counts
-    if (i >= 2 + nthr) return;
-    double s = 0.0;
-    for (int b = 0; b < nblocks; ++b) s += partial[(long)b * (2 + MAX_THR) + i];
-    __shared__ double tot[2 + MAX_THR];
-    tot[i] = s;
-    __syncthreads();
-    if (i == 0) out[0] = (float)(tot[0] / tot[1]);
-    else if (i == 1) out[1] = (float)tot[1];
-    else out[i] = (float)(tot[i] / tot[1]);
-}
-
-constexpr int EPE_BLOCKS = 512;
-
 }  // namespace nnd
 
 using namespace nnd;
@@ -142,29 +80,6 @@ int nnd_replicate_pad(const float* src, float* dst, int B, int C, int H, int W, 
     NND_REQUIRE(Ho > 0 && Wo > 0, "replicate_pad: padding (%d,%d,%d,%d) leaves nothing of a %dx%d map", left, right, top, bottom, H, W);
     hipLaunchKernelGGL(replicate_pad_kernel, dim3((unsigned)cdiv64((int64_t)Ho * Wo, 256), B * C), dim3(256), 0, (hipStream_t)stream,
                        src, dst, H, W, Ho, Wo, left, top);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
-}
-
-int64_t nnd_epe_metrics_workspace_bytes(void) { return (int64_t)EPE_BLOCKS * (2 + MAX_THR) * sizeof(double); }
-
-int nnd_epe_metrics(const float* disp_gt, const float* disp_pred, const unsigned char* valid_mask, int B, int C, int H, int W,
-                    float max_flow, const float* thresholds, int num_thresholds, void* workspace, float* out, void* stream) {
-    NND_REQUIRE(disp_gt && disp_pred && workspace && out, "epe_metrics: null pointer");
-    NND_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "epe_metrics: bad shape");
-    NND_REQUIRE(num_thresholds >= 0 && num_thresholds <= MAX_THR && (num_thresholds == 0 || thresholds),
-                "epe_metrics: at most %d thresholds", MAX_THR);
-    EpeArgs a;
-    a.nthr = num_thresholds;
-    a.max_flow = max_flow;
-    for (int k = 0; k < MAX_THR; ++k) a.thr[k] = k < num_thresholds ? thresholds[k] : 0.f;
-    const long HW = (long)H * W, total = (long)B * HW;
-    const int nblocks = (int)(cdiv64(total, 256) < EPE_BLOCKS ? cdiv64(total, 256) : EPE_BLOCKS);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(epe_partial_kernel, dim3(nblocks), dim3(256), 0, s, disp_gt, disp_pred, valid_mask, C, HW, total, a,
-                       (double*)workspace);
-    NND_LAUNCH_CHECK();
-    hipLaunchKernelGGL(epe_final_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, nblocks, num_thresholds, out);
     NND_LAUNCH_CHECK();
     return NND_OK;
 }

@@ -3,7 +3,7 @@
 // to the host.
 //
 //   view_range      : min / max per batch element of the map get_view colours (|disp| with occluded pixels at 0; depth over
-//                     its valid pixels), two passes like epe_partial_kernel / epe_final_kernel, result left in device memory
+//                     its valid pixels), two passes like se_partial_kernel / se_final_kernel of stereo_eval.hip, result left in device memory
 //   colorize        : matplotlib.colors.Normalize(vmin, vmax, clip=True) + Colormap.__call__ + (rgb * 255).astype(uint8) as
 //                     one closed form.  matplotlib normalises an fp32 map in float64 (its vmin / vmax are float64 scalars), and
 //                     the table index is a truncation, so the normalisation here is float64 too: in fp32 a handful of pixels

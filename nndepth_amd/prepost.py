@@ -7,6 +7,7 @@ the stereo scripts' criterion, sequence loss and dataset mean over every output 
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from ._lib import NND_STEREO_EVAL_MAX_OUTPUTS, NND_STEREO_EVAL_MAX_THRESHOLDS, NndError, StereoEvalDesc, check, lib
@@ -81,53 +82,46 @@ def downsample_gt(disp_gt: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 
 
 class EvalCriterion:
-    """EPE and dX metrics computed on the device; returns the same dict of floats as the reference (one D2H of a few
-    floats instead of the disparity maps).  Inputs of different sizes are first brought to the prediction's size the way
-    the reference does it (max-pool of the negated GT, nearest resize) by `downsample_gt`."""
+    """EPE and dX metrics computed on the device; returns the same dict of floats as the reference (one D2H of a few doubles
+    instead of the disparity maps).  The single-output front of `StereoEvalCriterion`: a coarse prediction is scored against the
+    ground truth brought to its size the reference's way, a 1-channel ground truth serves both channels of a 2-channel map."""
 
     def __init__(self, d_threshold: Optional[Dict[str, float]] = None, max_flow: int = 1000):
         self.d_threshold = d_threshold
         self.max_flow = max_flow
 
     def __call__(self, disp_gt: torch.Tensor, disp_pred: torch.Tensor, valid_mask: Optional[torch.Tensor] = None):
+        keys = list(self.d_threshold) if self.d_threshold else []
+        # the caller's keys stay here (any name, "count" too); the columns get positional names
+        crit = StereoEvalCriterion({f"above{i}": self.d_threshold[k] for i, k in enumerate(keys)}, None, self.max_flow)
         d = _dev(disp_gt, disp_pred)
-        if disp_pred.shape[-2:] != disp_gt.shape[-2:]:
-            gt = downsample_gt(disp_gt, disp_pred.shape[-2:])
-        else:
-            gt = disp_gt
-        gt, pred = gt.contiguous(), disp_pred.contiguous()
-        B, Cc, H, W = pred.shape
-        keys = list(self.d_threshold.keys()) if self.d_threshold else []
-        if len(keys) > 4:
-            raise NndError("EvalCriterion: at most 4 thresholds per call")
-        thr = (C.c_float * max(1, len(keys)))(*[float(self.d_threshold[k]) for k in keys])
         mask = None
-        if valid_mask is not None:
+        if valid_mask is not None:  # any dtype, shape and device with B*h*w elements
+            B, _, h, w = disp_pred.shape
             mask = valid_mask.to(device=d, dtype=torch.uint8).contiguous()
-            if mask.numel() != B * H * W:
-                raise NndError(f"EvalCriterion: valid_mask has {mask.numel()} elements, expected {B * H * W}")
-        ws = torch.empty(int(lib.nnd_epe_metrics_workspace_bytes()), dtype=torch.uint8, device=d)
-        out = torch.empty(2 + len(keys), dtype=torch.float32, device=d)
-        with torch.cuda.device(d):
-            check(lib.nnd_epe_metrics(_p(gt), _p(pred), _p(mask), B, Cc, H, W, float(self.max_flow), thr, len(keys), _p(ws), _p(out),
-                                      _stream(d)), "epe_metrics")
-        vals = out.cpu().tolist()
+            if mask.numel() != B * h * w:
+                raise NndError(f"EvalCriterion: valid_mask has {mask.numel()} elements, expected {B * h * w}")
+            mask = mask.view(B, h, w)
+        out, _ = crit._run(disp_gt, disp_pred, mask)
+        vals = out.cpu().numpy().astype(np.float32).tolist()  # the reference's results are fp32
         metrics = {"epe": vals[0]}
         for i, k in enumerate(keys):
-            metrics[k] = vals[2 + i]
+            metrics[k] = vals[3 + i]
         return metrics
 
 
 _STEREO_EVAL_WS: Dict[str, torch.Tensor] = {}  # per device, grown to the largest number of outputs seen
 
 
-def _stereo_eval_workspace(device: torch.device, n_outputs: int) -> torch.Tensor:
-    n = int(lib.nnd_stereo_eval_workspace_bytes(n_outputs))
-    if n <= 0:
-        check(n, "stereo_eval_workspace_bytes")
-    ws = _STEREO_EVAL_WS.get(str(device))
-    if ws is None or ws.numel() * 8 < n:
-        ws = _STEREO_EVAL_WS[str(device)] = torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
+def _cached_workspace(cache: Dict[str, torch.Tensor], device: torch.device, nbytes: int) -> torch.Tensor:
+    """`cache`'s float64 buffer of `device`, grown to the `nbytes` a *_workspace_bytes of the library answered (negative: its refusal,
+    which nnd_last_error names)."""
+    nbytes = int(nbytes)
+    if nbytes <= 0:
+        check(nbytes, "workspace_bytes")
+    ws = cache.get(str(device))
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = cache[str(device)] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
     return ws
 
 
@@ -227,7 +221,7 @@ class StereoEvalCriterion:
         """The N*K + 1 doubles of nnd_stereo_eval on the device, and N."""
         desc, d, keep = self.describe(disp_gt, outputs, valid_mask)
         n = desc.num_outputs
-        ws = _stereo_eval_workspace(d, n)
+        ws = _cached_workspace(_STEREO_EVAL_WS, d, lib.nnd_stereo_eval_workspace_bytes(n))
         out = torch.empty(n * len(self.columns) + 1, dtype=torch.float64, device=d)
         with torch.cuda.device(d):
             check(lib.nnd_stereo_eval(C.byref(desc), _p(ws), ws.numel() * 8, _p(out), _stream(d)), "stereo_eval")
@@ -297,16 +291,6 @@ DEPTH_METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "d
 _DEPTH_EVAL_WS: Dict[str, torch.Tensor] = {}  # per device, grown to the largest batch seen
 
 
-def _depth_eval_workspace(device: torch.device, B: int) -> torch.Tensor:
-    n = int(lib.nnd_depth_eval_workspace_bytes(B))
-    if n <= 0:
-        check(n, "depth_eval_workspace_bytes")
-    ws = _DEPTH_EVAL_WS.get(str(device))
-    if ws is None or ws.numel() * 8 < n:
-        ws = _DEPTH_EVAL_WS[str(device)] = torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
-    return ws
-
-
 class DepthEvalCriterion:
     """The monocular evaluation criterion computed on the device: scale / shift alignment per sample, abs_rel, sq_rel, rmse,
     rmse_log, delta1..3 and the two scale-and-shift-invariant errors, in float64 (nnd_depth_eval states every step).  Returns
@@ -333,7 +317,7 @@ class DepthEvalCriterion:
         pred, gt = depth_pred.contiguous(), depth_gt.contiguous()
         mask = _mask_bytes(valid_mask, pred, what)
         B, _, H, W = pred.shape
-        ws = _depth_eval_workspace(d, B)
+        ws = _cached_workspace(_DEPTH_EVAL_WS, d, lib.nnd_depth_eval_workspace_bytes(B))
         out = torch.empty(10, dtype=torch.float64, device=d)
         with torch.cuda.device(d):
             check(lib.nnd_depth_eval(_p(pred), _p(gt), _p(mask), B, H, W, float(self.max_depth), _p(ws), ws.numel() * 8, _p(out),

@@ -7,8 +7,9 @@ Workload 2 (a CREStereo-shaped forward): 40 two-channel outputs, 10 at 270 x 480
 1-channel 1080 x 1920 ground truth, no mask.
   metrics_tensor_ms  StereoEvalCriterion.metrics_tensor: the launches alone (events; no host synchronisation inside)
   call_ms            StereoEvalCriterion.__call__: the launches and the one copy of N*K + 1 doubles, wall time
-  eval_criterion_ms  workload 1 only: one EvalCriterion call per output on the same maps (each allocates, launches twice and
-                     synchronises), wall time; it returns epe and the `above` fractions only
+  eval_criterion_ms  workload 1 only: one EvalCriterion call per output on the same maps (each is a single-output
+                     StereoEvalCriterion call: fills a descriptor, launches twice, copies K + 1 doubles and synchronises), wall
+                     time; it returns epe and the `above` fractions only
   eager_ms           the reference's lines (evaluate.py:63-82, loss.py:23-33, 47-50) as PyTorch ops on the device in fp32, one
                      copy at the end, wall time
 `bytes` is the algorithmic traffic: every output read once, the ground truth and the mask once per size group;
@@ -18,7 +19,7 @@ final).  The reference itself does not travel with the repository, so it is not 
 Method: 5 warm-up calls, then the median of 30 timed calls (10 for the eager route), min and max beside it.  The only
 requirement: on workload 1, call_ms is below eval_criterion_ms (asserted).
 
-    timeout -k 10 600 python scripts/bench_stereo_eval.py [--out profiles/stereo_eval_bench.jsonl]
+    timeout -k 10 600 python scripts/bench_stereo_eval.py [--out profiles/stereo_eval_bench.jsonl] [--note TEXT]
 """
 import argparse
 import json
@@ -141,6 +142,7 @@ def measure(name, gt, outs, mask, with_eval_criterion):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stereo_eval_bench.jsonl"))
+    ap.add_argument("--note", default=None, help="kept in every line, e.g. the commit measured")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_stereo_eval.py needs the MI355X"
     gen = torch.Generator(device=DEV)
@@ -155,6 +157,8 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a") as f:
         for row in rows:
+            if args.note:
+                row["note"] = args.note
             print(json.dumps(row), flush=True)
             f.write(json.dumps(row) + "\n")
     r = rows[0]

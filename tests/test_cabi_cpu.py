@@ -25,8 +25,10 @@ def test_library_exports_every_declared_symbol():
     raw = C.CDLL(_lib.LIB_PATH)
     for s in syms:
         assert hasattr(raw, s), f"{s} declared in include/nndepth_amd.h but not exported"
+    for s in ("nnd_epe_metrics", "nnd_epe_metrics_workspace_bytes"):  # retired with 105: nnd_stereo_eval with one output
+        assert not hasattr(raw, s), f"{s} is still exported"
     assert set(_lib.SIGNATURES) == set(syms), "ctypes table and header out of sync"
-    assert _lib.lib.nnd_version() == 104
+    assert _lib.lib.nnd_version() == 105
     assert _lib.lib.nnd_device_count() >= 0  # must not raise / abort on a CPU-only host
 
 

@@ -379,12 +379,25 @@ def test_loftr_shape_history(ops):
 
 # ------------------------------------------------------------------------------------------------ the small workspaces
 def test_eval_criterion(ops, monkeypatch):
-    """A mask and two thresholds at 2x2x37x53; its byte workspace gets the patterns' bytes."""
-    from nndepth_amd.prepost import EvalCriterion
+    """A mask and two thresholds at 2x2x37x53, the cached per-device workspace replaced by exactly the bytes the library asks for
+    one output."""
+    from nndepth_amd import prepost
+    from nndepth_amd._lib import lib
     gt, pred = rnd("epe/gt", 2, 2, 37, 53, scale=40.0), rnd("epe/pred", 2, 2, 37, 53, scale=40.0)
     mask = rnd("epe/mask", 2, 1, 37, 53) > -0.4
-    crit = EvalCriterion({"d1": 1.0, "d3": 3.0})
-    check_prior_contents(ops, monkeypatch, lambda kind: crit(gt, pred, mask), raw_bytes=True)
+    crit = prepost.EvalCriterion({"d1": 1.0, "d3": 3.0})
+    nbytes = int(lib.nnd_stereo_eval_workspace_bytes(1))
+    assert nbytes > 0 and nbytes % 8 == 0
+
+    def call(kind):
+        ws = prepost._STEREO_EVAL_WS[DEV] = hu.aligned_buffer(nbytes // 8, kind, DEV, seed=7, dtype=torch.float64)
+        out = crit(gt, pred, mask)
+        assert prepost._STEREO_EVAL_WS[DEV].data_ptr() == ws.data_ptr()
+        return out
+    try:
+        check_prior_contents(ops, monkeypatch, call)
+    finally:
+        prepost._STEREO_EVAL_WS.pop(DEV, None)
 
 
 def test_depth_eval_criterion(ops, monkeypatch):

@@ -106,6 +106,47 @@ def test_eval_criterion_on_a_coarse_output_equals_the_parent_expression(inputs):
     assert list(got) == ["epe"] + list(sc.ABOVE) and got == want
 
 
+def _same32(got: dict, cols) -> bool:
+    """The dict's values are Python floats with the bits of the float64 columns `cols` rounded to fp32."""
+    want = [float(np.float32(x)) for x in cols]
+    return all(type(v) is float for v in got.values()) and _same(list(got.values()), want)
+
+
+@pytest.mark.parametrize("name", ["A", "B", "T", "C", "D", "M", "E", "G2", "G3", "G4", "V"])
+def test_eval_criterion_is_the_fp32_rounding_of_the_single_output_row(inputs, device_results, name):
+    """EvalCriterion is StereoEvalCriterion with one output: epe and the `above` columns of row 0 rounded to fp32, NaN where they
+    are NaN (E).  D: the 1-channel ground truth under a 2-channel map; G2, G3, G4: ragged pooling; V: a cropped view read where it
+    lies; B, E: a mask and the empty mask; M: a binding max_flow."""
+    from nndepth_amd.prepost import EvalCriterion
+    c = inputs[name]
+    assert len(c.outputs) == 1
+    got = EvalCriterion(dict(sc.ABOVE), max_flow=c.max_flow)(c.gt, c.outputs[0], c.mask)
+    row = device_results[name][0][0]
+    assert list(got) == ["epe"] + list(sc.ABOVE)
+    assert _same32(got, [row[0]] + list(row[3:3 + NA])), (name, got, row)
+    assert [math.isnan(v) for v in got.values()] == [bool(np.isnan(x)) for x in [row[0]] + list(row[3:3 + NA])]
+
+
+def test_eval_criterion_takes_a_mask_of_any_dtype_and_shape(inputs):
+    from nndepth_amd.prepost import EvalCriterion
+    c = inputs["B"]
+    crit = EvalCriterion(dict(sc.ABOVE), max_flow=c.max_flow)
+    assert c.mask.dtype == torch.bool and c.mask.dim() == 4 and c.mask.shape[1] == 1
+    want = crit(c.gt, c.outputs[0], c.mask)
+    for mask in (c.mask.float(), c.mask.reshape(-1)):
+        got = crit(c.gt, c.outputs[0], mask)
+        assert list(got) == list(want) and _same(list(got.values()), list(want.values()))
+
+
+def test_eval_criterion_keeps_a_threshold_key_that_is_a_column_name(inputs, device_results):
+    from nndepth_amd.prepost import EvalCriterion
+    c = inputs["A"]
+    thr = list(sc.ABOVE.values())[0]
+    got = EvalCriterion({"count": thr}, max_flow=c.max_flow)(c.gt, c.outputs[0], c.mask)
+    row = device_results["A"][0][0]
+    assert list(got) == ["epe", "count"] and _same32(got, [row[0], row[3]])
+
+
 @pytest.mark.parametrize("name", sc.NAMES)
 def test_at_least_as_close_to_float64_as_the_reference(fx, device_results, name):
     (d, dloss), w = device_results[name], fx[name]

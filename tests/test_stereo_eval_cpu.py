@@ -193,6 +193,10 @@ def test_python_seam_refuses_before_the_device():
         downsample_gt(torch.ones(1, 1, 8, 8), (4, 4))
     with pytest.raises(NndError, match="HIP device"):
         EvalCriterion()(torch.ones(1, 1, 8, 8), torch.ones(1, 1, 4, 4))
+    with pytest.raises(NndError, match="thresholds"):
+        EvalCriterion({f"d{i}": float(i) for i in range(9)})(x, x)
+    with pytest.raises(NndError, match="HIP device"):
+        EvalCriterion({"count": 1.0})(x, x)  # the caller's keys are not column names
     with pytest.raises(NndError, match="outputs"):
         crit(x, [x] * 65)
     with pytest.raises(NndError, match="outputs"):
