@@ -200,7 +200,10 @@ int nnd_convex_upsample(const float* flow, const float* mask, float* out,
  *     tanh epilogues and the layers behind them (nnd_update_block_forward: and at no output outside the reach of its convs);
  *   - nnd_update_block_scale_slots gives the float offsets of the layers' slots in the blob: slot[1] = 2^xs, so the valid range
  *     of layer i is |x| < 65504 / slot[1] (the Python engines expose it as `activation_ranges()`).
- * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once).                              */
+ * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once).
+ * arithmetic = 1 ("fp16", one piece) has the same scales, slots, calibration and range behaviour — finite up to 32 * M, inf / NaN
+ * beyond, never a finite wrong value — with the precision of ONE piece: 11 significand bits per operand while |x| >= M * 2^-25
+ * (an fp16 subnormal below: absolute error <= M * 2^-36).                                                                      */
 typedef struct {
     int32_t struct_size;   /* sizeof(nnd_update_block_desc) */
     int32_t hidden_dim;    /* 128; a multiple of 32, at most 192 (160 with 2 flow channels): flow_head.conv2 stages them all in LDS */
@@ -220,6 +223,13 @@ typedef struct {
                               (activations x4 while staged, weights per layer at pack time) that the kernel undoes after the K
                               loop, so the low pieces stay out of fp16's subnormals; the activation scale is per layer and
                               calibrated from data, see "fp16x2 activation range" above; csrc/split_arith.h.
+                              1 = "fp16", NOT an fp32-parity arithmetic (opt-in): each operand as ONE range-scaled fp16 piece,
+                              x^ = fp16_rne(x * 2^xs), w^ = fp16_rne(w * 2^s), one product per K step on v_mfma_f32_32x32x16_f16
+                              with fp32 accumulation — a third of the matrix work of 2, half its packed weight bytes.  11
+                              significand bits per operand (the bf16 autocast the reference's trainers validate under has 8);
+                              valid range as for 2: finite up to 32 x the calibrated maximum of a layer (uncalibrated: |x| <
+                              16376), inf / NaN in the output beyond.  Layers the 16-bit kernels do not build (Cin % 16 != 0)
+                              stay exact fp32 inside the blob, as under 2 and 3.
                               The packed blob is specific to the value. */
     int32_t split_layers;  /* 0: every convolution the split kernels are built for takes `arithmetic`; else bit i = convolution i
                               (nnd_conv_name) may take it, the others stay exact fp32 (diagnostic: bisecting a difference).  Part
@@ -241,6 +251,17 @@ int nnd_update_block_pack(const nnd_update_block_desc* desc, const float* const*
                           float* packed_host);
 /* workspace (floats) needed by nnd_update_block_forward / nnd_raft_stereo_refine          */
 int64_t nnd_update_block_workspace_floats(const nnd_update_block_desc* desc, int B, int H, int W);
+/* ONE convolution of the block, `which` in nnd_conv_name order (not convc1 and convf2: those run inside fused kernels), launched
+ * exactly as the block launches it — its sources, epilogue (ReLU, GRU z / r and q, bias maps, 0.25 scale), two-source reads and
+ * tile-major layouts.  The workspace tensors it touches are filled from in[i] (NCHW, NULL: left as they are) before the launch and
+ * copied to out[i] (NULL: not wanted) behind it, i = NND_UB_*:
+ *   C1 (B,256,H,W) relu(convc1)        CF (B,256,H,W) [convc2 192 | convf2 64]     HX (B,2*hidden+context,H,W) [h | inp | motion, flow]
+ *   Z (B,hidden,H,W)   RH (B,hidden,H,W) r*h   FM (B,3*hidden,H,W) [flow_head.conv1 | mask.0]
+ *   CTXB (B,6*hidden,H,W) context terms [zr1 2h | q1 h | zr2 2h | q2 h]            MASK (B,mask_channels,H,W)
+ * desc.flags may carry NND_FLAG_CALIBRATE (then nnd_update_block_calibration_finish as usual).  For tests of a single launch. */
+enum { NND_UB_C1 = 0, NND_UB_CF, NND_UB_HX, NND_UB_Z, NND_UB_RH, NND_UB_FM, NND_UB_CTXB, NND_UB_MASK, NND_UB_TENSORS };
+int nnd_update_block_layer_forward(const nnd_update_block_desc* desc, const float* packed_dev, int which, const float* const* in,
+                                   float* const* out, float* workspace, int B, int H, int W, void* stream);
 /* fp16x2 calibration (see "fp16x2 activation range"): after one or more calls of nnd_update_block_forward / nnd_*_refine with
  * NND_FLAG_CALIBRATE on this blob, turns the recorded maxima into the layers' activation scales (one tiny kernel on `stream`, no
  * synchronisation) and clears the records.  status_dev: optional device int32 that receives |= 1 if a recorded maximum was
@@ -281,7 +302,7 @@ int nnd_conv2d_pack_ex(const float* w_host, const float* b_host, int Cout, int C
                        float* packed_host);
 int nnd_conv2d_forward_ex(const float* packed_dev, const float* x, float* y, int B, int Cin, int H, int W,
                           int Cout, int KH, int KW, int relu, int arithmetic, void* stream);
-/* fp16x2 calibration of such a single layer (arithmetic == 2; no-op otherwise): sets the blob's activation scale from the
+/* fp16x2 / fp16 calibration of such a single layer (arithmetic == 2 or 1; no-op otherwise): sets the blob's activation scale from the
  * largest |x| of this input (see "fp16x2 activation range").  status_dev as nnd_update_block_calibration_finish.          */
 int nnd_conv2d_calibrate_ex(float* packed_dev, const float* x, int B, int Cin, int H, int W, int Cout, int KH, int KW,
                             int arithmetic, int32_t* status_dev, void* stream);
@@ -324,6 +345,18 @@ int nnd_conv_pack(const nnd_conv_desc* desc, const float* w_host, const float* b
                   const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, float* packed_host);
 int nnd_conv_forward(const nnd_conv_desc* desc, const float* packed_dev, const float* x, const float* residual, float* y,
                      int B, int Hin, int Win, int relu, int relu_after_residual, void* stream);
+/* The same layer with the arithmetic chosen (nnd_update_block_desc.arithmetic: 0, 3, 2 or 1; the stride-1 1x1 projections stay
+ * exact, as in the encoder) and, with workspace != NULL (nnd_conv_workspace_floats_ex floats), run in the encoder's own layout —
+ * tile-major with 4 channels interleaved: x, residual and y are NCHW here and converted on the way.  flags = NND_FLAG_CALIBRATE:
+ * the layer's activation scale is set from this input behind the launch (packed_dev is written; status_dev as
+ * nnd_update_block_calibration_finish, may be NULL).                                                                      */
+int64_t nnd_conv_packed_floats_ex(const nnd_conv_desc* desc, int arithmetic);
+int nnd_conv_pack_ex(const nnd_conv_desc* desc, int arithmetic, const float* w_host, const float* bias_host, const float* bn_gamma,
+                     const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, float* packed_host);
+int64_t nnd_conv_workspace_floats_ex(const nnd_conv_desc* desc, int B, int Hin, int Win);
+int nnd_conv_forward_ex(const nnd_conv_desc* desc, int arithmetic, int flags, float* packed_dev, const float* x, const float* residual,
+                        float* y, float* workspace, int32_t* status_dev, int B, int Hin, int Win, int relu, int relu_after_residual,
+                        void* stream);
 
 /* ------------------------------------------------------------------------- feature encoder
  * Replaces BasicEncoder.forward  nndepth/encoders/basic_encoder.py:71-93 (norm_fn "batch" in eval mode, or "none"),
@@ -340,7 +373,9 @@ typedef struct nnd_encoder_desc {
     int32_t struct_size; /* sizeof(nnd_encoder_desc) */
     int32_t output_dim, norm, cnet_dim;
     int32_t arithmetic; /* 0 = exact fp32 MFMA; 3 / 2 = the 3x3 convolutions at stride 1 and 2, the stride-2 1x1 shortcuts and
-                           cnet_proj on the 16-bit MFMA with 3 bf16 / 2 fp16 split operands (see nnd_update_block_desc.arithmetic);
+                           cnet_proj on the 16-bit MFMA with 3 bf16 / 2 fp16 split operands (see nnd_update_block_desc.arithmetic); 1 = the same
+                           layers with ONE range-scaled fp16 piece per operand (11 significand bits; finite up to 32 x a layer's
+                           calibrated maximum, inf / NaN beyond);
                            the stem, the stride-1 1x1 shortcuts and the 1x1 output conv stay exact fp32 */
     int32_t flags;      /* NND_FLAG_* */
 } nnd_encoder_desc;
@@ -671,7 +706,7 @@ typedef struct nnd_conv3d_desc {
     int32_t struct_size; /* sizeof(nnd_conv3d_desc) */
     int32_t Cout, Cin0, Cin1, stride;
     int32_t arithmetic; /* 0 = exact fp32 MFMA; 3 / 2 = 16-bit MFMA with 3 bf16 / 2 fp16 split operands
-                           (see nnd_update_block_desc.arithmetic) */
+                           (see nnd_update_block_desc.arithmetic); 1 (one fp16 piece) is not built for Conv3d and is refused */
     int32_t flags;      /* NND_FLAG_* */
 } nnd_conv3d_desc;
 int64_t nnd_conv3d_packed_floats(const nnd_conv3d_desc* desc);

@@ -109,6 +109,7 @@ SIGNATURES = {
     "nnd_update_block_pack": (_I, [C.POINTER(UpdateBlockDesc), C.POINTER(_P), _P]),
     "nnd_update_block_workspace_floats": (C.c_int64, [C.POINTER(UpdateBlockDesc), _I, _I, _I]),
     "nnd_update_block_forward": (_I, [C.POINTER(UpdateBlockDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_update_block_layer_forward": (_I, [C.POINTER(UpdateBlockDesc), _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "nnd_update_block_calibration_finish": (_I, [C.POINTER(UpdateBlockDesc), _P, _P, _P]),
     "nnd_update_block_scale_slots": (_I, [C.POINTER(UpdateBlockDesc), C.POINTER(C.c_int64), _I]),
     "nnd_conv2d_calibrate_ex": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -143,6 +144,10 @@ SIGNATURES = {
     "nnd_conv_packed_floats": (C.c_int64, [C.POINTER(ConvDesc)]),
     "nnd_conv_pack": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_float, _P]),
     "nnd_conv_forward": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "nnd_conv_packed_floats_ex": (C.c_int64, [C.POINTER(ConvDesc), _I]),
+    "nnd_conv_pack_ex": (_I, [C.POINTER(ConvDesc), _I, _P, _P, _P, _P, _P, _P, C.c_float, _P]),
+    "nnd_conv_workspace_floats_ex": (C.c_int64, [C.POINTER(ConvDesc), _I, _I, _I]),
+    "nnd_conv_forward_ex": (_I, [C.POINTER(ConvDesc), _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nnd_encoder_num_tensors": (_I, [C.POINTER(EncoderDesc)]),
     "nnd_encoder_packed_floats": (C.c_int64, [C.POINTER(EncoderDesc)]),
     "nnd_encoder_workspace_floats": (C.c_int64, [C.POINTER(EncoderDesc), _I, _I, _I]),

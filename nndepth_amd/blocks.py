@@ -49,8 +49,8 @@ class BasicUpdateBlock(nn.Module):
         self.flow_head = fh
         self.mask = nn.Sequential(_conv(hidden_dim, hidden_dim * 2, 3, 1), nn.ReLU(inplace=True),
                                   _conv(hidden_dim * 2, sps * 9, 1, 0))
-        # arithmetic of the fused loops' convolutions: "fp32" (exact fp32 MFMA, default), "bf16x3" (3 bf16 pieces) or "fp16x2"
-        # (2 range-scaled fp16 pieces), both in csrc/conv_split.hip
+        # arithmetic of the fused loops' convolutions: "fp32" (exact fp32 MFMA, default), "bf16x3" (3 bf16 pieces), "fp16x2"
+        # (2 range-scaled fp16 pieces) or "fp16" (ONE such piece: 11 significand bits, opt-in); the last three in csrc/conv_split.hip
         self.engine = ops.UpdateBlockEngine(hidden_dim, context_dim, cor_planes, flow_channel, sps * 9, gru, arithmetic)
         self._packed = ops.ParamCache()
 

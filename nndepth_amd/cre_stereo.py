@@ -110,7 +110,7 @@ class CREStereoBase(AutoCalibrate, nn.Module):
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
                  fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
         super().__init__()
-        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces), "fp32" (exact fp32 MFMA) or "fp16" (opt-in: ONE range-scaled fp16 piece, 11 significand bits, finite up to 32 x the calibrated maximum)
         # "all": every iteration's up_disp; "last": [{"up_disp": final}] (raft_stereo.check_outputs).  test_mode (the reference's switch,
         # returns the final flow tensor) runs last-only as well
         self.outputs = check_outputs(outputs)

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include "../../include/nndepth_amd.h"
+#include "split_arith.h"
 
 namespace nnd {
 
@@ -87,7 +88,7 @@ static inline int raise_lds_limit(const void* kern, std::atomic<unsigned>& done,
 }
 
 // ---------------------------------------------------------------------------------------
-// fp16x2 activation-range calibration (calib.hip, split_arith.h): an entry point called with NND_FLAG_CALIBRATE opens a
+// fp16x2 / fp16 activation-range calibration (calib.hip, split_arith.h; "fp16x2" below stands for both): an entry point called with NND_FLAG_CALIBRATE opens a
 // CalibScope on the calling thread; while it is open every launcher of a kernel that stages fp16x2 activations first measures
 // the largest |activation| of what the launch will stage into the layer's slot of the packed blob (calib_amax_*), and
 // nnd_*_calibration_finish turns the slots into the layers' activation scales (calib_finish).  Thread-local: a forward running
@@ -132,6 +133,11 @@ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
 }
 #endif
 
+// NCHW (C-ABI) <-> tile-major (layout.h) copies of a C-channel tensor (update_block.hip); dbs / sbs: floats between batches of the
+// tile-major tensor, c0: first channel of the slice inside it, c4: it keeps 4 channels interleaved; src == nullptr writes zeros
+int to_tiled(const float* src, float* dst, int64_t dbs, int B, int C, int H, int W, hipStream_t s, int c0 = 0, bool c4 = false);
+int from_tiled(const float* src, int64_t sbs, float* dst, int B, int C, int H, int W, hipStream_t s, int c0 = 0, bool c4 = false);
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -160,7 +166,8 @@ struct ConvLayer {
     int stride = 1;               // 1 or 2 ("same" padding K/2; output = ceil(input / stride) for odd K)
     int arith = 0;                // 0: exact fp32 MFMA (conv_mfma.hip); 3: fp32 carried as 3 bf16 pieces on the bf16 MFMA; 2: as 2
                                   //    range-scaled fp16 pieces on the fp16 MFMA (conv_split.hip, split_arith.h; CI_T = 16, weights
-                                  //    packed as 16-bit fragments)
+                                  //    packed as 16-bit fragments); 1: as ONE such piece (11 significand bits: reduced precision)
+    bool range_scaled() const { return split_range_scaled(arith); }  // fp16x2 / fp16: has a SPLIT_TAIL_* slot, is calibrated
     int64_t s_off = -1;           // float offset of the per-channel scale (EPI_AFFINE), ncb*32 floats; -1: none
     int nchunks;                  // ceil(Cin / CI_T)
     int ncb;                      // ceil(Cout / 32) output-channel blocks
@@ -169,9 +176,9 @@ struct ConvLayer {
         return arith ? (int64_t)ncb * nchunks * KH * KW * arith * 256  // [cb][chunk][tap][piece] x 64 lanes x 16 B
                      : (int64_t)ncb * nchunks * KH * KW * CI_T * 32;
     }
-    int64_t b_floats() const { return (int64_t)ncb * 32 + (arith == 2 ? 4 : 0); }  // fp16x2: + the output scale (split_arith.h)
+    int64_t b_floats() const { return (int64_t)ncb * 32 + (range_scaled() ? 4 : 0); }  // fp16x2 / fp16: + the output scale (split_arith.h)
     double flops(int B, int H, int W) const { return 2.0 * B * H * W * (double)Cout * Cin * KH * KW; }
-    int64_t tail_off() const { return b_off + (int64_t)ncb * 32; }  // fp16x2: float offset of the SPLIT_TAIL_* slot (split_arith.h)
+    int64_t tail_off() const { return b_off + (int64_t)ncb * 32; }  // fp16x2 / fp16: float offset of the SPLIT_TAIL_* slot (split_arith.h)
 };
 
 // A source / destination activation: channel-slice of an NCHW tensor (channel stride = H*W).

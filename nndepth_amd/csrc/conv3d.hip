@@ -50,6 +50,7 @@ static int make_conv3d_plan(const nnd_conv3d_desc* d, Conv3dPlan* p) {
     if (int rc = check_desc(d, NND_FLAG_CALIBRATE, "conv3d")) return rc;
     NND_REQUIRE(d->Cout > 0 && d->Cin0 > 0 && d->Cin1 >= 0, "conv3d: bad channel counts");
     NND_REQUIRE(d->stride == 1 || d->stride == 2, "conv3d: stride %d not supported (1, 2)", d->stride);
+    NND_REQUIRE(d->arithmetic != 1, "conv3d: arithmetic 1 (fp16) is not built for Conv3d (the one-piece arithmetic covers the 2-D convs of the loops and the encoder); use 2 (fp16x2)");
     NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2, "conv3d: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3) or 2 (fp16x2)");
     const int Ct = d->Cin0 + d->Cin1;
     int64_t off = 0, rel = 0;

@@ -39,7 +39,7 @@ namespace nnd {
 
 // --------------------------------------------------------------------------- host side
 namespace {
-// fp16x2 pieces on the host: clang's _Float16 conversion is IEEE round-to-nearest-even including subnormal results
+// fp16x2 / fp16 pieces on the host: clang's _Float16 conversion is IEEE round-to-nearest-even including subnormal results
 uint16_t f16_rn(float x) {
     const _Float16 h = (_Float16)x;
     uint16_t u;
@@ -195,12 +195,13 @@ void print_split_plan(const ConvLayer& L, const ConvIO& io, const SplitCfg& cfg)
 }
 }  // namespace
 
-// the kernel instantiations live in conv_split_ns2.hip / conv_split_ns3.hip
+// the kernel instantiations live in conv_split_ns1.hip / conv_split_ns2.hip / conv_split_ns3.hip
+extern template int launch_split_ns<1>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 extern template int launch_split_ns<2>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 extern template int launch_split_ns<3>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 
 bool conv_split_supported(int KH, int KW, int Cin, int stride, int arith, int Cout) {
-    if ((arith != 3 && arith != 2) || (stride != 1 && stride != 2) || Cin % 16 != 0) return false;
+    if ((arith != 3 && arith != 2 && arith != 1) || (stride != 1 && stride != 2) || Cin % 16 != 0) return false;
     // stride 2: planar sources only (checked at launch), and at least 3 output-channel blocks: the 9 x 17-position patch of a
     // sub-tile is staged by the workgroup's output-channel waves, fewer of them would need more than 4 staging units per thread
     if (stride == 2) return ((KH == 3 && KW == 3) || (KH == 1 && KW == 1)) && Cout >= 96;
@@ -232,10 +233,12 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
         a.dbg_stamp = only < 0 || idx == only;
     }
 #endif
-    if (calibrating() && L.arith == 2)  // record the largest |activation| this launch stages (calib.hip)
+    if (calibrating() && split_range_scaled(L.arith))  // record the largest |activation| this launch stages (calib.hip)
         for (const Act* src : {&io.src0, &io.src1}) NND_TRY(calib_amax_act(*src, a.ls, B, Hin, Win, blob + L.tail_off(), stream));
     if (switches().conv_verbose) print_split_plan(L, io, cfg);
-    rc = L.arith == 3 ? launch_split_ns<3>(a, cfg, L.KH, L.KW, stream) : launch_split_ns<2>(a, cfg, L.KH, L.KW, stream);
+    rc = L.arith == 3   ? launch_split_ns<3>(a, cfg, L.KH, L.KW, stream)
+         : L.arith == 2 ? launch_split_ns<2>(a, cfg, L.KH, L.KW, stream)
+                        : launch_split_ns<1>(a, cfg, L.KH, L.KW, stream);
     NND_REQUIRE(rc != NND_ERR_UNSUPPORTED, "conv_split: shape %dx%d P=%d nu=%d %s is not instantiated", L.KH, L.KW, cfg.P, cfg.nu, cfg.fast ? "fast" : "generic");
     if (rc != NND_OK) return rc;
     NND_LAUNCH_CHECK();
@@ -244,7 +247,7 @@ int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, i
 
 // Host packer: same (cout, cin_src, KH, KW) inputs as pack_conv; blob order [cb][chunk][tap][piece][lane][8] 16-bit values with
 // lane = h*32 + (co % 32) holding channels chunk*16 + 8h + 0..7 (the A operand of v_mfma_f32_32x32x16_{bf16,f16}).
-// fp16x2 (arith 2): the pieces are those of w * 2^s, s per layer such that max|w| * 2^s lies in [2^13, 2^14), and the 4 floats
+// fp16x2 / fp16 (arith 2 / 1: two pieces / the first one alone): the pieces are those of w * 2^s, s per layer such that max|w| * 2^s lies in [2^13, 2^14), and the 4 floats
 // behind the bias vector (bias[ncb*32 ...], split_arith.h: SPLIT_TAIL_*) are oscale = 2^-(s + xs), which the kernels multiply their
 // accumulators by, the activation scale 2^xs (xs = SPLIT_F16_XSHIFT until the layer is calibrated), the calibration accumulator
 // and 2^-s.
@@ -256,8 +259,9 @@ void pack_conv_split(const ConvLayer& L, int nparts, const float* const* w, cons
     float* bp = blob + L.b_off;
     memset(wp, 0, sizeof(float) * L.w_floats());
     memset(bp, 0, sizeof(float) * L.b_floats());
+    const bool f16 = split_range_scaled(NS);
     float wscale = 1.f;
-    if (NS == 2) {
+    if (f16) {
         float wmax = 0.f;
         for (int part = 0; part < nparts; ++part)
             for (int col = 0; col < cout[part]; ++col)
@@ -286,8 +290,8 @@ void pack_conv_split(const ConvLayer& L, int nparts, const float* const* w, cons
                 for (int t = 0; t < NT; ++t) {
                     float res = w[part][((size_t)col * cin_src + (ci_map ? ci_map[ci] : ci)) * NT + t] * wscale;
                     for (int s = 0; s < NS; ++s) {
-                        const uint16_t piece = NS == 2 ? f16_rn(res) : bf16_rn(res);
-                        res -= NS == 2 ? f16_to_f(piece) : bf16_to_f(piece);
+                        const uint16_t piece = f16 ? f16_rn(res) : bf16_rn(res);
+                        res -= f16 ? f16_to_f(piece) : bf16_to_f(piece);
                         wp[((((((size_t)cb * L.nchunks + chunk) * NT + t) * NS + s) * 64 + lane) * 8) + j] = piece;
                     }
                 }
@@ -325,7 +329,7 @@ static int launch_fb(const FlowBranchArgs& a, dim3 grid, dim3 block, hipStream_t
 }
 
 bool flow_branch_supported(const ConvLayer& f2, int fc) {
-    return (f2.arith == 3 || f2.arith == 2) && f2.KH == 3 && f2.KW == 3 && f2.Cin == FB_C1 && f2.Cout == 64 && f2.stride == 1 && (fc == 1 || fc == 2);
+    return (f2.arith == 3 || f2.arith == 2 || f2.arith == 1) && f2.KH == 3 && f2.KW == 3 && f2.Cin == FB_C1 && f2.Cout == 64 && f2.stride == 1 && (fc == 1 || fc == 2);
 }
 
 int make_flow_branch_args(const ConvLayer& f2, const float* blob, const float* w7t, const float* b7, const float* flow, int64_t fbs,
@@ -354,8 +358,8 @@ int launch_flow_branch(const ConvLayer& f2, const float* blob, const float* w7t,
     if (rc0 != NND_OK) return rc0;
     dim3 grid(a.c.npos, 1, B), block(512);
     int rc;
-    if (fc == 1) rc = f2.arith == 3 ? launch_fb<1, 3>(a, grid, block, stream) : launch_fb<1, 2>(a, grid, block, stream);
-    else rc = f2.arith == 3 ? launch_fb<2, 3>(a, grid, block, stream) : launch_fb<2, 2>(a, grid, block, stream);
+    if (fc == 1) rc = f2.arith == 3 ? launch_fb<1, 3>(a, grid, block, stream) : f2.arith == 2 ? launch_fb<1, 2>(a, grid, block, stream) : launch_fb<1, 1>(a, grid, block, stream);
+    else rc = f2.arith == 3 ? launch_fb<2, 3>(a, grid, block, stream) : f2.arith == 2 ? launch_fb<2, 2>(a, grid, block, stream) : launch_fb<2, 1>(a, grid, block, stream);
     if (rc != NND_OK) return rc;
     NND_LAUNCH_CHECK();
     return NND_OK;

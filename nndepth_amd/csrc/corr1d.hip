@@ -759,6 +759,16 @@ __global__ void __launch_bounds__(512) flow_branch_lookup_kernel(FlowBranchArgs 
     else lookup_convc1_body<false>(q, reinterpret_cast<float(*)[32 * 32]>(fbl_lds), (int)blockIdx.x - nfb, (int)blockIdx.z);
 }
 
+template <int FC, int NS>
+static int launch_fbl(const FlowBranchArgs& fa, const LookupC1Args& q, dim3 grid, dim3 block, hipStream_t stream) {
+    static std::atomic<unsigned> raised{0};
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(flow_branch_lookup_kernel<FC, NS>), raised)) return rc;
+    constexpr size_t lds = fb_lds_bytes<FC, NS>();
+    hipLaunchKernelGGL((flow_branch_lookup_kernel<FC, NS>), grid, block, lds, stream, fa, q);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
 // coords (tile-major) -> c1 = relu(convc1(lookup(coords))) (tile-major, 256 channels); wpk / bias: the packed convc1 layer.
 // geo == nullptr: RAFT-Stereo pyramid; otherwise the IGEV feature + geometry pyramids with G groups.
 static int lookup_convc1_launch_impl(const float* pyr, const float* geo, int G, const float* coords, const ConvLayer& L, const float* blob,
@@ -780,21 +790,11 @@ static int lookup_convc1_launch_impl(const float* pyr, const float* geo, int G, 
     dim3 grid(tiles_x * cdiv(H, 4), 1, B), block(512);
     LookupC1Args q{pyr, geo, coords, wpk, bias, c1, (long)c1_bs, a, geo ? G : 1, tiles_x, cb_stride, c1_c4 ? 1 : 0};
     if (fb) {  // the flow-branch workgroups of the same iteration in the same launch
-        NND_REQUIRE(!geo && flow_branch_lookup_supported(fb_ns), "lookup_convc1: the merged flow-branch launch is built for RAFT-Stereo pyramids and arithmetic 2");
+        NND_REQUIRE(!geo && flow_branch_lookup_supported(fb_ns), "lookup_convc1: the merged flow-branch launch is built for RAFT-Stereo pyramids and arithmetics 2 / 1");
         NND_REQUIRE(fb->c.npos == (int)grid.x && fb->c.tiles_x == tiles_x, "lookup_convc1: flow-branch tiling differs");
         grid.x *= 2;
-        const size_t lds = fb_fc == 1 ? fb_lds_bytes<1, 2>() : fb_lds_bytes<2, 2>();
-        if (fb_fc == 1) {
-            static std::atomic<unsigned> raised{0};
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(flow_branch_lookup_kernel<1, 2>), raised)) return rc;
-            hipLaunchKernelGGL((flow_branch_lookup_kernel<1, 2>), grid, block, lds, stream, *fb, q);
-        } else {
-            static std::atomic<unsigned> raised{0};
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(flow_branch_lookup_kernel<2, 2>), raised)) return rc;
-            hipLaunchKernelGGL((flow_branch_lookup_kernel<2, 2>), grid, block, lds, stream, *fb, q);
-        }
-        NND_LAUNCH_CHECK();
-        return NND_OK;
+        if (fb_fc == 1) return fb_ns == 2 ? launch_fbl<1, 2>(*fb, q, grid, block, stream) : launch_fbl<1, 1>(*fb, q, grid, block, stream);
+        return fb_ns == 2 ? launch_fbl<2, 2>(*fb, q, grid, block, stream) : launch_fbl<2, 1>(*fb, q, grid, block, stream);
     }
     if (geo) hipLaunchKernelGGL(lookup_convc1_kernel<true>, grid, block, 0, stream, q);
     else hipLaunchKernelGGL(lookup_convc1_kernel<false>, grid, block, 0, stream, q);
@@ -802,7 +802,7 @@ static int lookup_convc1_launch_impl(const float* pyr, const float* geo, int G, 
     return NND_OK;
 }
 
-bool flow_branch_lookup_supported(int arith) { return arith == 2; }
+bool flow_branch_lookup_supported(int arith) { return split_range_scaled(arith); }
 
 int lookup_convc1_launch(const float* pyr, const float* geo, int G, const float* coords, const ConvLayer& L, const float* blob,
                          float* c1, int64_t c1_bs, int B, int H, int W, int num_levels, int radius, hipStream_t stream, bool c1_c4) {
@@ -1070,7 +1070,7 @@ __global__ void __launch_bounds__(512, 2) igev_lookup_convc1_il_split_kernel(con
     float br[16];
     load_c1_bias(bias, wave, h2, br);
     float oscale = 1.f, xscale = 1.f;
-    if constexpr (NS == 2) {  // behind the 8 x 32 bias values of the packed layer (split_arith.h)
+    if constexpr (split_range_scaled(NS)) {  // behind the 8 x 32 bias values of the packed layer (split_arith.h)
         oscale = bias[256 + SPLIT_TAIL_OSCALE];
         xscale = bias[256 + SPLIT_TAIL_XSCALE];
     }
@@ -1119,7 +1119,7 @@ __global__ void __launch_bounds__(512, 2) igev_lookup_convc1_il_split_kernel(con
                 x = x * wm1;
                 const float cf = ceilf(x) - x;
                 float res = pin[i] ? cf * v0[i][k] + (1.0f - cf) * v1[i][k] : 0.f;  // the sample, in the reference's op order
-                if constexpr (NS == 2) res = res * xscale;
+                if constexpr (split_range_scaled(NS)) res = res * xscale;
                 const int ch = vg * IL_NTAP + k;                              // channel inside the level
                 unsigned short* dst = reinterpret_cast<unsigned short*>(buf + (((ch >> 4) * NS * 2 + ((ch >> 3) & 1)) * 64 + pcol[i]) * 16) + (ch & 7);
 #pragma unroll
@@ -1130,8 +1130,9 @@ __global__ void __launch_bounds__(512, 2) igev_lookup_convc1_il_split_kernel(con
                         res -= (float)pv;
                         bits = __builtin_bit_cast(unsigned short, pv);
                     } else {
-                        const _Float16 pv = (_Float16)res;
+                        _Float16 pv = (_Float16)res;
                         res -= (float)pv;
+                        if constexpr (NS == 1) pv = split_inf_to_nan(pv);
                         bits = __builtin_bit_cast(unsigned short, pv);
                     }
                     dst[sp * (2 * 64 * 8)] = bits;  // next piece: 2 k halves x 64 pixels x 8 values further
@@ -1176,7 +1177,7 @@ __global__ void __launch_bounds__(512, 2) igev_lookup_convc1_il_split_kernel(con
         if (more) put(lvl + 1, xsb + ((lvl + 1) & 1) * LVB);
         __syncthreads();
     }
-    if constexpr (NS == 2) {
+    if constexpr (split_range_scaled(NS)) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc0[i] *= oscale, acc1[i] *= oscale;
     }
@@ -1206,7 +1207,12 @@ int igev_lookup_convc1_il_launch(const float* il, int G, const float* coords, co
         const int tiles_x = cdiv(W, 8), ntiles = tiles_x * cdiv(H, 4);
         const size_t ldsb = (size_t)2 * (IL_LC / 16) * L.arith * 2 * 64 * 16;
         dim3 grid(cdiv(ntiles, 2), 1, B), block(512);
-        if (L.arith == 2) {
+        if (L.arith == 1) {
+            static std::atomic<unsigned> raised1{0};
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(igev_lookup_convc1_il_split_kernel<1>), raised1)) return rc;
+            hipLaunchKernelGGL(igev_lookup_convc1_il_split_kernel<1>, grid, block, ldsb, stream, il, coords, blob + L.w_off, blob + L.b_off, c1,
+                               (long)c1_bs, IL, make_lay(H, W, true), H, W, num_levels, ntiles, tiles_x, c1_c4 ? 1 : 0);
+        } else if (L.arith == 2) {
             static std::atomic<unsigned> raised2{0};
             if (int rc = raise_lds_limit(reinterpret_cast<const void*>(igev_lookup_convc1_il_split_kernel<2>), raised2)) return rc;
             hipLaunchKernelGGL(igev_lookup_convc1_il_split_kernel<2>, grid, block, ldsb, stream, il, coords, blob + L.w_off, blob + L.b_off, c1,

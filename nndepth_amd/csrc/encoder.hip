@@ -420,7 +420,7 @@ static int make_enc_plan(const nnd_encoder_desc* d, EncPlan* p) {
     if (int rc = check_desc(d, NND_FLAG_CALIBRATE, "encoder")) return rc;
     NND_REQUIRE(d->output_dim > 0 && d->cnet_dim >= 0, "encoder: bad output_dim / cnet_dim");
     NND_REQUIRE(d->norm >= 0 && d->norm <= 2, "encoder: norm must be 0 (none), 1 (batch, eval) or 2 (instance); group norm is not built");
-    NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2, "encoder: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3) or 2 (fp16x2)");
+    NND_REQUIRE(d->arithmetic >= 0 && d->arithmetic <= 3, "encoder: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3), 2 (fp16x2) or 1 (fp16)");
     p->d = *d;
     int64_t off = 0;
     p->stem_w = off; off += STEM_K * 64;
@@ -499,6 +499,64 @@ int nnd_conv_forward(const nnd_conv_desc* desc, const float* packed_dev, const f
                          (hipStream_t)stream);
 }
 
+// The same layer with the arithmetic chosen, optionally in the encoder's own layout (tile-major, 4 channels interleaved)
+int64_t nnd_conv_packed_floats_ex(const nnd_conv_desc* desc, int arithmetic) {
+    ConvLayer L;
+    int64_t total;
+    if (arithmetic < 0 || arithmetic > 3 || conv_layer(desc, &L, &total, arithmetic) != NND_OK) return NND_ERR_INVALID;
+    return total;
+}
+
+int nnd_conv_pack_ex(const nnd_conv_desc* desc, int arithmetic, const float* w, const float* bias, const float* bn_gamma,
+                     const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, float* packed_host) {
+    ConvLayer L;
+    NND_REQUIRE(arithmetic >= 0 && arithmetic <= 3, "conv_pack_ex: arithmetic must be 0, 1, 2 or 3");
+    int rc = conv_layer(desc, &L, nullptr, arithmetic);
+    if (rc != NND_OK) return rc;
+    NND_REQUIRE(w && packed_host, "conv_pack_ex: null pointer");
+    NND_REQUIRE(!bn_gamma || (bn_beta && bn_mean && bn_var), "conv_pack_ex: incomplete batch-norm parameters");
+    pack_conv_norm(L, w, bias, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, packed_host);
+    return NND_OK;
+}
+
+int64_t nnd_conv_workspace_floats_ex(const nnd_conv_desc* desc, int B, int Hin, int Win) {
+    ConvLayer L;
+    if (conv_layer(desc, &L, nullptr) != NND_OK || B <= 0 || Hin <= 0 || Win <= 0) return NND_ERR_INVALID;
+    const int H = (Hin + L.stride - 1) / L.stride, W = (Win + L.stride - 1) / L.stride;
+    return (int64_t)B * (cdiv(L.Cin, 4) * 4 * tiled_plane(Hin, Win) + 2 * (int64_t)cdiv(L.Cout, 4) * 4 * tiled_plane(H, W));
+}
+
+int nnd_conv_forward_ex(const nnd_conv_desc* desc, int arithmetic, int flags, float* packed_dev, const float* x, const float* residual,
+                        float* y, float* workspace, int32_t* status_dev, int B, int Hin, int Win, int relu, int relu_after_residual,
+                        void* stream) {
+    ConvLayer L;
+    NND_REQUIRE(arithmetic >= 0 && arithmetic <= 3 && (flags & ~NND_FLAG_CALIBRATE) == 0, "conv_forward_ex: bad arithmetic / flags");
+    int rc = conv_layer(desc, &L, nullptr, arithmetic);
+    if (rc != NND_OK) return rc;
+    NND_REQUIRE(packed_dev && x && y && B > 0 && Hin > 0 && Win > 0, "conv_forward_ex: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = (Hin + L.stride - 1) / L.stride, W = (Win + L.stride - 1) / L.stride;
+    const int ef = (relu ? 1 : 0) | (relu_after_residual ? 2 : 0);
+    const bool calib = (flags & NND_FLAG_CALIBRATE) && L.range_scaled();
+    {
+        CalibScope scope(calib);
+        if (!workspace) {
+            rc = run_conv_norm(L, packed_dev, x, (int64_t)L.Cin * Hin * Win, false, residual, (int64_t)L.Cout * H * W, y,
+                               (int64_t)L.Cout * H * W, false, ef, B, Hin, Win, s);
+        } else {  // the encoder's layout: tile-major, 4 channels interleaved
+            const int64_t xbs = (int64_t)cdiv(L.Cin, 4) * 4 * tiled_plane(Hin, Win), ybs = (int64_t)cdiv(L.Cout, 4) * 4 * tiled_plane(H, W);
+            float *xt = workspace, *rt = xt + B * xbs, *yt = rt + B * ybs;
+            NND_TRY(to_tiled(x, xt, xbs, B, L.Cin, Hin, Win, s, 0, true));
+            if (residual) NND_TRY(to_tiled(residual, rt, ybs, B, L.Cout, H, W, s, 0, true));
+            rc = run_conv_norm(L, packed_dev, xt, xbs, true, residual ? rt : nullptr, ybs, yt, ybs, true, ef, B, Hin, Win, s, true, true);
+            if (rc == NND_OK) rc = from_tiled(yt, ybs, y, B, L.Cout, H, W, s, 0, true);
+        }
+    }
+    if (rc != NND_OK || !calib) return rc;
+    const int64_t off = L.tail_off();
+    return calib_finish(packed_dev, &off, 1, status_dev, s);
+}
+
 int nnd_encoder_num_tensors(const nnd_encoder_desc* desc) {
     EncPlan p;
     if (make_enc_plan(desc, &p) != NND_OK) return NND_ERR_INVALID;
@@ -574,11 +632,11 @@ int nnd_encoder_calibration_finish(const nnd_encoder_desc* desc, float* packed_d
     int64_t offs[3 * ENC_BLOCKS + 1];
     int n = 0;
     for (int i = 0; i < ENC_BLOCKS; ++i) {
-        if (p.c1[i].arith == 2) offs[n++] = p.base1[i] + p.c1[i].tail_off();
-        if (p.c2[i].arith == 2) offs[n++] = p.base2[i] + p.c2[i].tail_off();
-        if (p.ds[i].arith == 2 && (p.strides[i] != 1 || p.inpl[i] != p.planes[i])) offs[n++] = p.based[i] + p.ds[i].tail_off();
+        if (p.c1[i].range_scaled()) offs[n++] = p.base1[i] + p.c1[i].tail_off();
+        if (p.c2[i].range_scaled()) offs[n++] = p.base2[i] + p.c2[i].tail_off();
+        if (p.ds[i].range_scaled() && (p.strides[i] != 1 || p.inpl[i] != p.planes[i])) offs[n++] = p.based[i] + p.ds[i].tail_off();
     }
-    if (desc->cnet_dim > 0 && p.cnet.arith == 2) offs[n++] = p.base_cnet + p.cnet.tail_off();
+    if (desc->cnet_dim > 0 && p.cnet.range_scaled()) offs[n++] = p.base_cnet + p.cnet.tail_off();
     return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
 }
 
@@ -595,7 +653,7 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed, cons
     NND_REQUIRE(packed && frames && fmap && workspace && N > 0 && H > 0 && W > 0, "encoder_forward: bad argument");
     NND_REQUIRE(!frames_b || (nsplit > 0 && nsplit < N), "encoder_forward2: a second frame tensor needs 0 < nsplit < N");
     NND_REQUIRE(!cnet_out || (desc->cnet_dim > 0 && n_cnet > 0 && n_cnet <= N), "encoder_forward: cnet_out needs cnet_dim > 0 and 0 < n_cnet <= N");
-    CalibScope calib((desc->flags & NND_FLAG_CALIBRATE) && desc->arithmetic == 2);
+    CalibScope calib((desc->flags & NND_FLAG_CALIBRATE) && split_range_scaled(desc->arithmetic));
     hipStream_t s = (hipStream_t)stream;
     const int64_t bufsz = enc_buf_floats(N, H, W);
     float* buf[4] = {workspace, workspace + bufsz, workspace + 2 * bufsz, workspace + 3 * bufsz};

@@ -1,4 +1,4 @@
-// Flow branch of the motion encoder as one workgroup program (arithmetics 2 / 3): device body shared by flow_branch_kernel
+// Flow branch of the motion encoder as one workgroup program (arithmetics 1 / 2 / 3): device body shared by flow_branch_kernel
 // (conv_split.hip) and flow_branch_lookup_kernel (corr1d.hip).  Design notes: conv_split.hip.
 #pragma once
 #include "conv_split_kernel.h"
@@ -59,7 +59,7 @@ __device__ __forceinline__ void flow_branch_body(const FlowBranchArgs& a, unsign
     const int cbi = wave & 1, kj = wave >> 1;
     const uint4* wq = reinterpret_cast<const uint4*>(a.c.wpk) + (size_t)cbi * FB_NCH * (9 * NS * 64) + lane;
     float oscale = 1.f, xscale = 1.f;
-    if constexpr (NS == 2) {  // undoes the fp16 range scaling / the layer's activation scale (split_arith.h)
+    if constexpr (split_range_scaled(NS)) {  // undoes the fp16 range scaling / the layer's activation scale (split_arith.h)
         const float* tail = a.c.bias + (((a.c.Cout + 31) >> 5) << 5);
         oscale = tail[SPLIT_TAIL_OSCALE];
         xscale = tail[SPLIT_TAIL_XSCALE];
@@ -164,7 +164,7 @@ __device__ __forceinline__ void flow_branch_body(const FlowBranchArgs& a, unsign
         split_mfma_step<NS>(ab[st % NA], bq, acc[0]);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (NS == 2) {
+    if constexpr (split_range_scaled(NS)) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) acc[0][reg] *= oscale;
     }

@@ -14,7 +14,8 @@
 //     (tile row, sub-row) so the HBM stores are whole 256-B runs.
 // NS = 3 (arithmetic 3, round 2): the same GEMM with both operands as 3 bf16 pieces and 6 products per fp32 product on
 // v_mfma_f32_32x32x16_bf16 (conv_split.hip's arithmetic; weights in its packing); NS = 2 (arithmetic 2, round 3): 2 range-scaled
-// fp16 pieces, 3 products on v_mfma_f32_32x32x16_f16 (split_arith.h); NS = 0: the exact fp32 MFMA.  Phase stamps of the exact kernel at 68x120
+// fp16 pieces, 3 products on v_mfma_f32_32x32x16_f16 (split_arith.h); NS = 1 (arithmetic 1): ONE range-scaled fp16 piece, 1 product — 11
+// significand bits per operand, half the weight stream; NS = 0: the exact fp32 MFMA.  Phase stamps of the exact kernel at 68x120
 // (scripts/stamps_mu.py): stage 3.8 us, K loop 22 (2.4 GFLOP on the fp32 MFMA = 15.3 us at peak: the kernel is matrix-bound),
 // softmax + store 3.2.  The x tile is staged as [16-ch chunk][piece][k half][pixel][8 bf16], so a B fragment is one
 // conflict-free ds_read_b128 per piece, shared by the wave's 3 output-channel blocks.
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__((MaskUpCfg<RATE, CIN>::NT + 64 * FHW)) mask_up
     const long HW = (long)H * W;
     const long XP = a.lay.plane;
     float oscale = 1.f, xscale = 1.f;  // fp16x2: undoes the power-of-two range scaling of both operands / the layer's activation scale (packed behind the bias, split_arith.h)
-    if constexpr (NS == 2) {
+    if constexpr (split_range_scaled(NS)) {
         oscale = a.bias[Cfg::NCB * 32 + SPLIT_TAIL_OSCALE];
         xscale = a.bias[Cfg::NCB * 32 + SPLIT_TAIL_XSCALE];
     }
@@ -359,7 +360,7 @@ __global__ void __launch_bounds__((MaskUpCfg<RATE, CIN>::NT + 64 * FHW)) mask_up
             split_mfma_step<NP>(ab[u % NA], bq[ch & 1], acc[cbi]);  // x_i * w_j with i + j descending: the small products first
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (NS == 2) {
+        if constexpr (split_range_scaled(NS)) {
 #pragma unroll
             for (int cbi = 0; cbi < CBW; ++cbi)
 #pragma unroll
@@ -467,7 +468,7 @@ __global__ void __launch_bounds__((MaskUpCfg<RATE, CIN>::NT + 64 * FHW)) mask_up
     NND_MSTAMP(4);
 }
 
-constexpr int MU_FHW = 4;  // flow-head waves of the concurrent fold (fp16x2: 105 VGPRs, 16 waves per CU fit)
+constexpr int MU_FHW = 4;  // flow-head waves of the concurrent fold (<8, 256>: fp16x2 106 VGPRs, fp16 83: 16 waves per CU fit)
 template <int RATE, int CIN, int NS, int FHW>
 static int launch_mu_fhw(MaskUpArgs a, int B, hipStream_t stream) {
     using Cfg = MaskUpCfg<RATE, CIN>;
@@ -488,14 +489,14 @@ static int launch_mu_fhw(MaskUpArgs a, int B, hipStream_t stream) {
 template <int RATE, int CIN, int NS = 0>
 static int launch_mu(const MaskUpArgs& a, int B, hipStream_t stream) {
     if (a.fh.x) {
-        if constexpr (NS == 2) return launch_mu_fhw<RATE, CIN, NS, MU_FHW>(a, B, stream);
-        else NND_REQUIRE(false, "mask_upsample: the folded flow head is built for the fp16x2 arithmetic");
+        if constexpr (split_range_scaled(NS)) return launch_mu_fhw<RATE, CIN, NS, MU_FHW>(a, B, stream);
+        else NND_REQUIRE(false, "mask_upsample: the folded flow head is built for the fp16x2 and fp16 arithmetics");
     }
     return launch_mu_fhw<RATE, CIN, NS, 0>(a, B, stream);
 }
 
 // the folded flow head exists for this mask layer / hidden size (the caller decides whether it pays: small grids)
-bool mask_upsample_fold_supported(const ConvLayer& L, int hid) { return L.arith == 2 && hid % 16 == 0 && hid <= 128; }
+bool mask_upsample_fold_supported(const ConvLayer& L, int hid) { return split_range_scaled(L.arith) && hid % 16 == 0 && hid <= 128; }
 
 bool mask_upsample_supported(int rate, int cin, int flow_channels) {
     return (flow_channels == 1 || flow_channels == 2) && ((rate == 8 && (cin == 256 || cin == 128)) || (rate == 4 && (cin == 256 || cin == 128)));
@@ -504,7 +505,7 @@ bool mask_upsample_supported(int rate, int cin, int flow_channels) {
 int mask_upsample_launch(const ConvLayer& L, const float* blob, const float* x, int64_t xbs, const float* flow, float* out,
                          int B, int H, int W, int rate, hipStream_t stream, bool tiled, int flow_channels, bool x_c4,
                          const MaskUpFlowHead* fh) {
-    NND_REQUIRE(L.KH == 1 && L.KW == 1 && L.CI_T == (L.arith ? 16 : 128) && L.Cout == 9 * rate * rate && (L.arith == 0 || L.arith == 3 || L.arith == 2),
+    NND_REQUIRE(L.KH == 1 && L.KW == 1 && L.CI_T == (L.arith ? 16 : 128) && L.Cout == 9 * rate * rate && L.arith >= 0 && L.arith <= 3,
                 "mask_upsample: layer shape / packing");
     NND_REQUIRE(mask_upsample_supported(rate, L.Cin, flow_channels), "mask_upsample: rate %d / Cin %d / %d flow channels not built",
                 rate, L.Cin, flow_channels);
@@ -527,10 +528,16 @@ int mask_upsample_launch(const ConvLayer& L, const float* blob, const float* x, 
         if (rate == 4 && L.Cin == 256) return launch_mu<4, 256, 3>(a, B, stream);
         return launch_mu<4, 128, 3>(a, B, stream);
     }
-    if (L.arith == 2) {  // range-scaled fp16 pieces
+    if (split_range_scaled(L.arith)) {  // range-scaled fp16 pieces
         if (calibrating()) {  // record the largest |x| this launch stages (calib.hip)
             const Act xa{const_cast<float*>(x), xbs, L.Cin};
             if (int rc = calib_amax_act(xa, make_lay(H, W, tiled, x_c4), B, H, W, blob + L.tail_off(), stream)) return rc;
+        }
+        if (L.arith == 1) {  // one piece
+            if (rate == 8 && L.Cin == 256) return launch_mu<8, 256, 1>(a, B, stream);
+            if (rate == 8 && L.Cin == 128) return launch_mu<8, 128, 1>(a, B, stream);
+            if (rate == 4 && L.Cin == 256) return launch_mu<4, 256, 1>(a, B, stream);
+            return launch_mu<4, 128, 1>(a, B, stream);
         }
         if (rate == 8 && L.Cin == 256) return launch_mu<8, 256, 2>(a, B, stream);
         if (rate == 8 && L.Cin == 128) return launch_mu<8, 128, 2>(a, B, stream);

@@ -65,8 +65,8 @@ static int make_plan(const nnd_update_block_desc* d, Plan* p) {
                 "update_block: hidden_dim %d with %d flow channel(s) is not supported: flow_head.conv2 would stage %zu bytes of LDS (at most 65536)",
                 hid, fc, fc2_lds_bytes(hid, fc));
     NND_REQUIRE(d->gru_kind == 0 || d->gru_kind == 1, "update_block: gru_kind must be 0 (sep_conv) or 1 (conv_gru)");
-    NND_REQUIRE(d->arithmetic == 0 || d->arithmetic == 3 || d->arithmetic == 2,
-                "update_block: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3 split) or 2 (fp16x2 split)");
+    NND_REQUIRE(d->arithmetic >= 0 && d->arithmetic <= 3,
+                "update_block: arithmetic must be 0 (fp32 MFMA), 3 (bf16x3 split), 2 (fp16x2 split) or 1 (fp16, one piece)");
     // arithmetic == 3: every MFMA conv whose shape conv_split.hip builds takes the split-bf16 kernel (mask.2 inside the fused
     // mask + upsample kernel; convf2 together with convf1 in flow_branch_kernel), except convc1 (its weights are consumed by the
     // fused lookup kernels in the fp32 packing); desc.split_layers (diagnostic) restricts it to a subset, bit = ConvId (e.g. 2 =
@@ -522,7 +522,7 @@ static int run_fc2(const Plan& p, const float* blob, const Bufs& w, float* delta
 // LDS — under NND_FLAG_CALIBRATE the stand-alone convf1 kernel writes it to w.f1 (unused otherwise on this path) and its largest
 // value is recorded in convf2's slot.
 static int calib_flow_branch(const Plan& p, const float* blob, const Bufs& w, const float* flow, int B, int H, int W, hipStream_t s) {
-    if (!calibrating() || p.L[C_F2].arith != 2) return NND_OK;
+    if (!calibrating() || !p.L[C_F2].range_scaled()) return NND_OK;
     const int64_t n = tiled_plane(H, W);
     int rc = run_convf1(p, blob, flow, (int64_t)p.d.flow_channels * n, w.f1, B, H, W, s);
     if (rc != NND_OK) return rc;
@@ -571,14 +571,14 @@ static int run_update(const Plan& p, const float* blob, const Bufs& w, Act corr,
 
 // NCHW <-> workspace tensor `dst` / `src` (its channel 0), slice of C channels starting at channel c0; c4: that tensor is in
 // the 4-channel-interleaved layout; src == nullptr (to_tiled) writes zeros
-static int to_tiled(const float* src, float* dst, int64_t dbs, int B, int C, int H, int W, hipStream_t s, int c0 = 0, bool c4 = false) {
+int to_tiled(const float* src, float* dst, int64_t dbs, int B, int C, int H, int W, hipStream_t s, int c0, bool c4) {
     const long total = (long)B * C * H * W;
     hipLaunchKernelGGL(to_tiled_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, s, src, dst, (long)dbs, c0, B, C, H, W,
                        make_lay(H, W, true, c4));
     NND_LAUNCH_CHECK();
     return NND_OK;
 }
-static int from_tiled(const float* src, int64_t sbs, float* dst, int B, int C, int H, int W, hipStream_t s, int c0 = 0, bool c4 = false) {
+int from_tiled(const float* src, int64_t sbs, float* dst, int B, int C, int H, int W, hipStream_t s, int c0, bool c4) {
     const long total = (long)B * C * H * W;
     hipLaunchKernelGGL(from_tiled_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, s, src, (long)sbs, c0, dst, B, C, H, W,
                        make_lay(H, W, true, c4));
@@ -675,7 +675,7 @@ int nnd_update_block_scale_slots(const nnd_update_block_desc* desc, int64_t* off
     Plan p;
     int rc = make_plan(desc, &p);
     if (rc != NND_OK) return rc;
-    for (int i = 0; offsets && i < n && i < C_COUNT; ++i) offsets[i] = p.L[i].arith == 2 ? p.L[i].tail_off() : -1;
+    for (int i = 0; offsets && i < n && i < C_COUNT; ++i) offsets[i] = p.L[i].range_scaled() ? p.L[i].tail_off() : -1;
     return C_COUNT;
 }
 
@@ -687,8 +687,37 @@ int nnd_update_block_calibration_finish(const nnd_update_block_desc* desc, float
     int64_t offs[C_COUNT];
     int n = 0;
     for (int i = 0; i < C_COUNT; ++i)
-        if (p.L[i].arith == 2 && (p.sep || (i != C_ZR2 && i != C_Q2 && i != C_ZR2X && i != C_Q2X && i != C_ZR2C && i != C_Q2C))) offs[n++] = p.L[i].tail_off();
+        if (p.L[i].range_scaled() && (p.sep || (i != C_ZR2 && i != C_Q2 && i != C_ZR2X && i != C_Q2X && i != C_ZR2C && i != C_Q2C))) offs[n++] = p.L[i].tail_off();
     return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
+}
+
+// One convolution of the block on its own: the workspace tensors it touches come from / go to NCHW tensors of the caller.
+int nnd_update_block_layer_forward(const nnd_update_block_desc* desc, const float* packed, int which, const float* const* in,
+                                   float* const* out, float* workspace, int B, int H, int W, void* stream) {
+    Plan p;
+    int rc = make_plan(desc, &p);
+    if (rc != NND_OK) return rc;
+    if ((rc = refuse_last_only(desc, "update_block_layer_forward")) != NND_OK) return rc;
+    NND_REQUIRE(packed && in && out && workspace && B > 0 && H > 0 && W > 0, "update_block_layer_forward: bad argument");
+    NND_REQUIRE(which > C_C1 && which < C_COUNT && which != C_F2, "update_block_layer_forward: convolution %d has no stand-alone launch here", which);
+    NND_REQUIRE(p.sep || (which != C_ZR2 && which != C_Q2 && which != C_ZR2X && which != C_Q2X && which != C_ZR2C && which != C_Q2C),
+                "update_block_layer_forward: conv_gru has no second GRU pass");
+    CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && split_range_scaled(p.d.arithmetic));
+    hipStream_t s = (hipStream_t)stream;
+    Bufs w;
+    carve(p, B, H, W, workspace, &w);
+    const int hid = p.d.hidden_dim, ctx = p.d.context_dim;
+    const int64_t n = tiled_plane(H, W);
+    // NND_UB_* order of the header: buffer, channels, 4-channel-interleaved (as conv_io lays them out)
+    struct { float* buf; int C; bool c4; } t[NND_UB_TENSORS] = {
+        {w.c1, 256, ws_c4()}, {w.cf, 256, ws_c4()}, {w.hx, 2 * hid + ctx, ws_c4()}, {w.z, hid, ws_c4()}, {w.rh, hid, ws_c4()},
+        {w.fm, 3 * hid, ws_c4()}, {w.ctxb, 6 * hid, ws_c4()}, {w.mask, p.d.mask_channels, false}};
+    for (int i = 0; i < NND_UB_TENSORS; ++i)
+        if (in[i]) NND_TRY(to_tiled(in[i], t[i].buf, (int64_t)t[i].C * n, B, t[i].C, H, W, s, 0, t[i].c4));
+    NND_TRY(run_conv(p, packed, w, which, act(w.corr, p.d.cor_planes * n, p.d.cor_planes), w.mask, w.delta, B, H, W, s));
+    for (int i = 0; i < NND_UB_TENSORS; ++i)
+        if (out[i]) NND_TRY(from_tiled(t[i].buf, (int64_t)t[i].C * n, out[i], B, t[i].C, H, W, s, 0, t[i].c4));
+    return NND_OK;
 }
 
 int64_t nnd_update_block_workspace_floats(const nnd_update_block_desc* desc, int B, int H, int W) {
@@ -708,7 +737,7 @@ int nnd_update_block_forward(const nnd_update_block_desc* desc, const float* pac
     if ((rc = refuse_last_only(desc, "update_block_forward")) != NND_OK) return rc;
     NND_REQUIRE(packed && net && inp && corr && flow && net_out && delta_out && workspace, "update_block_forward: null pointer");
     NND_REQUIRE(B > 0 && H > 0 && W > 0, "update_block_forward: bad shape");
-    CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && p.d.arithmetic == 2);
+    CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && split_range_scaled(p.d.arithmetic));
     hipStream_t s = (hipStream_t)stream;
     Bufs w;
     carve(p, B, H, W, workspace, &w);
@@ -798,7 +827,7 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
 
     NND_REQUIRE(p.d.mask_channels == 9 * rate * rate, "raft_stereo_refine: mask_channels %d != 9*rate^2", p.d.mask_channels);
     NND_REQUIRE(B > 0 && H > 0 && W > 0 && iters > 0, "raft_stereo_refine: bad shape");
-    CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && p.d.arithmetic == 2);
+    CalibScope calib((p.d.flags & NND_FLAG_CALIBRATE) && split_range_scaled(p.d.arithmetic));
     hipStream_t s = (hipStream_t)stream;
     Bufs w;
     carve(p, B, H, W, workspace, &w);
@@ -887,7 +916,7 @@ static int enqueue_refine(const nnd_update_block_desc* desc, const float* packed
     };
     // IGEV, fp16x2 convc1 inside the interleaved lookup: its operands are interpolated from the interleaved pyramid, whose largest
     // value bounds them (the sampler is a convex combination of two entries)
-    if (calibrating() && fused_lk && interleaved && p.L[C_C1].arith == 2 && igev_lookup_convc1_il_supported(groups, num_levels, radius))
+    if (calibrating() && fused_lk && interleaved && p.L[C_C1].range_scaled() && igev_lookup_convc1_il_supported(groups, num_levels, radius))
         NND_TRY(calib_amax_flat(interleaved, nnd_igev_interleaved_floats(B, groups, H, W, num_levels), packed + p.L[C_C1].tail_off(), s));
     for (int it = 0; it < iters; ++it) {
         // RAFT-Stereo, arithmetic 2: the flow branch and lookup + convc1 — independent of each other — as ONE launch of two
@@ -973,7 +1002,7 @@ static int conv2d_layer(int Cout, int Cin, int KH, int KW, int arithmetic, ConvL
     NND_REQUIRE(Cout > 0 && Cin > 0, "conv2d: bad channel counts");
     NND_REQUIRE(conv_shape_built(KH, KW), "conv2d: kernel %dx%d not built (1x1, 3x3, 1x5, 5x1)", KH, KW);
     NND_REQUIRE(arithmetic == 0 || conv_split_supported(KH, KW, Cin, 1, arithmetic),
-                "conv2d: arithmetic %d not built for %dx%d with %d input channels (3 = bf16x3 split, Cin %% 16 == 0)", arithmetic, KH, KW, Cin);
+                "conv2d: arithmetic %d not built for %dx%d with %d input channels (3 = bf16x3, 2 = fp16x2, 1 = fp16: Cin %% 16 == 0)", arithmetic, KH, KW, Cin);
     int64_t off = 0;
     *L = mk(KH, KW, Cin, Cout, &off, arithmetic);
     if (total) *total = off;
@@ -1021,7 +1050,7 @@ int nnd_conv2d_calibrate_ex(float* packed_dev, const float* x, int B, int Cin, i
     int rc = conv2d_layer(Cout, Cin, KH, KW, arithmetic, &L, nullptr);
     if (rc != NND_OK) return rc;
     NND_REQUIRE(packed_dev && x && B > 0 && H > 0 && W > 0, "conv2d_calibrate: bad argument");
-    if (L.arith != 2) return NND_OK;
+    if (!L.range_scaled()) return NND_OK;
     const int64_t n = (int64_t)H * W;
     rc = calib_amax_act(act(const_cast<float*>(x), Cin * n, Cin), make_lay(H, W, false), B, H, W, packed_dev + L.tail_off(), (hipStream_t)stream);
     if (rc != NND_OK) return rc;

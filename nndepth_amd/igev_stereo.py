@@ -160,8 +160,10 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
                  context_dim: int = 128, corr_levels: int = 4, corr_radius: int = 4, tracing: bool = False,
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
                  fused_loop: bool = True, arithmetic: str = "fp16x2", outputs: str = "all"):
+        """`arithmetic="fp16"` (one range-scaled fp16 piece, 11 significand bits) applies to the update block's 2-D convolutions; it is
+        not built for Conv3d, so under it the cost-volume regulariser runs "fp16x2"."""
         super().__init__()
-        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces), "fp32" (exact fp32 MFMA) or "fp16" (opt-in: ONE range-scaled fp16 piece, 11 significand bits, finite up to 32 x the calibrated maximum)
         self.outputs = check_outputs(outputs)  # "all": every iteration's up_disp; "last": [{"up_disp": final}] (raft_stereo.check_outputs)
         if update_cls != "basic_update_block":
             raise KeyError(update_cls)
@@ -173,7 +175,8 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
                                              arithmetic=arithmetic)
         self.cv_regularizer = self._init_cost_volume_filter()
         if hasattr(self.cv_regularizer, "arithmetic"):  # the HIP regulariser follows the model's arithmetic (5.4 -> 4.3 ms per
-            self.cv_regularizer.arithmetic = arithmetic  # 544x960 sample with fp16x2: profiles/r03_igev_regulariser_layers_*.txt)
+            # ("fp16" is not built for Conv3d: under it the regulariser runs "fp16x2")
+            self.cv_regularizer.arithmetic = "fp16x2" if arithmetic == "fp16" else arithmetic  # 544x960 sample with fp16x2: profiles/r03_igev_regulariser_layers_*.txt)
         self.corr_fn = GeometryAwareCostVolume
         self.cv_squeezer = nn.Conv3d(cv_groups, 1, 3, 1, 1)
         self._sq_cache = ops.ParamCache()

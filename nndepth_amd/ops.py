@@ -72,6 +72,18 @@ class ParamCache:
 # reading `c.status` afterwards synchronises: bit 0 = a layer saw inf / NaN at its old scale (run the block again), bit 1 = some
 # fp16x2 layer of an engine was not on the path.
 _calib_tls = threading.local()
+# the arithmetics whose operands are range-scaled fp16 pieces: they have a per-layer activation range to calibrate
+# ("fp16x2": two pieces, fp32 to rounding level; "fp16": one piece, 11 significand bits — csrc/split_arith.h)
+RANGE_SCALED = ("fp16x2", "fp16")
+
+
+def arithmetic_id(name: str) -> int:
+    """The descriptor value of an arithmetic name (UpdateBlockEngine.ARITHMETIC); NndError for an unknown one."""
+    if name not in UpdateBlockEngine.ARITHMETIC:
+        raise NndError(f"unknown arithmetic {name!r} (fp32 = exact fp32 MFMA, bf16x3 = 3-piece split on the bf16 MFMA, "
+                       "fp16x2 = 2-piece range-scaled split on the fp16 MFMA, fp16 = ONE range-scaled fp16 piece: 11 significand bits, "
+                       "not fp32 parity)")
+    return UpdateBlockEngine.ARITHMETIC[name]
 
 
 class _Calibration:
@@ -108,7 +120,7 @@ def _call_desc(engine, extra_flags: int = 0):
     `with calibration()` for an fp16x2 engine, plus `extra_flags`).  The engine's own descriptor is never written after
     __init__, so calls on one engine from several threads do not race on it and no flag reaches a later call."""
     d = type(engine.desc).from_buffer_copy(engine.desc)
-    d.flags = (_calib_flags(engine) if engine.arithmetic == "fp16x2" else 0) | extra_flags
+    d.flags = (_calib_flags(engine) if engine.arithmetic in RANGE_SCALED else 0) | extra_flags
     return d
 
 
@@ -195,11 +207,13 @@ def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, rate: int) -> torch.
 # ------------------------------------------------------------------------ generic conv2d
 class Conv2d:
     """One packed stride-1 "same" convolution (1x1, 3x3, 1x5, 5x1): arithmetic "fp32" = the exact fp32-MFMA kernel,
-    "bf16x3" = fp32 operands as 3 bf16 pieces on the bf16 MFMA (csrc/conv_split.hip, Cin % 16 == 0)."""
+    "bf16x3" = fp32 operands as 3 bf16 pieces on the bf16 MFMA (csrc/conv_split.hip, Cin % 16 == 0), "fp16x2" = as 2 range-scaled
+    fp16 pieces, "fp16" = as ONE range-scaled fp16 piece: 11 significand bits per operand (not fp32 parity), finite up to 32 x the
+    calibrated maximum |x| and inf / NaN beyond."""
 
     def __init__(self, weight: torch.Tensor, bias: torch.Tensor, device="cuda", arithmetic: str = "fp32"):
         self.Cout, self.Cin, self.KH, self.KW = (int(s) for s in weight.shape)
-        self.arith = UpdateBlockEngine.ARITHMETIC[arithmetic]
+        self.arith = arithmetic_id(arithmetic)
         n = int(lib.nnd_conv2d_packed_floats_ex(self.Cout, self.Cin, self.KH, self.KW, self.arith))
         if n <= 0:
             check(n, "conv2d_packed_floats")
@@ -211,7 +225,7 @@ class Conv2d:
         self.calibrated = False
 
     def calibrate(self, x: torch.Tensor) -> "Conv2d":
-        """fp16x2: set the layer's activation scale from the largest |x| of this input (include/nndepth_amd.h
+        """fp16x2 / fp16: set the layer's activation scale from the largest |x| of this input (include/nndepth_amd.h
         "fp16x2 activation range"); the other arithmetics have no range to calibrate."""
         d = _dev(x, self.packed)
         x = x.contiguous()
@@ -225,8 +239,8 @@ class Conv2d:
         return self
 
     def activation_range(self) -> float:
-        """Largest |x| the layer represents (fp16x2: 65504 / its activation scale; inf otherwise)."""
-        if self.arith != 2:
+        """Largest |x| the layer represents (fp16x2 / fp16: 65504 / its activation scale; inf otherwise)."""
+        if self.arith not in (1, 2):
             return float("inf")
         ncb = (self.Cout + 31) // 32
         n = self.packed.numel()
@@ -238,7 +252,7 @@ class Conv2d:
         B, Cin, H, W = x.shape
         if Cin != self.Cin:
             raise NndError(f"conv2d: input has {Cin} channels, weights expect {self.Cin}")
-        if self.arith == 2:
+        if self.arith in (1, 2):
             if getattr(_calib_tls, "active", None) is not None:  # inside `with calibration()`: a single layer calibrates on the spot
                 self.calibrate(x)
             else:
@@ -365,15 +379,15 @@ class _RefineCall(NamedTuple):
 class UpdateBlockEngine:
     """Packed parameters + workspace for one BasicUpdateBlock configuration."""
 
-    ARITHMETIC = {"fp32": 0, "bf16x3": 3, "fp16x2": 2}
+    # "fp16": ONE range-scaled fp16 piece per operand (11 significand bits: above the bf16 autocast the reference validates under,
+    # below fp32 parity; finite up to 32 x the calibrated maximum, inf / NaN beyond) — opt-in, never a default
+    ARITHMETIC = {"fp32": 0, "bf16x3": 3, "fp16x2": 2, "fp16": 1}
 
     def __init__(self, hidden_dim: int, context_dim: int, cor_planes: int, flow_channels: int,
                  mask_channels: int, gru: str = "sep_conv", arithmetic: str = "fp32"):
         if gru not in ("sep_conv", "conv_gru"):
             raise NndError(f"unknown gru kind {gru!r}")
-        if arithmetic not in self.ARITHMETIC:
-            raise NndError(f"unknown arithmetic {arithmetic!r} (fp32 = exact fp32 MFMA, bf16x3 = 3-piece split on the bf16 MFMA, "
-                           "fp16x2 = 2-piece range-scaled split on the fp16 MFMA)")
+        arithmetic_id(arithmetic)  # refuses an unknown name
         self.gru = gru
         self.arithmetic = arithmetic
         # split_layers: diagnostic subset of the convolutions that take the split arithmetic (bit = index in conv_names();
@@ -856,7 +870,7 @@ class EncoderEngine:
         self.norm = norm
         self.arithmetic = arithmetic
         self.desc = EncoderDesc(int(output_dim), {"none": 0, "batch": 1, "instance": 2}[norm], int(cnet_dim),
-                                UpdateBlockEngine.ARITHMETIC[arithmetic], 0)
+                                arithmetic_id(arithmetic), 0)
         self.calibrated = False
         n = int(lib.nnd_encoder_packed_floats(C.byref(self.desc)))
         if n <= 0:
@@ -1746,7 +1760,7 @@ class Conv3dNorm:
             raise NndError("Conv3dNorm: only 3x3x3 kernels")
         cin0 = split if split > 0 else Cin
         self.arithmetic = arithmetic
-        self.desc = Conv3dDesc(Cout, cin0, Cin - cin0, int(stride), UpdateBlockEngine.ARITHMETIC[arithmetic], 0)
+        self.desc = Conv3dDesc(Cout, cin0, Cin - cin0, int(stride), arithmetic_id(arithmetic), 0)
         self.calibrated = False
         self.leaky = float(leaky_slope)
         self.packed = _pack_conv_norm("conv3d", self.desc, weight, bias, bn, eps, device)

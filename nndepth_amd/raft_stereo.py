@@ -88,7 +88,10 @@ class AutoCalibrate:
     absolute error <= M * 2^-36 below, finite results up to 32 * M, inf / NaN in the output beyond (never a silently wrong value).
     With `auto_calibrate` (default) the first `forward()` after the parameters were (re)packed calibrates on its own input — one
     extra forward, once; call `calibrate()` yourself with representative frames to choose the data, or set
-    `auto_calibrate = False` to keep the default scales.  `activation_ranges()` reports the valid |x| per update-block layer."""
+    `auto_calibrate = False` to keep the default scales.  `activation_ranges()` reports the valid |x| per update-block layer.
+
+    The "fp16" arithmetic (opt-in) keeps the first of the two pieces only: 11 significand bits per operand — three more than the bf16
+    autocast the reference's trainers validate under, not fp32 parity — with the same scales, calibration and range behaviour."""
 
     auto_calibrate = True
 
@@ -107,7 +110,7 @@ class AutoCalibrate:
     def _forward_calibrated(self, *args, **kwargs):
         """`_forward`, calibrating first if an fp16x2 engine on its path still has the default activation scales."""
         check_outputs(getattr(self, "outputs", "all"))  # (an attribute: it may have been set after construction)
-        if self.arithmetic != "fp16x2" or not self.auto_calibrate:
+        if self.arithmetic not in ops.RANGE_SCALED or not self.auto_calibrate:
             return self._forward(*args, **kwargs)
         try:
             with ops.require_calibrated():
@@ -136,7 +139,7 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
                  fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
         super().__init__()
-        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces) or "fp32" (exact fp32 MFMA)
+        self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces), "fp32" (exact fp32 MFMA) or "fp16" (opt-in: ONE range-scaled fp16 piece, 11 significand bits, finite up to 32 x the calibrated maximum)
         self.outputs = check_outputs(outputs)  # "all": every iteration's up_disp; "last": [{"up_disp": final}] (check_outputs)
         self.iters, self.fnet_dim, self.hidden_dim, self.context_dim = iters, fnet_dim, hidden_dim, context_dim
         self.corr_levels, self.corr_radius = corr_levels, corr_radius
