@@ -591,6 +591,48 @@ int nnd_depth_eval(const float* pred, const float* gt, const unsigned char* vali
                    void* workspace, int64_t workspace_bytes, double* out, void* stream);
 int nnd_depth_eval_accumulate(const double* metrics, double* sums, double* counts, void* stream);
 
+/* ------------------------------------------------------------- value of the monocular training loss on the device (additions within 105)
+ * nnd_midas_loss : MiDasLoss.forward  nndepth/models/midas/loss.py:62-221 (what the trainer's validation loop scores a checkpoint
+ *     on, midas/trainer.py:168-180, 321-352).  The VALUE only: there is no backward.
+ *     pred (B,1,H,W) fp32 read through its batch and row strides (in elements; the innermost stride is 1; rows do not overlap), so a
+ *     cropped view is read where it lies; target (B,1,H,W) fp32 and valid_mask (B,1,H,W) bytes, both contiguous, the mask REQUIRED;
+ *     no input is written.  H, W >= 16, B <= 65535, B*H*W < 2^31.  Written p, t, m; everything after the fp32 loads in double:
+ *       1 n_b = valid pixels of sample b, n = sum n_b; tmin, tmax = min / max of t over the valid pixels of the whole batch;
+ *         tn = (t - tmin) / (tmax - tmin + 1e-6)  (normalize_01_depth, loss.py:56-58);
+ *       2 per sample, for tn and for p separately: shift = the lower median over the sample's valid pixels (sorted position
+ *         (n_b - 1) / 2, torch.median; tn is increasing in t, so it is the normalised median of the raw t), scale = mean |x - shift|,
+ *         a scale of exactly 0 becomes 1;  st = (tn - shift_t) / scale_t,  sp = (p - shift_p) / scale_p  (loss.py:6-43);
+ *       3 abs_dev = sum over valid pixels of |sp - st| / n  (loss.py:211-213);
+ *       4 trimmed_mae (loss.py:62-122, 201-203): per sample e = |sp - st| on its valid pixels, trim_b = (int64)((double)n_b * 0.1)
+ *         (Python's int(n * 0.1), computed on the device); trim_b == 0 (n_b < 10): the sample contributes nothing, the reference's
+ *         loss[:-0] being empty (a quirk, kept); otherwise the sum of its k_b = n_b - trim_b smallest e, and k_b pixels;
+ *         trimmed_mae = sum_b sum_b / sum_b k_b, 0 / 0 = NaN.  The k_b smallest of the double values: sum(e < tau) +
+ *         (k_b - count(e < tau)) * tau with tau the e of rank k_b - 1 (which of several equal values is kept does not matter);
+ *       5 gradient_reg (gradient_regulizer, loss.py:125-165) on T = tn with 0 at invalid pixels, P = sp (read at EVERY pixel, as
+ *         the reference does), M = m, for four levels: R = P - T; term(y,x) = |R(y,x) - R(y,x+1)| + |R(y,x) - R(y+1,x)| for
+ *         y < h-1, x < w-1, summed where M(y+1,x+1) is set (the reference's shifted mask, kept; selected, not multiplied: a NaN
+ *         behind a cleared bit does not enter); then T = 2x2 stride-2 max pool (floor sizes), M = M at the arg-max of T (the first
+ *         maximum in row-major window order, a NaN wins: max_pool2d(return_indices=True), as nnd_pool_abs restates it), P = 2x2
+ *         stride-2 mean over all four pixels.  gradient_reg = the sum over the four levels / n;
+ *       6 loss = trimmed_coef * trimmed_mae + gradient_coef * gradient_reg.
+ *     out (device, 6 doubles) = loss, trimmed_mae, gradient_reg, abs_dev, n, sum_b k_b.
+ *     Where this departs from the reference:  (a) the reference pools a fifth time and raises when H // 16 == 0 or W // 16 == 0:
+ *     H < 16 or W < 16 is refused here, before anything is launched;  (b) the reference raises on a batch without any valid pixel
+ *     (min() of an empty tensor); the device cannot raise without a synchronisation: out = NaN for the four values, 0 for both
+ *     counts;  (c) as in the reference, ONE sample without a valid pixel is no error: its median and scale are NaN, every use of them
+ *     is masked, it contributes nothing.
+ *     `workspace` = nnd_midas_loss_workspace_bytes(B, H, W) device bytes (8-byte aligned; a little over 1.3 doubles per pixel: e, and
+ *     the three pooled levels of T, P, M), checked against workspace_bytes.  Nine small launches on `stream`, no allocation, no host
+ *     synchronisation, no floating-point atomics: the same bits run to run, whatever workspace and out held before.  Non-finite
+ *     inputs inside the mask are outside the contract.
+ * nnd_midas_loss_accumulate : the validation loop's lists  nndepth/models/midas/trainer.py:341-350 as running sums:
+ *     sums[i] += values[i] for i < 6, count[0] += 1 (all device doubles); a NaN propagates as np.mean over those lists does.      */
+int64_t nnd_midas_loss_workspace_bytes(int B, int H, int W);
+int nnd_midas_loss(const float* pred, const float* target, const unsigned char* valid_mask, int B, int H, int W, int64_t pred_stride_b,
+                   int64_t pred_stride_row, double trimmed_coef, double gradient_coef, void* workspace, int64_t workspace_bytes,
+                   double* out, void* stream);
+int nnd_midas_loss_accumulate(const double* values, double* sums, double* count, void* stream);
+
 /* ------------------------------------------------------------- stereo evaluation of a whole forward on the device (additions within 104)
  * nnd_stereo_eval : EvalCriterion.__call__  nndepth/models/raft_stereo/scripts/evaluate.py:48-83 (likewise igev_stereo/ and
  *     cre_stereo/scripts/evaluate.py) for EVERY output of a forward in one call, with the per-output term and the value of the

@@ -196,6 +196,9 @@ SIGNATURES = {
     "nnd_depth_eval_workspace_bytes": (C.c_int64, [_I]),
     "nnd_depth_eval": (_I, [_P, _P, _P, _I, _I, _I, C.c_float, _P, C.c_int64, _P, _P]),
     "nnd_depth_eval_accumulate": (_I, [_P, _P, _P, _P]),
+    "nnd_midas_loss_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "nnd_midas_loss": (_I, [_P, _P, _P, _I, _I, _I, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.c_int64, _P, _P]),
+    "nnd_midas_loss_accumulate": (_I, [_P, _P, _P, _P]),
     "nnd_stereo_eval_workspace_bytes": (C.c_int64, [_I]),
     "nnd_stereo_eval": (_I, [C.POINTER(StereoEvalDesc), _P, C.c_int64, _P, _P]),
     "nnd_stereo_eval_accumulate": (_I, [_P, _I, _P, _P]),

@@ -16,8 +16,9 @@
 //                                                                                         -> P3[b][blk][12]
 //   4 median      grid (2 maps, B), one workgroup each: the lower median of the sample's g, and of its aligned p, over the
 //                 metric mask: radix select on the order-preserving integer key of the fp32 value, 4 passes of 8 bits with
-//                 an LDS histogram (integer atomics only).  The fit is monotone (decreasing for scale < 0), so the aligned
-//                 map's median is the aligned value of the raw p at the rank, mirrored if scale < 0   -> MED[b][2]
+//                 an LDS histogram (integer atomics only; rank_select of eval_chain.h, shared with midas_loss.hip).  The fit is
+//                 monotone (decreasing for scale < 0), so the aligned map's median is the aligned value of the raw p at the
+//                 rank, mirrored if scale < 0                                                       -> MED[b][2]
 //   5 ssi_scale   batch-global min / max from P3 (all samples), shift = normalised median; sum |xn - shift| for both maps
 //                                                                                         -> P5[b][blk][2]
 //   6 ssi_error   scale = mean |xn - shift| from P5 (0 -> 1); sum |ssi_p - ssi_g|, sum (.)^2 -> P6[b][blk][2]
@@ -27,12 +28,10 @@
 // the ten doubles are the same bits run to run.  Inputs are fp32; everything after the load is double.  Compiled with
 // -ffp-contract=off: aligned = p * scale + shift is a rounded product and a rounded sum, as the float64 statement of the
 // contract has it (the delta counts are compared with it exactly).
-#include "common.h"
+#include "eval_chain.h"
 
 namespace nnd {
 
-constexpr int DE_T = 256;      // threads of the reduction kernels
-constexpr int DE_GMAX = 64;    // blocks per sample at most
 constexpr int DE_MED_T = 1024;  // threads of a median workgroup
 constexpr int DE_MED_U = 8;     // pixels a median thread has in flight
 constexpr int DE_N1 = 3, DE_N2 = 2, DE_N3 = 12, DE_N5 = 2, DE_N6 = 2;
@@ -68,31 +67,6 @@ struct DeIn {
 
 __device__ __forceinline__ bool de_valid(const DeIn& a, long i) { return !a.mask || a.mask[i] != 0; }
 __device__ __forceinline__ bool de_metric(const DeIn& a, long i, float g) { return de_valid(a, i) && g > a.lo && g < a.hi; }
-
-// sums acc[0..N) over the block in a fixed tree; the totals are in sh[0][*] afterwards
-template <int N>
-__device__ __forceinline__ void de_block_sum(double (&acc)[N], double (*sh)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) sh[threadIdx.x][i] = acc[i];
-    __syncthreads();
-    for (int s = DE_T / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-#pragma unroll
-            for (int i = 0; i < N; ++i) sh[threadIdx.x][i] += sh[threadIdx.x + s][i];
-        __syncthreads();
-    }
-}
-
-// tot[q] = sum over blk < G of part[blk * N + q], in index order (thread q); visible to the block after the barrier
-template <int N>
-__device__ __forceinline__ void de_sum_partials(const double* __restrict__ part, int G, double* tot) {
-    if ((int)threadIdx.x < N) {
-        double s = 0.0;
-        for (int k = 0; k < G; ++k) s += part[(long)k * N + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
 
 // scale, shift of sample b from the two stages of partial sums (evaluate.py:129-145): unaligned (1, 0) up to 100 valid pixels;
 // a constant prediction c takes the minimum-norm solution torch.linalg.lstsq returns on the CPU
@@ -207,19 +181,12 @@ __global__ void __launch_bounds__(DE_T) de_metrics_kernel(DeIn a, const double* 
     if (threadIdx.x < DE_N3) p3[((long)b * G + blockIdx.x) * DE_N3 + threadIdx.x] = sh[0][threadIdx.x];
 }
 
-// order-preserving key of an fp32 value (-0.0 sorts before +0.0: the same number either way)
-__device__ __forceinline__ unsigned de_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float de_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 // blockIdx.x: 0 = gt, 1 = prediction; blockIdx.y: sample.  med[2b + map] = the raw fp32 value whose (aligned) value is the lower
 // median, position (n - 1) / 2 of the sorted values, of the sample's n pixels in the metric mask; untouched if n == 0
 __global__ void __launch_bounds__(DE_MED_T) de_median_kernel(DeIn a, int G, const double* __restrict__ fit, const double* __restrict__ p3,
                                                              double* __restrict__ med) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_prefix, s_rank;
+    __shared__ RankSelectLds<unsigned> lds;
+    __shared__ unsigned s_rank;
     __shared__ int s_n;
     const int map = blockIdx.x, b = blockIdx.y;
     if (threadIdx.x == 0) {
@@ -229,7 +196,6 @@ __global__ void __launch_bounds__(DE_MED_T) de_median_kernel(DeIn a, int G, cons
         unsigned rank = n > 0.0 ? (unsigned)(((long)n - 1) / 2) : 0u;
         if (map == 1 && fit[2 * b] < 0.0) rank = (unsigned)((long)n - 1) - rank;  // decreasing fit: count from the other end
         s_rank = rank;
-        s_prefix = 0u;
     }
     __syncthreads();
     if (s_n == 0) return;  // the whole block
@@ -237,49 +203,15 @@ __global__ void __launch_bounds__(DE_MED_T) de_median_kernel(DeIn a, int G, cons
     const float* g = a.gt + (long)b * a.HW;
     DeIn s = a;
     if (s.mask) s.mask += (long)b * a.HW;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int j = threadIdx.x; j < 256; j += DE_MED_T) hist[j] = 0u;
-        __syncthreads();
-        const unsigned prefix = s_prefix;
-        const unsigned long long himask = ~0ull << (shift + 8);  // the bits already decided
-        // DE_MED_U pixels per thread and trip, their loads issued together (a pixel past the end reads pixel 0 and is not counted)
-        for (long base = threadIdx.x; base < a.HW; base += (long)DE_MED_T * DE_MED_U) {
-            float gv[DE_MED_U], vv[DE_MED_U];
-            bool ok[DE_MED_U];
-#pragma unroll
-            for (int j = 0; j < DE_MED_U; ++j) {
-                const long i = base + (long)j * DE_MED_T;
-                ok[j] = i < a.HW;
-                const long ii = ok[j] ? i : 0;
-                gv[j] = g[ii];
-                vv[j] = v[ii];
-                if (s.mask) ok[j] = ok[j] && s.mask[ii] != 0;
-            }
-#pragma unroll
-            for (int j = 0; j < DE_MED_U; ++j) {
-                if (!(ok[j] && gv[j] > a.lo && gv[j] < a.hi)) continue;
-                const unsigned key = de_key(vv[j]);
-                if (((unsigned long long)(key ^ prefix) & himask & 0xffffffffull) == 0ull) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned rank = s_rank, cum = 0u, digit = 255u;
-            bool found = false;
-            for (int j = 0; j < 256; ++j) {
-                if (!found && cum + hist[j] > rank) {
-                    digit = (unsigned)j;
-                    rank -= cum;
-                    found = true;
-                }
-                cum += hist[j];
-            }
-            s_rank = rank;
-            s_prefix = prefix | (digit << shift);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) med[2 * b + map] = (double)de_unkey(s_prefix);
+    const unsigned key = rank_select<unsigned, DE_MED_T, DE_MED_U>(
+        a.HW, s_rank,
+        [&](long i, unsigned& k) {
+            const float gv = g[i];
+            k = de_key(v[i]);
+            return de_valid(s, i) && gv > a.lo && gv < a.hi;
+        },
+        lds);
+    if (threadIdx.x == 0) med[2 * b + map] = (double)de_unkey(key);
 }
 
 // the batch-global range of g and of the aligned p over the metric mask, from every sample's partials; r[0..4) = gmin, gmax,

@@ -3,7 +3,8 @@
 `EvalCriterion` (nndepth/models/raft_stereo/scripts/evaluate.py:29-83) that keep the frames and the disparity on the GPU, for
 the stereo scripts' criterion, sequence loss and dataset mean over every output of a forward (`StereoEvalCriterion`,
 `StereoEvalMean`: evaluate.py:48-83, 141-169, loss.py:15-52), and for `DepthEvalCriterion` with its dataset mean
-(nndepth/models/midas/scripts/evaluate.py:38-211, 300-312) on the monocular side."""
+(nndepth/models/midas/scripts/evaluate.py:38-211, 300-312) and the value of `MiDasLoss` with the validation loop's mean
+(nndepth/models/midas/loss.py:62-221, trainer.py:321-352) on the monocular side."""
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
@@ -351,3 +352,88 @@ class DepthEvalMean:
         sums, counts = self._acc.cpu().tolist() if self._acc is not None else ([0.0] * 9, [0.0] * 9)
         return {k: (s / c if c > 0 else (0.0 if k.startswith("delta") else float("inf")))
                 for k, s, c in zip(DEPTH_METRICS, sums, counts)}
+
+
+MIDAS_LOSS_METRICS = ("loss", "trimmed_mae", "gradient_reg", "abs_dev")
+_MIDAS_LOSS_WS: Dict[str, torch.Tensor] = {}  # per device, grown to the largest batch of maps seen
+
+
+class MiDasLoss:
+    """The value of the reference's MiDasLoss (nndepth/models/midas/loss.py:168-221) computed on the device: the trimmed
+    scale-and-shift-invariant error, the four-level gradient term and the absolute deviation, in float64 (nnd_midas_loss states
+    every step and the three places where it departs from the reference).  A value only: there is no backward, so a prediction
+    that asks for a gradient is refused.  The maps stay on the GPU and are never modified; six doubles come back."""
+
+    def __init__(self, trimmed_loss_coef: float = 1.0, gradient_reg_coef: float = 0.1):
+        self.trimmed_loss_coef = trimmed_loss_coef
+        self.gradient_reg_coef = gradient_reg_coef
+
+    def values_tensor(self, pred: torch.Tensor, target: torch.Tensor, valid_mask: torch.Tensor) -> torch.Tensor:
+        """(6,) float64 on the device: loss, trimmed_mae, gradient_reg, abs_dev, the number of valid pixels, the number of pixels
+        the trimmed error was taken over.  No host synchronisation, allocations through PyTorch only: it can be captured into a HIP
+        graph (call once before the capture, so that the device's workspace exists)."""
+        what = "MiDasLoss"
+        if not (torch.is_tensor(pred) and torch.is_tensor(target)):
+            raise NndError(f"{what}: pred and target are tensors on the HIP device")
+        if valid_mask is None:
+            raise NndError(f"{what}: valid_mask is required (torch.bool or torch.uint8, the shape of pred)")
+        if not torch.is_tensor(valid_mask) or valid_mask.dtype not in (torch.bool, torch.uint8):
+            raise NndError(f"{what}: valid_mask is torch.bool or torch.uint8; got {getattr(valid_mask, 'dtype', type(valid_mask))}")
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise NndError(f"{what}: pred and target are fp32; got {pred.dtype} and {target.dtype}")
+        if pred.dim() != 4 or pred.shape[1] != 1:
+            raise NndError(f"{what}: maps are (B,1,H,W); got pred {tuple(pred.shape)}")
+        if target.shape != pred.shape or valid_mask.shape != pred.shape:
+            raise NndError(f"{what}: pred {tuple(pred.shape)}, target {tuple(target.shape)}, valid_mask {tuple(valid_mask.shape)} "
+                           "must have one shape")
+        B, _, H, W = pred.shape
+        if H < 16 or W < 16:
+            raise NndError(f"{what}: maps of {H}x{W}: H and W must be at least 16 (four levels of 2x2 pooling; the reference raises "
+                           "below that too)")
+        d = _dev(pred, target)
+        if pred.requires_grad and torch.is_grad_enabled():
+            raise NndError(f"{what}: pred requires grad, but this is the loss's value and has no backward (call it under "
+                           "torch.no_grad(), as the validation loop does, or detach the prediction)")
+        p = pred.detach()
+        if p.stride(3) != 1:
+            p = p.contiguous()  # kept alive across the call
+        tgt = target.detach().contiguous()
+        mask = _mask_bytes(valid_mask, tgt, what)
+        ws = _cached_workspace(_MIDAS_LOSS_WS, d, lib.nnd_midas_loss_workspace_bytes(B, H, W))
+        out = torch.empty(6, dtype=torch.float64, device=d)
+        with torch.cuda.device(d):
+            check(lib.nnd_midas_loss(_p(p), _p(tgt), _p(mask), B, H, W, p.stride(0), p.stride(2), float(self.trimmed_loss_coef),
+                                     float(self.gradient_reg_coef), _p(ws), ws.numel() * 8, _p(out), _stream(d)), "midas_loss")
+        return out
+
+    def __call__(self, pred: torch.Tensor, target: torch.Tensor, valid_mask: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, float]]:
+        """(loss, metrics) as the reference returns them: the loss a 0-dim float64 device tensor, the metrics Python floats from one
+        copy of the six doubles."""
+        values = self.values_tensor(pred, target, valid_mask)
+        return values[0], dict(zip(MIDAS_LOSS_METRICS, values.cpu().tolist()[:4]))
+
+
+class MiDasLossMean:
+    """The validation loop's mean over batches (midas/trainer.py:341-350) kept on the device: `update` only enqueues the batch's
+    loss and adds its doubles to running sums; `result` copies the sums once and divides by the number of updates, which is np.mean
+    of the per-batch values: a NaN propagates, as it does in the reference."""
+
+    def __init__(self, trimmed_loss_coef: float = 1.0, gradient_reg_coef: float = 0.1):
+        self.criterion = MiDasLoss(trimmed_loss_coef, gradient_reg_coef)
+        self._acc: Optional[torch.Tensor] = None  # (7,) float64: the six sums, the number of updates
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor, valid_mask: torch.Tensor) -> None:
+        v = self.criterion.values_tensor(pred, target, valid_mask)
+        if self._acc is None:
+            self._acc = torch.zeros(7, dtype=torch.float64, device=v.device)
+        elif self._acc.device != v.device:
+            raise NndError(f"MiDasLossMean: batches on {self._acc.device} and on {v.device}")
+        with torch.cuda.device(v.device):
+            check(lib.nnd_midas_loss_accumulate(_p(v), _p(self._acc), _p(self._acc[6:]), _stream(v.device)), "midas_loss_accumulate")
+
+    def result(self) -> Dict[str, float]:
+        keys = [f"val/{k}" for k in MIDAS_LOSS_METRICS]
+        if self._acc is None:
+            return {k: float("nan") for k in keys}  # np.mean of an empty list
+        acc = self._acc.cpu().tolist()
+        return {k: s / acc[6] for k, s in zip(keys, acc[:4])}
