@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define NND_VERSION 105 /* 0.1.5: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning); 105 the single-output EPE criterion's two symbols (the entry point and its workspace query) are removed: nnd_stereo_eval with one output is that criterion */
+#define NND_VERSION 105 /* 0.1.5: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning); 105 the single-output EPE criterion's two symbols (the entry point and its workspace query) are removed: nnd_stereo_eval with one output is that criterion (nnd_igev_init_disparity_dev — any G <= 64, D <= 4096, parameters read from device memory — with its queries nnd_igev_init_disparity_supported / _chunk / _kernel, and nnd_resize_nearest_scaled are additions within 105: nothing existing changed its signature or meaning) */
 
 /* Descriptors start with `struct_size` = sizeof(the descriptor type) of the header the caller was compiled against; every entry
  * point that takes one refuses another size (NND_ERR_INVALID), so a caller and a library of different versions cannot
@@ -175,9 +175,24 @@ int nnd_softargmin_disparity(const float* logits, float* out, int B, int D, int 
 /* cv_squeezer + regress_disparity in one pass (nndepth/models/igev_stereo/model.py:63,144-146): geo_level0 = level 0 of
  * the geometry pyramid, rows (b,g,h,w1) of D floats (GeometryAwareCostVolume.geo_aware_cv[0]); weight = the
  * Conv3d(G,1,3,1,1) kernel (1,G,3,3,3) over (candidate, h, w1), bias (1) or NULL — both HOST pointers (they travel as
- * kernel arguments); out (B,1,H,W) = -sum_d d * softmax_d(conv3d(geo)).  G <= 8, D <= 512, else NND_ERR_UNSUPPORTED. */
+ * kernel arguments); out (B,1,H,W) = -sum_d d * softmax_d(conv3d(geo)).  G <= 8, D <= 512, else NND_ERR_UNSUPPORTED.
+ * nnd_igev_init_disparity_dev: the same operation for G <= 64 and D <= 4096 (frames up to 16384 px wide at 1/4 resolution), else
+ * NND_ERR_UNSUPPORTED (the soft-argmin follows ATen's summation order, which opens another accumulator level beyond 4096 rows;
+ * beyond either limit the caller composes a Conv3d of its own with nnd_softargmin_disparity).  weight_dev / bias_dev (bias may
+ * be NULL) are DEVICE pointers the caller owns: the kernel stages them to LDS, there is no host copy and no synchronisation, so the
+ * call captures into a HIP graph.  It always runs the chunked kernel (the candidate axis walked in chunks of
+ * nnd_igev_init_disparity_chunk() candidates, the logits kept in LDS), also at shapes nnd_igev_init_disparity serves; the two
+ * entry points agree to within the fp32 order of the 27 G products, not bit for bit.  B <= 65535.
+ * nnd_igev_init_disparity_supported(G, D): 1 when one of the two entry points serves the shape (1 <= G <= 64, 1 <= D <= 4096).
+ * nnd_igev_init_disparity_kernel: the name of the kernel that serves the shape — nnd_igev_init_disparity's choice for G <= 8 and
+ * D <= 512 (under the current NND_IGEV_SQUEEZE_* switches), the chunked kernel otherwise — or NULL for an unsupported one. */
 int nnd_igev_init_disparity(const float* geo_level0, const float* weight_host, const float* bias_host, float* out,
                             int B, int G, int H, int W, int D, void* stream);
+int nnd_igev_init_disparity_dev(const float* geo_level0, const float* weight_dev, const float* bias_dev, float* out,
+                                int B, int G, int H, int W, int D, void* stream);
+int nnd_igev_init_disparity_supported(int G, int D);
+int nnd_igev_init_disparity_chunk(void);
+const char* nnd_igev_init_disparity_kernel(int B, int G, int H, int W, int D);
 
 /* ----------------------------------------------------------------------- convex upsample
  * Replaces RAFTStereo.convex_upsample  nndepth/models/raft_stereo/model.py:93-105
@@ -319,6 +334,10 @@ int nnd_conv2d_offset_forward(const float* packed_dev, const float* x, float* y,
  *                          (N,C,H/4,W/4) in one pass                           cre_stereo/model.py:154-177
  * nnd_resize_bilinear_ac : y (N,C,H,W) = mul * F.interpolate(x (N,C,h,w), (H,W), mode="bilinear", align_corners=True)
  *                          cre_stereo/model.py:205-212,235-241,259-265 (flow hand-over between cascade stages)
+ * nnd_resize_nearest_scaled : y (N,1,H,W) = mul * F.interpolate(x (N,1,h,w), size=(H,W)) (mode "nearest"), the frame-size stage
+ *                          outputs of the Coarse2Fine cascade, raft_stereo/model.py:309-314: y[n,oy,ox] = mul * x[n, oy*h/H, ox*w/W].
+ *                          H % h == 0 and W % w == 0 (integer ratios in both axes), else NND_ERR_INVALID; bit-identical to the
+ *                          PyTorch expression, NaN and signed zeros included.
  * nnd_pos_enc_sine_add   : y = x + pe[:, :, :H, :W], PositionEncodingSine.forward  nndepth/blocks/pos_enc.py:22-42 (used at
  *                          cre_stereo/model.py:180-196): the table is generated on the fly, pe[4k+j] = sin / cos (j odd) of
  *                          pos * exp(2k * rate), pos = column + 1 (j < 2) or row + 1, rate = the reference's
@@ -329,6 +348,7 @@ int nnd_pos_enc_sine_add(const float* x0, const float* x1, float* y0, float* y1,
                          void* stream);
 int nnd_avg_pool_2x_4x(const float* x, float* out2, float* out4, int N, int C, int H, int W, void* stream);
 int nnd_resize_bilinear_ac(const float* x, float* y, int N, int C, int h, int w, int H, int W, float mul, void* stream);
+int nnd_resize_nearest_scaled(const float* x, float* y, int N, int h, int w, int H, int W, float mul, void* stream);
 
 /* Convolution + folded eval-mode BatchNorm + ReLU / residual epilogue (the building block of the encoder):
  *   y = conv(x; w, stride, "same" padding K/2) ; y = (y + bias - mean) * gamma / sqrt(var + eps) + beta   [norm optional]

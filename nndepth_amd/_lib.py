@@ -98,6 +98,10 @@ SIGNATURES = {
     "nnd_igev_lookup": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_softargmin_disparity": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "nnd_igev_init_disparity": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "nnd_igev_init_disparity_dev": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "nnd_igev_init_disparity_supported": (_I, [_I, _I]),
+    "nnd_igev_init_disparity_chunk": (_I, []),
+    "nnd_igev_init_disparity_kernel": (C.c_char_p, [_I, _I, _I, _I, _I]),
     "nnd_convex_upsample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nnd_bilinear_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nnd_agcl_corr_iter": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -127,6 +131,7 @@ SIGNATURES = {
     "nnd_split_tanh_relu": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nnd_avg_pool_2x_4x": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "nnd_resize_bilinear_ac": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P]),
+    "nnd_resize_nearest_scaled": (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_float, _P]),
     "nnd_mask_upsample_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nnd_raft_stereo_refine": (_I, [C.POINTER(UpdateBlockDesc), _P, _P, _I, _I, _P, _P, _P, _P, C.c_int64, _P, _P, _P,
                                     _I, _I, _I, _I, _I, _P]),

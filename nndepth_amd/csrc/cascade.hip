@@ -94,6 +94,29 @@ __global__ void __launch_bounds__(256) resize_bilinear_ac_kernel(const float* __
     y[plane * H * W + idx] = mul * fmaf(t1, ly1, t0 * ly0);
 }
 
+// mul * F.interpolate(x, size=(H, W)) (mode "nearest") for a stack of single-channel maps, the frame-size outputs of the
+// Coarse2Fine cascade (raft_stereo/model.py:309-314).  Source index = min(int(floorf(dst * (float)in / out)), in - 1), ATen's
+// own arithmetic, = floor(dst * in / out) for the integer ratios the entry point admits.  A store kernel: the coarse map stays in
+// cache, a thread writes V consecutive outputs of a row (V = 4: one 16-byte store).
+template <int V>
+__global__ void __launch_bounds__(256) resize_nearest_scaled_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w, int H,
+                                                                    int W, float mul, long total) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // (map, row, unit of V columns)
+    if (idx >= total) return;
+    const int WV = W / V;
+    const long row = idx / WV;
+    const int ox = (int)(idx - row * WV) * V, oy = (int)(row % H);
+    const long n = row / H;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const float* src = x + (n * h + min((int)floorf((float)oy * sy), h - 1)) * w;
+    float v[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = mul * src[min((int)floorf((float)(ox + i) * sx), w - 1)];
+    float* dst = y + row * W + ox;
+    if (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    else dst[0] = v[0];
+}
+
 }  // namespace nnd
 
 using namespace nnd;
@@ -135,6 +158,24 @@ int nnd_resize_bilinear_ac(const float* x, float* y, int N, int C, int h, int w,
     NND_REQUIRE(x && y && N > 0 && C > 0 && h > 0 && w > 0 && H > 0 && W > 0, "resize_bilinear_ac: bad argument");
     hipLaunchKernelGGL(resize_bilinear_ac_kernel, dim3((unsigned)cdiv64((long)H * W, 256), (unsigned)(N * C)), dim3(256), 0,
                        (hipStream_t)stream, x, y, h, w, H, W, mul);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+int nnd_resize_nearest_scaled(const float* x, float* y, int N, int h, int w, int H, int W, float mul, void* stream) {
+    NND_REQUIRE(x && y, "resize_nearest_scaled: null pointer");
+    NND_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0, "resize_nearest_scaled: bad shape");
+    NND_REQUIRE(H % h == 0 && W % w == 0, "resize_nearest_scaled: %dx%d -> %dx%d is not an integer ratio in both axes", h, w, H, W);
+    const int V = (W & 3) == 0 ? 4 : 1;
+    const long total = (long)N * H * (W / V);
+    NND_REQUIRE(cdiv64(total, 256) < (1L << 31), "resize_nearest_scaled: grid of %ld workgroups too large (max 2^31 - 1)",
+                (long)cdiv64(total, 256));
+    if (V == 4)
+        hipLaunchKernelGGL(resize_nearest_scaled_kernel<4>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, h, w,
+                           H, W, mul, total);
+    else
+        hipLaunchKernelGGL(resize_nearest_scaled_kernel<1>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, h, w,
+                           H, W, mul, total);
     NND_LAUNCH_CHECK();
     return NND_OK;
 }

@@ -1919,6 +1919,218 @@ __global__ void __launch_bounds__(SQW_T, 2) igev_squeeze_walk_kernel(const float
     }
 }
 
+// The same operation for any group count up to SQG_MAXG and any candidate count up to SQG_MAXD (every shape the two kernels above
+// are not built for: G > 8 or D > 512).  One workgroup = SQ_PX pixels of one image row, as in the one-row kernel, but
+//   - the candidate axis is walked in chunks of SQG_C: per (chunk, group) the 3 x (SQ_PX + 2) neighbour rows are staged with one
+//     candidate of halo either side (the halo is the volume's own value; the zero pad sits at d = -1 and d = D only), thread =
+//     (candidate of the chunk, half of the pixels); the next (chunk, group) is fetched into registers while this one is multiplied;
+//   - a chunk's finished logits are parked in LDS (SQ_PX x D floats, row stride DL: an odd number of 16-byte units), and the
+//     soft-argmin runs once over all of them in the reference's evaluation order (softargmin_kernel), with ATen's cascade written
+//     out to its fourth accumulator (every 16 x 16 blocks; at D <= 4096 it only ever receives the final flush);
+//   - the 27 G weights and the bias are read from DEVICE memory and staged to LDS once per workgroup.
+// The sum over (g, kh, column, kw, kd) runs in that order, one FMA per term (this unit is built with -ffp-contract=off).
+constexpr int SQG_C = 128, SQG_T = 2 * SQG_C, SQG_MAXG = 64, SQG_MAXD = 4096, SQG_PXT = SQ_PX / 2;
+constexpr int SQG_DS = SQG_C + 8;             // staged row: candidate d0 - 1 at +3, the chunk from +4 (16-byte stores), candidate d0 + cl behind it
+constexpr int SQG_NROW = 3 * (SQ_PX + 2);     // staged rows [kh][column]
+constexpr int SQG_NL = (SQG_NROW * (SQG_C / 4) + SQG_T - 1) / SQG_T;  // 16-byte units of a thread per (chunk, group)
+static inline int sqg_logit_stride(int D) {
+    const int D4 = (D + 3) & ~3;
+    return ((D4 >> 2) & 1) ? D4 : D4 + 4;
+}
+__host__ __device__ static inline int sqg_weight_floats(int G) { return (27 * G + 3) & ~3; }
+static inline size_t sqg_lds_bytes(int G, int D) {
+    return sizeof(float) * ((size_t)SQG_NROW * SQG_DS + sqg_weight_floats(G) + 16 + (size_t)SQ_PX * sqg_logit_stride(D));
+}
+static_assert(sizeof(float) * (SQG_NROW * SQG_DS + ((27 * SQG_MAXG + 3) & ~3) + 16 + SQ_PX * (SQG_MAXD + 4)) <= 160 * 1024,
+              "the largest shape's staged rows, weights and parked logits fit in the LDS of a CU");
+
+__global__ void __launch_bounds__(SQG_T) igev_squeeze_general_kernel(const float* __restrict__ geo, const float* __restrict__ wdev,
+                                                                     const float* __restrict__ bdev, float* __restrict__ out, int G,
+                                                                     int H, int W, int D, int DL) {
+    extern __shared__ float sm[];  // staged rows [SQG_NROW][SQG_DS], weights [g][kd][kh][kw], maxima [8] + denominators [8], logits [SQ_PX][DL]
+    float* wl = sm + SQG_NROW * SQG_DS;
+    float* red = wl + sqg_weight_floats(G);
+    float* lg = red + 16;
+    const int tid = threadIdx.x, dl = tid & (SQG_C - 1), half = tid >> 7, lane = tid & 63, wave = tid >> 6;
+    static_assert(SQG_C == 128 && SQG_T == 256, "thread = (candidate of the chunk, pixel half)");
+    // XCD-aware mapping of the one-row kernel: XCD x gets the band of image rows [x*band, (x+1)*band)
+    const int nx = (W + SQ_PX - 1) / SQ_PX, band = (H + 7) / 8;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int h = xcd * band + slot / nx, w0 = (slot % nx) * SQ_PX, b = blockIdx.z;
+    if (h >= H) return;
+    for (int i = tid; i < 27 * G; i += SQG_T) wl[i] = wdev[i];
+    const float bias = bdev ? bdev[0] : 0.f;
+    auto row_rel = [&](int r, bool& ok) {  // floats from pixel (h, w0)'s row of a group to staged row r's; ok: that pixel exists
+        const int kh = r / (SQ_PX + 2), c = r - kh * (SQ_PX + 2);
+        const int hh = h + kh - 1, ww = w0 + c - 1;
+        ok = hh >= 0 && hh < H && ww >= 0 && ww < W;
+        return ((kh - 1) * W + (c - 1)) * D;
+    };
+    auto group_base = [&](int g) { return geo + ((((long)b * G + g) * H + h) * W + w0) * D; };
+    // D % 4 == 0: 16-byte loads into registers one (chunk, group) ahead; the unit -> (row, quad) map does not depend on the step
+    const bool vec = (D & 3) == 0;
+    float4 stage[SQG_NL];
+    float halo = 0.f;
+    int urel[SQG_NL], uq4[SQG_NL], udst[SQG_NL];  // a unit: floats from the group's base to its row, its first candidate in the chunk, its LDS offset
+    bool uok[SQG_NL];  // its row lies inside the image
+#pragma unroll
+    for (int k = 0; k < SQG_NL; ++k) {
+        const int i = tid + SQG_T * k;
+        const bool in = i < SQG_NROW * (SQG_C / 4);
+        const int r = in ? i / (SQG_C / 4) : 0, q = i % (SQG_C / 4);
+        bool ok;
+        urel[k] = row_rel(r, ok);
+        uok[k] = ok;
+        uq4[k] = in ? 4 * q : SQG_C;  // never below a chunk's length: the unit is skipped
+        udst[k] = r * SQG_DS + 4 + 4 * q;
+    }
+    bool hok = false;
+    const int hrel = row_rel(min(tid >> 1, SQG_NROW - 1), hok);  // threads 0 .. 2 NROW - 1: the halo of row tid / 2, left (even) or right
+    hok = hok && tid < 2 * SQG_NROW;
+    auto fetch = [&](int g, int d0, int cl) {
+        const float* base = group_base(g);
+#pragma unroll
+        for (int k = 0; k < SQG_NL; ++k) {
+            const bool in = uok[k] && uq4[k] < cl;
+            const float4 v = *reinterpret_cast<const float4*>(base + (in ? urel[k] + d0 + uq4[k] : d0));
+            stage[k] = in ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const int d = (tid & 1) ? d0 + cl : d0 - 1;
+        const bool in = hok && d >= 0 && d < D;
+        const float v = base[in ? hrel + d : d0];
+        halo = in ? v : 0.f;
+    };
+    auto commit = [&](int cl) {
+#pragma unroll
+        for (int k = 0; k < SQG_NL; ++k)
+            if (uq4[k] < cl) *reinterpret_cast<float4*>(sm + udst[k]) = stage[k];
+        if (tid < 2 * SQG_NROW) sm[(tid >> 1) * SQG_DS + ((tid & 1) ? 4 + cl : 3)] = halo;
+    };
+    auto stage_scalar = [&](int g, int d0, int cl) {  // any D: scalar loads straight into LDS, two rows at a time
+        const float* base = group_base(g);
+        for (int r = half; r < SQG_NROW; r += 2) {
+            bool ok;
+            const int rel = row_rel(r, ok);
+            for (int j = dl; j < cl + 2; j += SQG_C) {
+                const int d = d0 - 1 + j;
+                sm[r * SQG_DS + 3 + j] = (ok && d >= 0 && d < D) ? base[rel + d] : 0.f;
+            }
+        }
+    };
+    float acc[SQG_PXT];
+#pragma unroll
+    for (int p = 0; p < SQG_PXT; ++p) acc[p] = 0.f;
+    const int nchunk = (D + SQG_C - 1) / SQG_C;
+    if (vec) fetch(0, 0, min(SQG_C, D));
+    for (int k = 0; k < nchunk; ++k) {
+        const int d0 = k * SQG_C, cl = min(SQG_C, D - d0);
+        for (int g = 0; g < G; ++g) {
+            __syncthreads();  // the previous step's reads of the staged rows (and, once, the weights' staging) are done
+            if (vec) commit(cl);
+            else stage_scalar(g, d0, cl);
+            __syncthreads();
+            if (vec) {
+                if (g + 1 < G) fetch(g + 1, d0, cl);
+                else if (k + 1 < nchunk) fetch(0, d0 + SQG_C, min(SQG_C, D - d0 - SQG_C));
+            }
+            float w[27];
+#pragma unroll
+            for (int i = 0; i < 27; ++i) w[i] = wl[g * 27 + i];
+            const float* cols = sm + (SQG_PXT * half) * SQG_DS + 3 + dl;  // candidates d - 1, d, d + 1 of this thread's columns
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                for (int c = 0; c < SQG_PXT + 2; ++c) {
+                    const float* row = cols + (kh * (SQ_PX + 2) + c) * SQG_DS;
+                    const float r0 = row[0], r1 = row[1], r2 = row[2];
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        const int p = c - kw;
+                        if (p >= 0 && p < SQG_PXT)
+                            acc[p] = fmaf(w[2 * 9 + kh * 3 + kw], r2, fmaf(w[1 * 9 + kh * 3 + kw], r1, fmaf(w[0 * 9 + kh * 3 + kw], r0, acc[p])));
+                    }
+                }
+        }
+#pragma unroll
+        for (int p = 0; p < SQG_PXT; ++p) {  // threads beyond the chunk's length multiplied stale rows: not parked
+            if (dl < cl) lg[(SQG_PXT * half + p) * DL + d0 + dl] = acc[p] + bias;
+            acc[p] = 0.f;
+        }
+    }
+    __syncthreads();
+    // soft-argmin of the SQ_PX parked rows in the reference's evaluation order: max, e = exp(l - max), the sum of e strictly in
+    // order of d, terms d * (e / sum), ATen's cascade over them.  Candidates D .. DL - 1 of a row are zeros from here on: adding
+    // them changes no bit, so the ordered chains read whole 16-byte units.
+    for (int p = wave; p < SQ_PX; p += SQG_T / 64) {
+        float m = -INFINITY;
+        for (int d = lane; d < D; d += 64) m = fmaxf(m, lg[p * DL + d]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if (lane == 0) red[p] = m;
+    }
+    __syncthreads();
+    for (int p = 0; p < SQ_PX; ++p)
+        for (int d = tid; d < DL; d += SQG_T) lg[p * DL + d] = d < D ? expf(lg[p * DL + d] - red[p]) : 0.f;
+    __syncthreads();
+    const bool chain = (tid & 31) == 0;  // one ordered chain per pixel, two per wave
+    const int cp = tid >> 5;
+    if (chain) {
+        const float4* e4 = reinterpret_cast<const float4*>(lg + cp * DL);
+        const int n4 = DL >> 2;
+        float sden = 0.f;
+        for (int i = 0; i < n4; i += 4) {  // 4 x 16 bytes per step: the LDS latency is paid once per 16 ordered adds
+            float4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = e4[min(i + j, n4 - 1)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (i + j < n4) sden += v[j].x, sden += v[j].y, sden += v[j].z, sden += v[j].w;
+        }
+        red[8 + cp] = sden;
+    }
+    __syncthreads();
+    for (int p = 0; p < SQ_PX; ++p)
+        for (int d = tid; d < D; d += SQG_T) lg[p * DL + d] = (float)d * (lg[p * DL + d] / red[8 + p]);  // disp * softmax: a product, then summed
+    __syncthreads();
+    const int nb = D >> 4;
+    {  // sums of the blocks of 16 consecutive terms, each in order (thread = pixel x block); a block's sum replaces its first term
+        const int p = tid >> 5;
+        for (int blk = tid & 31; blk < nb; blk += 32) {
+            const float4* t4 = reinterpret_cast<const float4*>(lg + p * DL + 16 * blk);
+            float4 x[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] = t4[j];
+            float bs = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bs += x[j].x, bs += x[j].y, bs += x[j].z, bs += x[j].w;
+            lg[p * DL + 16 * blk] = bs;
+        }
+    }
+    __syncthreads();
+    if (chain && w0 + cp < W) {  // the levels of ATen's cascade: block sums in order, every 16 into the next level; tail rows last
+        float lvl1 = 0.f, lvl2 = 0.f, lvl3 = 0.f, tail = 0.f;
+        for (int blk = 0; blk < nb; ++blk) {
+            lvl1 += lg[cp * DL + 16 * blk];
+            if (((blk + 1) & 15) == 0) {
+                lvl2 += lvl1;
+                lvl1 = 0.f;
+                if (((blk + 1) & 255) == 0) {
+                    lvl3 += lvl2;
+                    lvl2 = 0.f;
+                }
+            }
+        }
+        for (int d = nb * 16; d < D; ++d) tail += lg[cp * DL + d];
+        out[((long)b * H + h) * W + w0 + cp] = -(((tail + lvl1) + lvl2) + lvl3);
+    }
+}
+
+// which kernel nnd_igev_init_disparity runs for a shape inside the first two kernels' limits (G <= SQ_MAXG, D <= 512)
+static inline bool squeeze_takes_walk(int B, int H, int W, int D) {
+    return D <= 256 && (D & 3) == 0 && !switches().igev_squeeze_v1 &&
+           ((long)cdiv(W, SQ_PX) * cdiv(H, 8) * B >= 384 || switches().igev_squeeze_walk);
+}
+
 extern "C" {
 int nnd_softargmin_disparity(const float* logits, float* out, int B, int D, int H, int W, void* stream) {
     NND_REQUIRE(logits && out && B > 0 && D > 0 && H > 0 && W > 0, "softargmin_disparity: bad argument");
@@ -1943,8 +2155,7 @@ int nnd_igev_init_disparity(const float* geo_level0, const float* weight, const 
     // the walking kernel, bands of 8 rows, when those fill the chip (2 workgroups of 512 per CU); smaller problems: measured slower
     // than the one-row kernel (68x120x120: 68 vs 54 us with bands of 2 rows), which also takes D > 256 and D % 4 != 0
     // (NND_IGEV_SQUEEZE_WALK: whenever it can run — the tests' small shapes)
-    if (D <= 256 && (D & 3) == 0 && !switches().igev_squeeze_v1 &&
-        ((long)cdiv(W, SQ_PX) * cdiv(H, 8) * B >= 384 || switches().igev_squeeze_walk)) {
+    if (squeeze_takes_walk(B, H, W, D)) {
         const int R = 8;
         const long nwg = (long)cdiv(W, SQ_PX) * cdiv(H, R) * B;
         NND_REQUIRE(nwg < (1L << 30), "igev_init_disparity: grid too large");
@@ -1962,6 +2173,39 @@ int nnd_igev_init_disparity(const float* geo_level0, const float* weight, const 
         hipLaunchKernelGGL(igev_squeeze_softargmin_kernel<1>, grid, block, lds, (hipStream_t)stream, geo_level0, out, a, G, H, W, D);
     else
         hipLaunchKernelGGL(igev_squeeze_softargmin_kernel<2>, grid, block, lds, (hipStream_t)stream, geo_level0, out, a, G, H, W, D);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+int nnd_igev_init_disparity_supported(int G, int D) { return G >= 1 && G <= SQG_MAXG && D >= 1 && D <= SQG_MAXD; }
+
+int nnd_igev_init_disparity_chunk(void) { return SQG_C; }
+
+const char* nnd_igev_init_disparity_kernel(int B, int G, int H, int W, int D) {
+    if (B <= 0 || H <= 0 || W <= 0 || !nnd_igev_init_disparity_supported(G, D)) return nullptr;
+    if (G > SQ_MAXG || D > 512) return "igev_squeeze_general_kernel";
+    return squeeze_takes_walk(B, H, W, D) ? "igev_squeeze_walk_kernel" : "igev_squeeze_softargmin_kernel";
+}
+
+int nnd_igev_init_disparity_dev(const float* geo_level0, const float* weight_dev, const float* bias_dev, float* out, int B, int G,
+                                int H, int W, int D, void* stream) {
+    NND_REQUIRE(geo_level0 && weight_dev && out, "igev_init_disparity_dev: null pointer");
+    NND_REQUIRE(B > 0 && G > 0 && H > 0 && W > 0 && D > 0, "igev_init_disparity_dev: bad shape (B, G, H, W, D >= 1)");
+    if (!nnd_igev_init_disparity_supported(G, D)) {
+        set_error("igev_init_disparity_dev: groups %d (max %d) / candidates %d (max %d) not built", G, SQG_MAXG, D, SQG_MAXD);
+        return NND_ERR_UNSUPPORTED;
+    }
+    NND_REQUIRE(B <= 65535, "igev_init_disparity_dev: batch %d exceeds the grid's z extent (max 65535)", B);
+    const long nwg = (long)cdiv(W, SQ_PX) * 8 * cdiv(H, 8);
+    NND_REQUIRE(nwg < (1L << 31), "igev_init_disparity_dev: grid of %ld workgroups per sample too large (max 2^31 - 1)", nwg);
+    NND_REQUIRE(((long)W + SQ_PX + 2) * D < (1L << 31),
+                "igev_init_disparity_dev: a row of %d pixels x %d candidates overflows the 32-bit offsets inside an image row", W, D);
+    const size_t lds = sqg_lds_bytes(G, D);
+    static std::atomic<unsigned> raised;
+    if (lds > 64 * 1024)
+        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(igev_squeeze_general_kernel), raised)) return rc;
+    hipLaunchKernelGGL(igev_squeeze_general_kernel, dim3((unsigned)nwg, 1, B), dim3(SQG_T), lds, (hipStream_t)stream, geo_level0,
+                       weight_dev, bias_dev, out, G, H, W, D, sqg_logit_stride(D));
     NND_LAUNCH_CHECK();
     return NND_OK;
 }

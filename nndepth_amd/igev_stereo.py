@@ -11,6 +11,7 @@ two hooks for subclasses (`_init_fnet`, `_init_cost_volume_filter`, `forward_fne
                                                     depth-major volumes, trilinear x2 and feature gating kernels
                                                     (`CostVolumeFilterNetwork` below; `.hip = False` keeps PyTorch ops)
     cv_squeezer Conv3d + soft-argmin init           HIP  nnd_igev_init_disparity (one pass over the volume) model.py:144-146
+                                                    (nnd_igev_init_disparity_dev beyond 8 groups / 512 candidates, up to 64 / 4096)
     for iters: combined lookup -> update block -> coords += delta -> convex upsample (absolute coords, Q5)
                                                     HIP, ONE C-ABI call: nnd_igev_stereo_refine          model.py:152-158
 
@@ -227,12 +228,16 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
         geo0 = corr.geo_level0 if hasattr(corr, "geo_level0") else corr.geo_aware_cv[0]  # model.py:144
         if ops.igev_init_disparity_supported(self.cv_groups, W2):
             # cv_squeezer + softmax + regress_disparity as one kernel over the volume where it lies
-            init = ops.igev_init_disparity(geo0, *self._squeezer_host(), B, self.cv_groups, H1, W1, W2)
+            # (up to 8 groups and 512 candidates the weights travel as kernel arguments: the cached host copy; beyond, the
+            # chunked kernel reads the module's parameters where they lie on the device)
+            sq = self.cv_squeezer
+            params = self._squeezer_host() if ops.igev_init_disparity_host_params(self.cv_groups, W2) else (sq.weight, sq.bias)
+            init = ops.igev_init_disparity(geo0, *params, B, self.cv_groups, H1, W1, W2)
         else:
-            # shapes the fused kernel is not built for (more than 8 groups or 512 candidates): the squeezer runs as a
+            # shapes the fused kernels are not built for (more than 64 groups or 4096 candidates): the squeezer runs as a
             # PyTorch-ROCm Conv3d, the soft-argmin in HIP — said once, never silently
             warnings.warn(f"IGEVStereoBase: cv_groups={self.cv_groups} / {W2} candidates are outside the fused squeezer + "
-                          "soft-argmin kernel (<= 8 groups, <= 512 candidates); the squeezer Conv3d runs on PyTorch-ROCm",
+                          "soft-argmin kernels (<= 64 groups, <= 4096 candidates); the squeezer Conv3d runs on PyTorch-ROCm",
                           RuntimeWarning, stacklevel=2)
             logits = self.cv_squeezer(geo0.reshape(B, self.cv_groups, H1, W1, W2).permute(0, 1, 4, 2, 3)).squeeze(1)
             init = ops.softargmin_disparity(logits.float())

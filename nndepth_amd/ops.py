@@ -336,6 +336,22 @@ def resize_bilinear_ac(x: torch.Tensor, size: Tuple[int, int], mul: float = 1.0)
     return y
 
 
+def resize_nearest_scaled(x: torch.Tensor, size: Tuple[int, int], mul: float = 1.0) -> torch.Tensor:
+    """mul * F.interpolate(x, size) (nearest) of a stack of single-channel maps (..., 1, h, w) -> (..., 1, H, W), integer ratios in
+    both axes (raft_stereo/model.py:309-314: the Coarse2Fine stage outputs at frame size); bit-identical to the PyTorch expression."""
+    d = _dev(x)
+    x = x.contiguous()
+    if x.dim() < 3 or x.shape[-3] != 1:
+        raise NndError(f"resize_nearest_scaled: single-channel maps (..., 1, h, w) expected, got {tuple(x.shape)}")
+    h, w = x.shape[-2:]
+    H, W = int(size[0]), int(size[1])
+    y = torch.empty(tuple(x.shape[:-2]) + (H, W), dtype=torch.float32, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_resize_nearest_scaled(_p(x), _p(y), x.numel() // (h * w), h, w, H, W, float(mul), _stream(d)),
+              "resize_nearest_scaled")
+    return y
+
+
 def mask_upsample(conv: "Conv2d", x: torch.Tensor, flow: torch.Tensor, rate: int) -> torch.Tensor:
     """convex_upsample(flow, 0.25 * conv1x1(x)) in one kernel; `conv` = Conv2d packed from mask.2's (9r^2,Cin,1,1)."""
     d = _dev(x, flow, conv.packed)
@@ -1640,13 +1656,50 @@ def softargmin_disparity(logits: torch.Tensor) -> torch.Tensor:
 
 
 def igev_init_disparity_supported(num_groups: int, D: int) -> bool:
-    return num_groups <= 8 and D <= 512
+    """Whether igev_init_disparity serves `num_groups` groups and D candidates: the library's own answer
+    (nnd_igev_init_disparity_supported: up to 64 groups, up to 4096 candidates)."""
+    return bool(lib.nnd_igev_init_disparity_supported(int(num_groups), int(D)))
+
+
+def igev_init_disparity_kernel(B: int, G: int, H: int, W: int, D: int) -> Optional[str]:
+    """Name of the kernel igev_init_disparity runs for the shape (under the current NND_IGEV_SQUEEZE_* switches); None: unsupported."""
+    name = lib.nnd_igev_init_disparity_kernel(B, G, H, W, D)
+    return None if name is None else name.decode()
+
+
+def igev_init_disparity_host_params(G: int, D: int) -> bool:
+    """Whether igev_init_disparity wants the squeezer's parameters as HOST tensors for this shape (the kernels that take them as
+    kernel arguments) rather than where they lie on the device (the chunked kernel): the library's dispatch, asked by name."""
+    return igev_init_disparity_kernel(1, G, 1, 1, D) not in (None, "igev_squeeze_general_kernel")
+
+
+def _on_device(t: Optional[torch.Tensor], d: torch.device) -> Optional[torch.Tensor]:
+    """fp32 contiguous on device `d`: the tensor itself when it already is (a model's parameter: no copy, no synchronisation)."""
+    return None if t is None else t.detach().to(d, torch.float32).contiguous()
+
+
+def igev_init_disparity_general(geo_level0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, G: int, H: int,
+                                W: int, D: int) -> torch.Tensor:
+    """igev_init_disparity through nnd_igev_init_disparity_dev, the chunked kernel, at ANY supported shape: weight / bias are read
+    where they lie on the device (no host copy, no synchronisation: the call captures into a HIP graph)."""
+    d = _dev(geo_level0)
+    assert geo_level0.numel() == B * G * H * W * D and tuple(weight.shape) == (1, G, 3, 3, 3)
+    wd, bd = _on_device(weight, d), _on_device(bias, d)
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=d)
+    with torch.cuda.device(d):
+        check(lib.nnd_igev_init_disparity_dev(_p(geo_level0.contiguous()), _p(wd), _p(bd), _p(out), B, G, H, W, D, _stream(d)),
+              "igev_init_disparity_dev")
+    return out
 
 
 def igev_init_disparity(geo_level0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, G: int, H: int,
                         W: int, D: int) -> torch.Tensor:
     """cv_squeezer Conv3d(G,1,3,1,1) + soft-argmin in one kernel (igev_stereo/model.py:144-146): geo_level0 = rows
-    (b,g,h,w1) of D candidates on the device, weight (1,G,3,3,3) / bias (1) = the squeezer's parameters -> (B,1,H,W)."""
+    (b,g,h,w1) of D candidates on the device, weight (1,G,3,3,3) / bias (1) = the squeezer's parameters -> (B,1,H,W).
+    G <= 8 and D <= 512: the kernels that take the weights as kernel arguments (host tensors wanted); any other shape up to 64
+    groups / 4096 candidates: igev_init_disparity_general (device tensors wanted)."""
+    if not igev_init_disparity_host_params(G, D):
+        return igev_init_disparity_general(geo_level0, weight, bias, B, G, H, W, D)
     d = _dev(geo_level0)
     assert geo_level0.numel() == B * G * H * W * D and tuple(weight.shape) == (1, G, 3, 3, 3)
     # 27*G floats passed by value to the kernel: hand in host tensors (a device tensor costs a synchronising copy here)

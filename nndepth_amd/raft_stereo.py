@@ -20,6 +20,7 @@ The classes are inference-only (eval-mode BatchNorm is folded into the convoluti
 `patch(model)` installs the same kernels behind the three duck-typed seams of an *unmodified*
 reference model instance: `corr_fn`, `update_block`, `convex_upsample`.
 """
+import os
 from typing import Dict, List, Optional
 
 import torch
@@ -215,6 +216,23 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
         return outs
 
 
+def frame_size_outputs(ups, frame_hw, stacked=None):
+    """A stage's upsampled maps at frame size, scaled by the width ratio (model.py:309-314: F.interpolate(u, size=frame) * rate).
+    An integer ratio in both axes — every frame the cascade accepts — is ONE HIP launch for `stacked`, the fused loop's
+    (n, B, 1, h, w) tensor whose slices `ups` are (ops.resize_nearest_scaled, bit-identical to the PyTorch expression), or one
+    launch per map without it.  NND_C2F_TORCH_RESIZE=1 (diagnostic, read per call) selects the PyTorch expression."""
+    h, w = ups[0].shape[-2:]
+    rate = frame_hw[1] / w
+    if rate == 1:
+        return list(ups)
+    if frame_hw[0] % h or frame_hw[1] % w or os.environ.get("NND_C2F_TORCH_RESIZE", "0") not in ("", "0"):
+        return [nn.functional.interpolate(u, size=frame_hw) * rate for u in ups]
+    if stacked is None:  # the seam-by-seam loop: one launch per map
+        return [ops.resize_nearest_scaled(u, frame_hw, rate) for u in ups]
+    big = ops.resize_nearest_scaled(stacked, frame_hw, rate)
+    return [big[i] for i in range(big.shape[0])]
+
+
 class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
     """The hot path of `Coarse2FineGroupRepViTRAFTStereo` (nndepth/models/raft_stereo/model.py:166-320) on HIP: per cascade stage the
     group correlation pyramid (GroupCorrBlock1D, quirks Q4 / Q6 kept), the ConvGRU update block (`gru="conv_gru"`, spatial scale
@@ -306,11 +324,11 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
                 eng = self.update_block.sync_engine(fmap1.device)
                 up, _, _ = eng.refine_group(corr._pyr, self.num_groups, self.corr_levels, self.corr_radius, net, inp, 4, self.iters,
                                             disp_init=up_last, keep_all=not last, last_only=last)
-                ups = [up[i] for i in range(up.shape[0])]
+                ups, stacked = [up[i] for i in range(up.shape[0])], up
             else:  # seam-by-seam loop (same shape as the reference's), every step still a HIP kernel
                 org = self.initialize_coords(fmap1)
                 coords1 = org if up_last is None else org + up_last
-                ups = []
+                ups, stacked = [], None
                 for i in range(self.iters):
                     sampled = corr(coords1)
                     net, mask, delta = self.update_block(net, inp, sampled, coords1 - org)
@@ -318,9 +336,7 @@ class Coarse2FineRAFTStereoBase(AutoCalibrate, nn.Module):
                     if not last or i == self.iters - 1:
                         ups.append(self.convex_upsample(coords1 - org, mask, rate=(4, 4)))
             if not last or idx == len(feats) - 1:
-                for u in ups:
-                    rate = frame_hw[1] / u.shape[-1]
-                    outs.append({"up_disp": u if rate == 1 else nn.functional.interpolate(u, size=tuple(frame_hw)) * rate})
+                outs.extend({"up_disp": u} for u in frame_size_outputs(ups, tuple(frame_hw), stacked))
             up_last = ups[-1]
         return outs
 
