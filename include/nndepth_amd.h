@@ -214,8 +214,12 @@ int nnd_convex_upsample(const float* flow, const float* mask, float* out,
  *     |x| < 32 * M, inf / NaN in the output beyond — at every output that reads the activation, through the ReLU / sigmoid /
  *     tanh epilogues and the layers behind them (nnd_update_block_forward: and at no output outside the reach of its convs);
  *   - nnd_update_block_scale_slots gives the float offsets of the layers' slots in the blob: slot[1] = 2^xs, so the valid range
- *     of layer i is |x| < 65504 / slot[1] (the Python engines expose it as `activation_ranges()`).
- * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once).
+ *     of layer i is |x| < 65504 / slot[1] (the Python engines expose it as `activation_ranges()`); nnd_encoder_scale_slots,
+ *     nnd_conv3d_scale_slots and nnd_conv2d_scale_slots_ex do the same for the other engines;
+ *   - nnd_scales_read / nnd_scales_write move the exponents xs out of and into a blob (set, or widen = per-layer minimum), in
+ *     place: a calibration is data — {layer name: xs}, independent of the weights' own scale s — that can be saved, loaded into
+ *     another process, merged over ranks and widened; nnd_nonfinite_flag reports an exceeded range from the output.
+ * The model classes of nndepth_amd calibrate on their first forward (one extra forward, once) unless a saved state was loaded.
  * arithmetic = 1 ("fp16", one piece) has the same scales, slots, calibration and range behaviour — finite up to 32 * M, inf / NaN
  * beyond, never a finite wrong value — with the precision of ONE piece: 11 significand bits per operand while |x| >= M * 2^-25
  * (an fp16 subnormal below: absolute error <= M * 2^-36).                                                                      */
@@ -321,6 +325,29 @@ int nnd_conv2d_forward_ex(const float* packed_dev, const float* x, float* y, int
  * largest |x| of this input (see "fp16x2 activation range").  status_dev as nnd_update_block_calibration_finish.          */
 int nnd_conv2d_calibrate_ex(float* packed_dev, const float* x, int B, int Cin, int H, int W, int Cout, int KH, int KW,
                             int arithmetic, int32_t* status_dev, void* stream);
+/* HOST: the one scale slot of such a blob (-1 unless arithmetic is 2 or 1); contract as nnd_encoder_scale_slots, returns 1. */
+int nnd_conv2d_scale_slots_ex(int Cout, int Cin, int KH, int KW, int arithmetic, int64_t* offsets, int n);
+
+/* Activation scales as data (see "fp16x2 activation range"): the exponent xs of a layer's scale 2^xs read from and written to the
+ * slots that nnd_*_scale_slots enumerate, so that a calibration can be saved, loaded into another process or rank, merged and
+ * widened.  `offsets`: a HOST array of n slot offsets (1 <= n <= 64, each >= 0), `xs_dev` n device int32.  One tiny kernel on
+ * `stream` each, no synchronisation.
+ *   nnd_scales_read   xs_dev[i] = xs of slot i; amax_dev (may be NULL) receives the slot's pending calibration record — the largest
+ *                     |activation| staged under NND_FLAG_CALIBRATE since the last finish, 0 if none — which clear_records != 0 then
+ *                     clears: a forward under the flag followed by this call instead of nnd_*_calibration_finish measures what
+ *                     each layer sees and changes no scale.
+ *   nnd_scales_write  mode 0: xs = xs_dev[i]; mode 1: xs = min(current, xs_dev[i]) — the range only grows (each step down doubles the
+ *                     largest representable |x| and moves the 13-octave full-precision window up with it).  xs is clamped to
+ *                     |xs| <= 60 like a calibration's, and the slot's 2^xs and 2^-(s+xs) are rewritten IN PLACE: the blob is not
+ *                     reallocated, so a captured graph that reads it runs with the new scales on its next replay.  A slot listed
+ *                     twice is refused.  Must not overlap inference on the same blob from another stream (the kernels read the
+ *                     two values separately).  Records are not touched.
+ * nnd_nonfinite_flag: *word_dev |= 1 if any of the n floats of x is inf or NaN (n >= 1).  An exceeded range always reaches the
+ * output as inf / NaN, so this over a model's final output detects it without a host synchronisation.                       */
+int nnd_scales_read(float* packed_dev, const int64_t* offsets, int n, int32_t* xs_dev, float* amax_dev, int clear_records,
+                    void* stream);
+int nnd_scales_write(float* packed_dev, const int64_t* offsets, int n, const int32_t* xs_dev, int mode, void* stream);
+int nnd_nonfinite_flag(const float* x, int64_t n, int32_t* word_dev, void* stream);
 
 /* conv + CREStereo's search-offset activation in the epilogue: y = range * (sigmoid(conv(x)) - 0.5) * 2
  *   nndepth/models/cre_stereo/model.py:158-159,171-172 (conv_offset_16 / conv_offset_8); blob of nnd_conv2d_pack.      */
@@ -412,6 +439,13 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed_dev, 
                          float* fmap, float* cnet_out, int n_cnet, float* workspace, int N, int H, int W, void* stream);
 /* fp16x2 calibration of the encoder's layers after forwards with NND_FLAG_CALIBRATE (as nnd_update_block_calibration_finish) */
 int nnd_encoder_calibration_finish(const nnd_encoder_desc* desc, float* packed_dev, int32_t* status_dev, void* stream);
+/* HOST (no GPU): float offsets inside the blob of the layers' 4-float scale slots (see nnd_update_block_scale_slots), one entry per
+ * convolution in nnd_encoder_pack's order, -1 where a convolution is not range-scaled (the stem, conv2, the stand-in shortcuts of
+ * the stride-1 blocks; every one under arithmetic 0 / 3).  Returns the number of convolutions; offsets == NULL sizes the array,
+ * n smaller than that number is refused.  nnd_encoder_scale_name: the reference's key of convolution `which` — "conv1",
+ * "layer1.0.conv1", "layer1.0.conv2", "layer1.0.downsample.0", ..., "conv2", "cnet_proj" — or "" beyond.                  */
+int nnd_encoder_scale_slots(const nnd_encoder_desc* desc, int64_t* offsets, int n);
+const char* nnd_encoder_scale_name(const nnd_encoder_desc* desc, int which);
 
 /* ------------------------------------------------------------------------- RepViT encoder side (Coarse2Fine)
  * Replaces the encoder side of Coarse2FineGroupRepViTRAFTStereo.forward  nndepth/models/raft_stereo/model.py:275-288: RepViT.forward
@@ -778,6 +812,13 @@ int nnd_conv3d_forward(const nnd_conv3d_desc* desc, const float* packed_dev, con
                        int N, int D, int H, int W, float leaky_slope, void* stream);
 /* fp16x2 calibration of the layer after forwards with NND_FLAG_CALIBRATE (as nnd_update_block_calibration_finish) */
 int nnd_conv3d_calibration_finish(const nnd_conv3d_desc* desc, float* packed_dev, int32_t* status_dev, void* stream);
+/* HOST: the slots of the formulations the blob packs, always 3 entries in the order nnd_conv3d_scale_name(0..2) names them — "plain"
+ * (one output slice per launch element), "grouped" (J slices; thin stride-1 layers), "slab" (depth-marching kernel) — with -1 for a
+ * formulation this shape does not pack or that is not fp16x2.  They all stage the layer's input: ONE activation range, which
+ * nnd_scales_write should give to every one of them (the forward picks the formulation from the depth).  Contract as
+ * nnd_encoder_scale_slots.                                                                                                    */
+int nnd_conv3d_scale_slots(const nnd_conv3d_desc* desc, int64_t* offsets, int n);
+const char* nnd_conv3d_scale_name(int which);
 int nnd_volume_to_depth_major(const float* x, float* y, int N, int C, int D, int H, int W, void* stream);
 int nnd_depth_major_to_volume(const float* x, float* y, int N, int C, int D, int H, int W, void* stream);
 /* the same for a volume stored (N, C, H, W, D), candidate axis contiguous — level 0 of the IGEV pyramids, rows

@@ -117,6 +117,14 @@ SIGNATURES = {
     "nnd_update_block_calibration_finish": (_I, [C.POINTER(UpdateBlockDesc), _P, _P, _P]),
     "nnd_update_block_scale_slots": (_I, [C.POINTER(UpdateBlockDesc), C.POINTER(C.c_int64), _I]),
     "nnd_conv2d_calibrate_ex": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "nnd_conv2d_scale_slots_ex": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int64), _I]),
+    "nnd_encoder_scale_slots": (_I, [C.POINTER(EncoderDesc), C.POINTER(C.c_int64), _I]),
+    "nnd_encoder_scale_name": (C.c_char_p, [C.POINTER(EncoderDesc), _I]),
+    "nnd_conv3d_scale_slots": (_I, [C.POINTER(Conv3dDesc), C.POINTER(C.c_int64), _I]),
+    "nnd_conv3d_scale_name": (C.c_char_p, [_I]),
+    "nnd_scales_read": (_I, [_P, C.POINTER(C.c_int64), _I, _P, _P, _I, _P]),
+    "nnd_scales_write": (_I, [_P, C.POINTER(C.c_int64), _I, _P, _I, _P]),
+    "nnd_nonfinite_flag": (_I, [_P, C.c_int64, _P, _P]),
     "nnd_encoder_forward2": (_I, [C.POINTER(EncoderDesc), _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
     "nnd_pos_enc_sine_add": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "nnd_encoder_calibration_finish": (_I, [C.POINTER(EncoderDesc), _P, _P, _P]),

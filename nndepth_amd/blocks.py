@@ -58,6 +58,10 @@ class BasicUpdateBlock(nn.Module):
         """(Re)pack the parameters for the HIP kernels if they changed since the last call."""
         return self._packed.get((self,), device, lambda: self.engine.load(self.state_dict(), device=device))
 
+    def calibration_site(self) -> ops.ScaleSite:
+        """The block's engine for a model's calibration state (raft_stereo.calibration_state)."""
+        return ops.ScaleSite(self.engine.scale_names(), lambda: self.engine if self.engine.packed is not None else None, self._packed)
+
     @torch.no_grad()
     def forward(self, net: torch.Tensor, inp: torch.Tensor, corr: torch.Tensor, flow: torch.Tensor):
         eng = self.sync_engine(net.device)

@@ -158,6 +158,13 @@ class CREStereoBase(AutoCalibrate, nn.Module):
             return fmaps[:B], fmaps[B:]
         return self.fnet([frame1, frame2])  # explicit opt-in (hip_encoder=False): PyTorch-ROCm modules
 
+    def _calibration_sites(self):
+        sites = {}
+        if self.hip_encoder and hip_encoder_blocker(self.fnet, ("instance", "batch", "none")) is None:
+            sites["fnet"] = self._encoder_site(self._enc_cache, self.fnet.conv2.out_channels, 0)
+        sites.update(super()._calibration_sites())
+        return sites
+
     def _offset_convs(self, device):
         """conv_offset_16 / conv_offset_8 packed for the MFMA conv (repacked when their parameters change)."""
         mods = (self.conv_offset_16, self.conv_offset_8)

@@ -111,6 +111,58 @@ __global__ void calib_finish_kernel(float* blob, CalibOffs offs, int n, int* sta
 
 unsigned* amax_slot(const float* tail) { return reinterpret_cast<unsigned*>(const_cast<float*>(tail)) + SPLIT_TAIL_AMAX; }
 
+// ---- scales as data (nnd_scales_read / nnd_scales_write): the exponent xs of xscale = 2^xs, per slot
+__device__ __forceinline__ int xs_of(const float* tail) {
+    int e;
+    (void)frexpf(tail[SPLIT_TAIL_XSCALE], &e);  // xscale = 2^(e - 1)
+    return e - 1;
+}
+
+// one block of CALIB_MAX_LAYERS threads, thread = slot.  Every read is done before any record is cleared (a slot may be listed twice).
+__global__ void scales_read_kernel(float* blob, CalibOffs offs, int n, int* xs, float* amax, int clear) {
+    const int i = threadIdx.x;
+    float* tail = i < n ? blob + offs.off[i] : nullptr;
+    if (tail) {
+        xs[i] = xs_of(tail);
+        if (amax) amax[i] = tail[SPLIT_TAIL_AMAX];  // the record is the bit pattern of the largest |x|: read as a float it is that value
+    }
+    __syncthreads();
+    if (tail && clear) tail[SPLIT_TAIL_AMAX] = 0.f;
+}
+
+// mode 0: xs = given; mode 1: xs = min(current, given) (the range only grows).  The clamp and the two products are calib_finish_kernel's.
+__global__ void scales_write_kernel(float* blob, CalibOffs offs, int n, const int* xs_in, int mode) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    float* tail = blob + offs.off[i];
+    int xs = xs_in[i];
+    if (mode == 1) {
+        const int cur = xs_of(tail);
+        xs = cur < xs ? cur : xs;
+    }
+    xs = xs < -60 ? -60 : (xs > 60 ? 60 : xs);
+    tail[SPLIT_TAIL_XSCALE] = ldexpf(1.f, xs);
+    tail[SPLIT_TAIL_OSCALE] = tail[SPLIT_TAIL_WSINV] * ldexpf(1.f, -xs);
+}
+
+__global__ void __launch_bounds__(256) nonfinite_flag_kernel(const float* __restrict__ x, long n, int* __restrict__ word) {
+    bool bad = false;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) bad = bad || abs_bits(x[i]) >= 0x7f800000u;
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(word, 1);  // one atomic per wave that saw one, none on finite data
+}
+
+// the slots of one nnd_scales_* call as a kernel argument; `unique`: a slot listed twice is refused (two writers)
+int scale_offs(const char* who, const void* blob, const int64_t* offsets, int n, bool unique, CalibOffs* o) {
+    NND_REQUIRE(blob && offsets, "%s: null pointer", who);
+    NND_REQUIRE(n >= 1 && n <= CALIB_MAX_LAYERS, "%s: n = %d slots (1 .. %d in one call)", who, n, CALIB_MAX_LAYERS);
+    for (int i = 0; i < n; ++i) {
+        NND_REQUIRE(offsets[i] >= 0, "%s: slot %d has offset %lld (a layer that is not range-scaled has no slot)", who, i, (long long)offsets[i]);
+        for (int j = 0; unique && j < i; ++j) NND_REQUIRE(offsets[j] != offsets[i], "%s: slots %d and %d are the same", who, j, i);
+        o->off[i] = (long)offsets[i];
+    }
+    return NND_OK;
+}
+
 }  // namespace
 
 int calib_amax_act(const Act& a, const Lay& lay, int B, int H, int W, const float* tail, hipStream_t s) {
@@ -150,3 +202,38 @@ int calib_finish(float* blob, const int64_t* tail_offs, int n, int32_t* status_d
 }
 
 }  // namespace nnd
+
+using namespace nnd;
+
+extern "C" {
+
+int nnd_scales_read(float* packed_dev, const int64_t* offsets, int n, int32_t* xs_dev, float* amax_dev, int clear_records, void* stream) {
+    CalibOffs o;
+    if (int rc = scale_offs("scales_read", packed_dev, offsets, n, false, &o)) return rc;
+    NND_REQUIRE(xs_dev, "scales_read: null xs_dev");
+    hipLaunchKernelGGL(scales_read_kernel, dim3(1), dim3(CALIB_MAX_LAYERS), 0, (hipStream_t)stream, packed_dev, o, n, (int*)xs_dev, amax_dev,
+                       clear_records ? 1 : 0);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+int nnd_scales_write(float* packed_dev, const int64_t* offsets, int n, const int32_t* xs_dev, int mode, void* stream) {
+    CalibOffs o;
+    if (int rc = scale_offs("scales_write", packed_dev, offsets, n, true, &o)) return rc;
+    NND_REQUIRE(xs_dev, "scales_write: null xs_dev");
+    NND_REQUIRE(mode == 0 || mode == 1, "scales_write: mode %d (0 = set, 1 = widen: the smaller of the current and the given exponent)", mode);
+    hipLaunchKernelGGL(scales_write_kernel, dim3(1), dim3(CALIB_MAX_LAYERS), 0, (hipStream_t)stream, packed_dev, o, n, (const int*)xs_dev, mode);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+int nnd_nonfinite_flag(const float* x, int64_t n, int32_t* word_dev, void* stream) {
+    NND_REQUIRE(x && word_dev, "nonfinite_flag: null pointer");
+    NND_REQUIRE(n >= 1, "nonfinite_flag: n = %lld elements", (long long)n);
+    const unsigned grid = (unsigned)std::min<long>(cdiv64(n, 256), 2048);
+    hipLaunchKernelGGL(nonfinite_flag_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (long)n, (int*)word_dev);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
+}  // extern "C"

@@ -340,6 +340,25 @@ int nnd_conv3d_calibration_finish(const nnd_conv3d_desc* desc, float* packed_dev
     return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
 }
 
+// the slot of every formulation the blob packs, in the order of nnd_conv3d_scale_name; -1: not packed for this shape, or not fp16x2.
+// All of them stage the same tensor, the layer's input: one activation range, held once per formulation.
+int nnd_conv3d_scale_slots(const nnd_conv3d_desc* desc, int64_t* offsets, int n) {
+    Conv3dPlan p;
+    int rc = make_conv3d_plan(desc, &p);
+    if (rc != NND_OK) return rc;
+    if (!offsets) return 3;
+    NND_REQUIRE(n >= 3, "conv3d_scale_slots: room for %d offsets, a layer has 3 formulations", n);
+    offsets[0] = p.tail1;
+    offsets[1] = p.tailJ;
+    offsets[2] = p.tail_slab;
+    return 3;
+}
+
+const char* nnd_conv3d_scale_name(int which) {
+    static const char* const kNames[3] = {"plain", "grouped", "slab"};
+    return (which >= 0 && which < 3) ? kNames[which] : "";
+}
+
 // the zero end slices of a depth-major output (N, Do+2, C, Ho*Wo)
 static int zero_end_slices(float* y, int N, int Do, int64_t slice, hipStream_t s) {
     for (int n = 0; n < N; ++n) {

@@ -640,6 +640,39 @@ int nnd_encoder_calibration_finish(const nnd_encoder_desc* desc, float* packed_d
     return calib_finish(packed_dev, offs, n, status_dev, (hipStream_t)stream);
 }
 
+// the convs in pack order (nnd_encoder_pack's units) under the reference's keys; a stride-1 block's shortcut is an identity there, its
+// packed 1x1 stands in for it and is exact fp32
+int nnd_encoder_scale_slots(const nnd_encoder_desc* desc, int64_t* offsets, int n) {
+    EncPlan p;
+    int rc = make_enc_plan(desc, &p);
+    if (rc != NND_OK) return rc;
+    if (!offsets) return p.units;
+    NND_REQUIRE(n >= p.units, "encoder_scale_slots: room for %d offsets, the descriptor has %d convolutions", n, p.units);
+    auto slot = [](const ConvLayer& L, int64_t base) { return L.range_scaled() ? base + L.tail_off() : (int64_t)-1; };
+    int k = 0;
+    offsets[k++] = -1;  // conv1: the stem is exact fp32
+    for (int i = 0; i < ENC_BLOCKS; ++i) {
+        offsets[k++] = slot(p.c1[i], p.base1[i]);
+        offsets[k++] = slot(p.c2[i], p.base2[i]);
+        offsets[k++] = slot(p.ds[i], p.based[i]);
+    }
+    offsets[k++] = slot(p.out, p.base_out);
+    if (desc->cnet_dim > 0) offsets[k++] = slot(p.cnet, p.base_cnet);
+    return p.units;
+}
+
+const char* nnd_encoder_scale_name(const nnd_encoder_desc* desc, int which) {
+    static const char* const kNames[] = {"conv1",
+                                         "layer1.0.conv1", "layer1.0.conv2", "layer1.0.downsample.0", "layer1.1.conv1", "layer1.1.conv2", "layer1.1.downsample.0",
+                                         "layer2.0.conv1", "layer2.0.conv2", "layer2.0.downsample.0", "layer2.1.conv1", "layer2.1.conv2", "layer2.1.downsample.0",
+                                         "layer3.0.conv1", "layer3.0.conv2", "layer3.0.downsample.0", "layer3.1.conv1", "layer3.1.conv2", "layer3.1.downsample.0",
+                                         "conv2", "cnet_proj"};
+    static_assert(sizeof(kNames) / sizeof(kNames[0]) == 1 + 3 * ENC_BLOCKS + 2, "one name per unit");
+    EncPlan p;
+    if (make_enc_plan(desc, &p) != NND_OK) return "";
+    return (which >= 0 && which < p.units) ? kNames[which] : "";
+}
+
 int nnd_encoder_forward(const nnd_encoder_desc* desc, const float* packed, const float* frames, float* fmap, float* cnet_out,
                         int n_cnet, float* workspace, int N, int H, int W, void* stream) {
     return nnd_encoder_forward2(desc, packed, frames, nullptr, N, fmap, cnet_out, n_cnet, workspace, N, H, W, stream);

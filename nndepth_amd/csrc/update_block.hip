@@ -1058,6 +1058,17 @@ int nnd_conv2d_calibrate_ex(float* packed_dev, const float* x, int B, int Cin, i
     return calib_finish(packed_dev, &off, 1, status_dev, (hipStream_t)stream);
 }
 
+// a single layer has one slot (-1 unless the arithmetic is range-scaled)
+int nnd_conv2d_scale_slots_ex(int Cout, int Cin, int KH, int KW, int arithmetic, int64_t* offsets, int n) {
+    ConvLayer L;
+    int rc = conv2d_layer(Cout, Cin, KH, KW, arithmetic, &L, nullptr);
+    if (rc != NND_OK) return rc;
+    if (!offsets) return 1;
+    NND_REQUIRE(n >= 1, "conv2d_scale_slots: room for %d offsets, a layer has 1 slot", n);
+    offsets[0] = L.range_scaled() ? L.tail_off() : -1;
+    return 1;
+}
+
 int nnd_conv2d_forward(const float* packed_dev, const float* x, float* y, int B, int Cin, int H, int W, int Cout, int KH,
                        int KW, int relu, void* stream) {
     return nnd_conv2d_forward_ex(packed_dev, x, y, B, Cin, H, W, Cout, KH, KW, relu, 0, stream);

@@ -124,6 +124,28 @@ class CostVolumeFilterNetwork(nn.Module):
         e["g3u"], e["g2u"] = gate(self.conv3_up_feat_guided), gate(self.conv2_up_feat_guided)
         return e
 
+    def calibration_sites(self, prefix: str):
+        """{module path: ops.ScaleSite} of the Conv3d layers under the reference's module names (raft_stereo.calibration_state): each is
+        ONE layer — all the formulations its blob packs stage the same volume."""
+        convs = {f"conv{i}.{j}": (getattr(self, f"conv{i}")[j], 2 - j, 0, (f"conv{i}", j)) for i in (1, 2, 3) for j in (0, 1)}
+        for n in ("conv3_up", "conv2_up", "conv1_up"):
+            convs[n] = (getattr(self, n), 1, 0, (n, None))
+        convs["proj_3"] = (self.proj_3, 1, self.conv3_up.conv.out_channels, ("proj_3", None))
+        convs["proj_2"] = (self.proj_2, 1, self.conv2_up.conv.out_channels, ("proj_2", None))
+        convs["final_conv"] = (self.final_conv, 1, 0, ("final", None))
+        sites = {}
+        for path, (m, stride, split, (key, idx)) in convs.items():
+            cout, cin = int(m.conv.weight.shape[0]), int(m.conv.weight.shape[1])
+            cin0 = split if split > 0 else cin
+            desc = ops.Conv3dDesc(cout, cin0, cin - cin0, stride, ops.arithmetic_id(self.arithmetic), 0)
+            names = [""] if ops.Conv3dNorm.formulations_of(desc) else []
+
+            def engine(key=key, idx=idx):
+                e = self._hip.value
+                return None if e is None else (e[key] if idx is None else e[key][idx])
+            sites[f"{prefix}.{path}"] = ops.ScaleSite(names, engine, self._hip)
+        return sites
+
     def forward_rows(self, rows: torch.Tensor, features: List[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The same network on a volume kept as the pyramids keep it, (B,G,H,W1,W2) with the candidate axis contiguous
         (`forward(x)` with x = rows.permute(0,1,4,2,3)); the result, in the same layout, optionally written into `out`.
@@ -184,6 +206,13 @@ class IGEVStereoBase(AutoCalibrate, nn.Module):
         self.tracing, self.include_preprocessing = tracing, include_preprocessing
         self.weights, self.strict_load = weights, strict_load
         self.fused_loop = fused_loop
+
+    def _calibration_sites(self):
+        sites = super()._calibration_sites()
+        reg = self.cv_regularizer
+        if getattr(reg, "hip", False) and hasattr(reg, "calibration_sites"):
+            sites.update(reg.calibration_sites("cv_regularizer"))
+        return sites
 
     def _squeezer_host(self):
         """Host copy of the cv_squeezer parameters (kernel arguments of nnd_igev_init_disparity), refreshed when they change."""

@@ -52,6 +52,7 @@ class ParamCache:
 
     def __init__(self):
         self.key, self.value = None, None
+        self.on_build: Optional[Callable[[object], None]] = None  # called with every freshly built value (a pinned calibration state)
 
     def get(self, modules: Sequence[torch.nn.Module], device, build: Callable[[], object], extra: tuple = (),
             track_modules: bool = False):
@@ -60,7 +61,13 @@ class ParamCache:
                      if t is not None),
                tuple(map(id, mods)) if track_modules else (), str(device), extra)
         if key != self.key:
-            self.value = build()
+            old, self.value = self.value, build()
+            if self.on_build is not None:
+                try:
+                    self.on_build(self.value)
+                except Exception:
+                    self.value = old
+                    raise
             self.key = key
         return self.value
 
@@ -137,7 +144,10 @@ def require_calibrated():
 
 
 @contextlib.contextmanager
-def calibration():
+def calibration(finish: bool = True):
+    """finish=False: the engines record under NND_FLAG_CALIBRATE but no scale is set when the block is left — the records stay
+    pending in the blobs for the caller to read AND clear (`read_records`, as the model classes' `range_report` does; a single
+    ops.Conv2d has no such mode, it calibrates on the spot)."""
     if getattr(_calib_tls, "active", None) is not None:
         raise NndError("calibration(): already active on this thread")
     c = _Calibration()
@@ -146,6 +156,8 @@ def calibration():
         yield c
     finally:
         _calib_tls.active = None
+    if not finish:
+        return
     for e in c.engines:
         d = e.packed.device
         if c._status is None:
@@ -153,6 +165,106 @@ def calibration():
         with torch.cuda.device(d):
             e._calibration_finish(c._status)
         e.calibrated = True
+
+
+# ---- activation scales as data (include/nndepth_amd.h: nnd_*_scale_slots, nnd_scales_read / nnd_scales_write)
+def _enumerate_slots(call: Callable, what: str) -> List[int]:
+    """The offsets of one nnd_*_scale_slots function, `call(offsets, n)`: sized with offsets = NULL, then filled.  Host work."""
+    n = int(call(None, 0))
+    if n < 0:
+        check(n, what)
+    offs = (C.c_int64 * n)()
+    rc = int(call(offs, n))
+    if rc < 0:
+        check(rc, what)
+    return list(offs)
+
+
+def scales_read(packed: torch.Tensor, offsets: Sequence[int], records: bool = False, clear: bool = False):
+    """(xs int32, records float32 or None) on packed's device for the slots at `offsets`: one launch, no synchronisation."""
+    d = packed.device
+    xs = torch.empty(len(offsets), dtype=torch.int32, device=d)
+    rec = torch.empty(len(offsets), dtype=torch.float32, device=d) if records else None
+    if offsets:
+        with torch.cuda.device(d):
+            check(lib.nnd_scales_read(_p(packed), (C.c_int64 * len(offsets))(*offsets), len(offsets), _p(xs), _p(rec), int(clear), _stream(d)),
+                  "scales_read")
+    return xs, rec
+
+
+def scales_write(packed: torch.Tensor, offsets: Sequence[int], xs, widen: bool = False) -> None:
+    """xs (ints, or an integer tensor anywhere) into the slots at `offsets`, in place; widen: the smaller of the current and the given."""
+    d = packed.device
+    xs = torch.as_tensor(xs).to(device=d, dtype=torch.int32).reshape(-1).contiguous()
+    if xs.numel() != len(offsets):
+        raise NndError(f"scales_write: {xs.numel()} exponents for {len(offsets)} layers")
+    if offsets:
+        with torch.cuda.device(d):
+            check(lib.nnd_scales_write(_p(packed), (C.c_int64 * len(offsets))(*offsets), len(offsets), _p(xs), int(bool(widen)), _stream(d)),
+                  "scales_write")
+
+
+def nonfinite_flag(x: torch.Tensor, word: torch.Tensor) -> None:
+    """word (1 device int32) |= 1 if x holds an inf or a NaN: one launch, no synchronisation."""
+    d = _dev(x)
+    if word.device != d or word.dtype != torch.int32 or word.numel() < 1:
+        raise NndError(f"nonfinite_flag: the word must be a torch.int32 tensor on {d}")
+    x = x.contiguous()
+    if x.numel():
+        with torch.cuda.device(d):
+            check(lib.nnd_nonfinite_flag(_p(x), x.numel(), _p(word), _stream(d)), "nonfinite_flag")
+
+
+class ScaleSlots:
+    """What the four range-scaled engines share: their layers' activation scales as data.  `_scale_slots()` (host work, from the
+    descriptor alone) lists (layer name, slot offset) of the layers that have a scale — none under "fp32" / "bf16x3"."""
+
+    def _scale_slots(self) -> List[Tuple[str, int]]:
+        raise NotImplementedError
+
+    def _slots(self) -> List[Tuple[str, int]]:
+        if self.__dict__.get("_slot_list") is None:
+            self._slot_list = self._scale_slots()
+        return self._slot_list
+
+    def on_device(self) -> bool:
+        """Packed, and on a HIP device (a blob packed on the host has its default scales and nothing to launch on)."""
+        return self.packed is not None and self.packed.device.type == "cuda"
+
+    def _blob(self) -> torch.Tensor:
+        if not self.on_device():
+            raise NndError(f"{type(self).__name__}: parameters not packed on a HIP device, there are no scales to read or write")
+        return self.packed
+
+    def scale_names(self) -> List[str]:
+        """The layers that carry an activation scale, by name, in the order of read_scales / write_scales (no GPU needed)."""
+        return [n for n, _ in self._slots()]
+
+    def read_scales(self) -> torch.Tensor:
+        """int32 device tensor, one exponent xs per scale_names() entry (the layer stages x * 2^xs).  No synchronisation."""
+        return scales_read(self._blob(), [o for _, o in self._slots()])[0]
+
+    def read_records(self, clear: bool = True) -> torch.Tensor:
+        """float32 device tensor: the largest |activation| each layer staged under NND_FLAG_CALIBRATE since the last finish (0: none)."""
+        return scales_read(self._blob(), [o for _, o in self._slots()], records=True, clear=clear)[1]
+
+    def write_scales(self, xs, widen: bool = False) -> None:
+        """Sets the exponents, in scale_names() order, in place (a captured graph picks them up on its next replay); widen=True
+        keeps the smaller of the current and the given one per layer.  Must not overlap a forward of this engine on another stream."""
+        scales_write(self._blob(), [o for _, o in self._slots()], xs, widen)
+        self.calibrated = True
+
+    def widen_scales(self, before: torch.Tensor) -> None:
+        """After a new calibration: per layer the smaller of the new exponent and `before` (read_scales() taken ahead of it)."""
+        self.write_scales(before, widen=True)
+
+
+class ScaleSite(NamedTuple):
+    """One engine of a model, as the model classes' calibration state sees it: its layer names (host work: known before anything is
+    packed), the packed engine (None until then) and the ParamCache that repacks it."""
+    names: List[str]
+    engine: Callable[[], Optional[ScaleSlots]]
+    cache: ParamCache
 
 
 # ---------------------------------------------------------------------------- correlation
@@ -205,11 +317,17 @@ def convex_upsample(flow: torch.Tensor, mask: torch.Tensor, rate: int) -> torch.
 
 
 # ------------------------------------------------------------------------ generic conv2d
-class Conv2d:
+class Conv2d(ScaleSlots):
     """One packed stride-1 "same" convolution (1x1, 3x3, 1x5, 5x1): arithmetic "fp32" = the exact fp32-MFMA kernel,
     "bf16x3" = fp32 operands as 3 bf16 pieces on the bf16 MFMA (csrc/conv_split.hip, Cin % 16 == 0), "fp16x2" = as 2 range-scaled
     fp16 pieces, "fp16" = as ONE range-scaled fp16 piece: 11 significand bits per operand (not fp32 parity), finite up to 32 x the
-    calibrated maximum |x| and inf / NaN beyond."""
+    calibrated maximum |x| and inf / NaN beyond.  Its one activation scale is the layer "" of scale_names()."""
+
+    def _scale_slots(self) -> List[Tuple[str, int]]:
+        offs = _enumerate_slots(lambda o, n: lib.nnd_conv2d_scale_slots_ex(self.Cout, self.Cin, self.KH, self.KW, self.arith, o, n),
+                                "conv2d_scale_slots")
+        return [("", o) for o in offs if o >= 0]
+
 
     def __init__(self, weight: torch.Tensor, bias: torch.Tensor, device="cuda", arithmetic: str = "fp32"):
         self.Cout, self.Cin, self.KH, self.KW = (int(s) for s in weight.shape)
@@ -392,8 +510,17 @@ class _RefineCall(NamedTuple):
     W: int
 
 
-class UpdateBlockEngine:
+class UpdateBlockEngine(ScaleSlots):
     """Packed parameters + workspace for one BasicUpdateBlock configuration."""
+
+    def _scale_slots(self) -> List[Tuple[str, int]]:
+        offs = _enumerate_slots(lambda o, n: lib.nnd_update_block_scale_slots(C.byref(self.desc), o, n), "update_block_scale_slots")
+        out, seen = [], set()
+        for i, o in enumerate(offs):
+            if o >= 0 and o not in seen:  # conv_gru has one pass: the slots of pass 2 are those of pass 1 again
+                seen.add(o)
+                out.append((lib.nnd_conv_name(C.byref(self.desc), i).decode() or f"conv{i}", o))
+        return out
 
     # "fp16": ONE range-scaled fp16 piece per operand (11 significand bits: above the bf16 autocast the reference validates under,
     # below fp32 parity; finite up to 32 x the calibrated maximum, inf / NaN beyond) — opt-in, never a default
@@ -874,11 +1001,15 @@ class ConvNorm:
 ENCODER_BLOCKS = ("layer1.0", "layer1.1", "layer2.0", "layer2.1", "layer3.0", "layer3.1")
 
 
-class EncoderEngine:
+class EncoderEngine(ScaleSlots):
     """BasicEncoder (+ optional cnet_proj) on the HIP encoder (csrc/encoder.hip).  Parameters come from state-dict
     style mappings: `enc_sd` with the reference's BasicEncoder keys (conv1.weight, norm1.running_mean,
     layer1.0.conv1.weight, layer1.0.downsample.0.weight, layer1.0.norm3.weight, ..., conv2.bias) and, optionally,
     `cnet_sd` with `0.weight` / `0.bias` of the cnet_proj Sequential."""
+
+    def _scale_slots(self) -> List[Tuple[str, int]]:
+        offs = _enumerate_slots(lambda o, n: lib.nnd_encoder_scale_slots(C.byref(self.desc), o, n), "encoder_scale_slots")
+        return [(lib.nnd_encoder_scale_name(C.byref(self.desc), i).decode(), o) for i, o in enumerate(offs) if o >= 0]
 
     def __init__(self, output_dim: int, norm: str = "batch", cnet_dim: int = 0, arithmetic: str = "fp32"):
         if norm not in ("batch", "none", "instance"):
@@ -1802,7 +1933,7 @@ def depth_major_to_volume_rows(x: torch.Tensor, out: Optional[torch.Tensor] = No
     return out
 
 
-class Conv3dNorm:
+class Conv3dNorm(ScaleSlots):
     """nn.Conv3d(k=3, padding=1, stride 1|2) [+ BatchNorm3d(eval)] [+ LeakyReLU] on depth-major volumes; the input may be the
     channel concat of two volumes.  `bn` = (weight, bias, running_mean, running_var) or None."""
 
@@ -1817,10 +1948,58 @@ class Conv3dNorm:
         self.calibrated = False
         self.leaky = float(leaky_slope)
         self.packed = _pack_conv_norm("conv3d", self.desc, weight, bias, bn, eps, device)
+        self._ran: Optional[torch.Tensor] = None  # device bools: which formulations recorded during the last calibration
 
     def _calibration_finish(self, status: Optional[torch.Tensor]) -> None:
+        offs = [o for _, o in self.formulations()]
+        if offs:  # which formulation(s) the calibration forwards took: the ones that hold a record (no synchronisation)
+            self._ran = scales_read(self.packed, offs, records=True)[1] != 0
         check(lib.nnd_conv3d_calibration_finish(C.byref(self.desc), _p(self.packed), _p(status), _stream(self.packed.device)),
               "conv3d_calibration_finish")
+
+    # ---- the layer's ONE activation range (scale_names() == [""]), held once per packed formulation
+    @staticmethod
+    def formulations_of(desc: Conv3dDesc) -> List[Tuple[str, int]]:
+        """(name, slot offset) of the fp16x2 formulations the blob of `desc` packs: "plain", "grouped", "slab" (host work)."""
+        offs = _enumerate_slots(lambda o, n: lib.nnd_conv3d_scale_slots(C.byref(desc), o, n), "conv3d_scale_slots")
+        return [(lib.nnd_conv3d_scale_name(i).decode(), o) for i, o in enumerate(offs) if o >= 0]
+
+    def formulations(self) -> List[Tuple[str, int]]:
+        if self.__dict__.get("_formulations") is None:
+            self._formulations = self.formulations_of(self.desc)
+        return self._formulations
+
+    def _scale_slots(self) -> List[Tuple[str, int]]:
+        f = self.formulations()
+        return [("", f[0][1])] if f else []
+
+    def read_scales(self, per_formulation: bool = False) -> torch.Tensor:
+        """The layer's exponent (1 element): that of the formulation(s) the last calibration ran, the smallest if several ran or none
+        is known to have (a loaded state sets them all alike).  per_formulation=True: one per formulations() entry, as stored."""
+        xs = scales_read(self._blob(), [o for _, o in self.formulations()])[0]
+        if per_formulation or xs.numel() == 0:
+            return xs
+        if self._ran is None:
+            return xs.min().reshape(1)
+        ran = self._ran | ~self._ran.any()
+        return torch.where(ran, xs, xs.max()).min().reshape(1)  # (the largest one stands in for those that did not run)
+
+    def read_records(self, clear: bool = True) -> torch.Tensor:
+        rec = scales_read(self._blob(), [o for _, o in self.formulations()], records=True, clear=clear)[1]
+        return rec.max().reshape(1) if rec.numel() else rec  # (a NaN record wins, as it does in the slot)
+
+    def write_scales(self, xs, widen: bool = False) -> None:
+        """Every packed formulation takes the exponent: the one the forward picks for another depth runs in the same range."""
+        offs = [o for _, o in self.formulations()]
+        xs = torch.as_tensor(xs).reshape(-1)
+        if xs.numel() != (1 if offs else 0):
+            raise NndError(f"Conv3dNorm.write_scales: {xs.numel()} exponents for {1 if offs else 0} layer")
+        scales_write(self._blob(), offs, xs.expand(len(offs)), widen)
+        self._ran = None
+        self.calibrated = True
+
+    def widen_scales(self, before: torch.Tensor) -> None:
+        self.write_scales(torch.minimum(self.read_scales(), before.to(self.packed.device)))
 
     def __call__(self, x0: torch.Tensor, x1: Optional[torch.Tensor] = None) -> torch.Tensor:
         d = _dev(x0, self.packed)

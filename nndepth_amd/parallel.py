@@ -93,6 +93,30 @@ def sharded_inference(n_pairs: int, load_pairs, forward_fn, micro_batch: int, ra
     return gather_ragged(local, n_pairs) if gather else local
 
 
+def sync_calibration(model, group=None) -> dict:
+    """The same fp16x2 activation ranges on every rank: each rank's calibration state (raft_stereo.calibration_state — calibrated on
+    its own shard, or loaded and still pending) is reduced to the per-layer MINIMUM of the exponents, i.e. the widest range any
+    rank needs, and loaded back (pinned).  ONE all-reduce of one int32 per layer, in sorted-key order; works on a gloo / CPU group
+    with states that are pending.  Every rank must call it; returns the common state."""
+    from .raft_stereo import calibration_state, load_calibration_state
+    state = calibration_state(model)
+    keys = sorted(state["layers"])
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        on_gpu = dist.get_backend(group) == "nccl"
+        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+        # the layer count first (as its minimum and the minimum of its negative): ranks whose models differ raise together
+        n = torch.tensor([len(keys), -len(keys)], dtype=torch.int32, device=dev)
+        dist.all_reduce(n, op=dist.ReduceOp.MIN, group=group)
+        if int(n[0]) != -int(n[1]):
+            raise ValueError(f"sync_calibration: the ranks hold between {int(n[0])} and {-int(n[1])} layers: not the same model")
+        xs = torch.tensor([state["layers"][k] for k in keys], dtype=torch.int32, device=dev)
+        if keys:
+            dist.all_reduce(xs, op=dist.ReduceOp.MIN, group=group)
+        state = {"version": state["version"], "arithmetic": state["arithmetic"], "layers": dict(zip(keys, xs.cpu().tolist()))}
+    load_calibration_state(model, state)
+    return state
+
+
 def max_over_ranks(seconds: float, device) -> float:
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return seconds

@@ -20,6 +20,9 @@ The classes are inference-only (eval-mode BatchNorm is folded into the convoluti
 `patch(model)` installs the same kernels behind the three duck-typed seams of an *unmodified*
 reference model instance: `corr_fn`, `update_block`, `convex_upsample`.
 """
+import contextlib
+import functools
+import json
 import os
 from typing import Dict, List, Optional
 
@@ -80,6 +83,116 @@ def calibration_passes(run, max_passes: int, error: str) -> None:
     raise NndError(error)
 
 
+# ------------------------------------------------------------------------------------------------ calibration state
+# The activation ranges of a model as data: {"version": 1, "arithmetic": name, "layers": {key: xs}} with xs the exponent of a layer's
+# activation scale 2^xs (its valid range is |x| < 65504 / 2^xs) and key = "<module path>/<layer name>" — "fnet/layer1.0.conv1",
+# "update_block/encoder.convc2" — or the module path alone where the module is one layer ("cv_regularizer.conv1.0").  Keys come
+# from the model's structure, never from the order in which its engines were built or used.  The state is independent of the weights'
+# own scales (those are fixed at pack time from the weights), plain Python, and never part of state_dict().  The functions take a
+# model class of this package or a reference model patched with patch() / patch_coarse2fine().
+CALIBRATION_STATE_VERSION = 1
+
+
+def calibration_sites(model: nn.Module) -> Dict[str, "ops.ScaleSite"]:
+    """{module path: ops.ScaleSite} of every engine that takes part in a calibration of `model`, in a fixed order."""
+    fn = getattr(model, "_calibration_sites", None)
+    if fn is not None:
+        return fn()
+    return {"update_block": model.update_block.calibration_site()}  # a patched reference model: the update block is the HIP engine
+
+
+def _model_arithmetic(model: nn.Module) -> str:
+    return getattr(model, "arithmetic", None) or model.update_block.engine.arithmetic
+
+
+def _site_engine(site: "ops.ScaleSite"):
+    """The site's engine if it is packed on a HIP device, else None (not built yet, or packed on the host)."""
+    eng = site.engine()
+    return eng if eng is not None and eng.on_device() else None
+
+
+def _layer_key(path: str, name: str) -> str:
+    return f"{path}/{name}" if name else path
+
+
+def calibration_state(model: nn.Module) -> dict:
+    """The model's activation ranges (see above).  A loaded state is returned as loaded, without a GPU; otherwise the exponents are
+    read from the packed engines (one small launch each, ONE synchronisation), which must exist: after a forward or calibrate()."""
+    pinned = getattr(model, "_calib_pinned", None)
+    if pinned is not None:
+        return {"version": CALIBRATION_STATE_VERSION, "arithmetic": pinned["arithmetic"], "layers": dict(pinned["layers"])}
+    keys, parts = [], []
+    for path, site in calibration_sites(model).items():
+        if not site.names:
+            continue
+        eng = _site_engine(site)
+        if eng is None:
+            raise NndError(f"calibration_state: '{path}' is not packed yet: run a forward or calibrate() first, or load a state")
+        keys += [_layer_key(path, n) for n in site.names]
+        parts.append(eng.read_scales())
+    xs = torch.cat([p.to(parts[0].device) for p in parts]).cpu().tolist() if parts else []
+    return {"version": CALIBRATION_STATE_VERSION, "arithmetic": _model_arithmetic(model), "layers": dict(zip(keys, xs))}
+
+
+def _apply_pinned(model: nn.Module, _built=None, force: bool = False) -> None:
+    """Writes the loaded state into every packed engine that does not carry it yet (ParamCache.on_build: after every repack)."""
+    pinned = getattr(model, "_calib_pinned", None)
+    if pinned is None:
+        return
+    for path, site in calibration_sites(model).items():
+        eng = _site_engine(site)
+        if eng is not None and site.names and (force or not eng.calibrated):
+            eng.write_scales([pinned["layers"][_layer_key(path, n)] for n in site.names])
+
+
+def load_calibration_state(model: nn.Module, state: dict) -> nn.Module:
+    """Pins `state` on the model: written into the engines that are packed (in place: a captured GraphedForward runs with it on its
+    next replay), kept pending for the others and written when they are packed, and again after every repack; the model classes do
+    not calibrate on their first forward any more.  NndError naming the difference if the state is of another arithmetic or its keys
+    are not this model's.  clear_calibration_state() or an explicit calibrate() unpins it."""
+    if not isinstance(state, dict) or state.get("version") != CALIBRATION_STATE_VERSION or not isinstance(state.get("layers"), dict):
+        raise NndError(f"load_calibration_state: not a version {CALIBRATION_STATE_VERSION} calibration state "
+                       "({'version', 'arithmetic', 'layers'})")
+    arith = _model_arithmetic(model)
+    if state.get("arithmetic") != arith:
+        raise NndError(f"load_calibration_state: the state is of arithmetic {state.get('arithmetic')!r}, the model runs {arith!r}")
+    sites = calibration_sites(model)
+    want = {_layer_key(p, n) for p, s in sites.items() for n in s.names}
+    missing, extra = sorted(want - set(state["layers"])), sorted(set(state["layers"]) - want)
+    if missing or extra:
+        raise NndError("load_calibration_state: the state's layers are not this model's: "
+                       + "; ".join(f"{what}: {', '.join(k)}" for what, k in (("missing", missing), ("unexpected", extra)) if k))
+    layers = {}
+    for k, v in state["layers"].items():
+        if isinstance(v, bool) or not isinstance(v, int) or abs(v) > 60:
+            raise NndError(f"load_calibration_state: layer {k!r}: exponent {v!r} is not an integer in -60 .. 60")
+        layers[k] = v
+    model._calib_pinned = {"arithmetic": arith, "layers": layers}
+    for site in sites.values():
+        site.cache.on_build = functools.partial(_apply_pinned, model)
+    _apply_pinned(model, force=True)
+    return model
+
+
+def clear_calibration_state(model: nn.Module) -> nn.Module:
+    """Unpins a loaded state: the engines keep the scales they have, a repack returns to the defaults (and the model classes to
+    calibrating on their next forward)."""
+    model._calib_pinned = None
+    for site in calibration_sites(model).values():
+        site.cache.on_build = None
+    return model
+
+
+def save_calibration(model: nn.Module, path: str) -> None:
+    with open(path, "w") as f:
+        json.dump(calibration_state(model), f, indent=1, sort_keys=True)
+
+
+def load_calibration(model: nn.Module, path: str) -> nn.Module:
+    with open(path) as f:
+        return load_calibration_state(model, json.load(f))
+
+
 class AutoCalibrate:
     """fp16x2 activation range (include/nndepth_amd.h "fp16x2 activation range", csrc/calib.hip), shared by the model classes.
 
@@ -92,33 +205,128 @@ class AutoCalibrate:
     `auto_calibrate = False` to keep the default scales.  `activation_ranges()` reports the valid |x| per update-block layer.
 
     The "fp16" arithmetic (opt-in) keeps the first of the two pieces only: 11 significand bits per operand — three more than the bf16
-    autocast the reference's trainers validate under, not fp32 parity — with the same scales, calibration and range behaviour."""
+    autocast the reference's trainers validate under, not fp32 parity — with the same scales, calibration and range behaviour.
+
+    The ranges are data (see "calibration state" above): `calibration_state()` / `load_calibration_state()` (`save_calibration` /
+    `load_calibration`: a JSON file) carry them to another process or rank (parallel.sync_calibration: the same ranges on every rank);
+    a loaded state is pinned — re-applied after every repack, no calibration on the first forward.  `calibrate(..., widen=True)` extends
+    the ranges held before instead of replacing them: per layer the smaller exponent, so a range only grows — each step doubles the
+    largest |x| and moves the 13 octaves of full precision up with it, away from the small values.  `watch_range = True` adds one small
+    launch per forward that looks for inf / NaN in the final output (an exceeded range always reaches it), `range_status()` reads the
+    answer; `range_report(frame1, frame2)` says which layer an input exceeds."""
 
     auto_calibrate = True
+    watch_range = False  # True: every forward() ORs "the final output holds inf / NaN" into a device word (range_status)
+    _calib_pinned = None  # a loaded calibration state: {"arithmetic", "layers"}
+    _range_word = None
+    _range_forwards = 0
 
-    def calibrate(self, *args, max_passes: int = 4, **kwargs):
-        require_eval(self)
+    @contextlib.contextmanager
+    def _all_outputs(self):
+        """Inside, the model returns every iteration's map: the mask head records its range over all of them, whatever `outputs` is."""
         outputs = getattr(self, "outputs", "all")
-        self.outputs = "all"  # the mask head records its range over every iteration, whatever the model returns
+        self.outputs = "all"
         try:
+            yield
+        finally:
+            self.outputs = outputs
+
+    def calibrate(self, *args, max_passes: int = 4, widen: bool = False, **kwargs):
+        """widen=False (default): the ranges of these frames replace the ones held.  widen=True: every engine that was calibrated
+        (or loaded) before keeps, per layer, the smaller of its old and its new exponent — the ranges only grow."""
+        require_eval(self)
+        clear_calibration_state(self)  # an explicit calibration unpins a loaded state
+        before = []
+        if widen and self.arithmetic in ops.RANGE_SCALED:
+            for site in calibration_sites(self).values():
+                eng = _site_engine(site)
+                if eng is not None and site.names and eng.calibrated:
+                    before.append((eng, eng.packed, eng.read_scales()))  # device tensors: no synchronisation
+        with self._all_outputs():
             calibration_passes(lambda: self._forward(*args, **kwargs), max_passes,
                                f"{type(self).__name__}.calibrate: activations still overflow fp16 after {max_passes} passes "
                                "(non-finite inputs or weights?)")
-        finally:
-            self.outputs = outputs
+        for eng, blob, xs in before:
+            if eng.packed is blob:  # (not repacked in between)
+                eng.widen_scales(xs)
         return self
 
     def _forward_calibrated(self, *args, **kwargs):
         """`_forward`, calibrating first if an fp16x2 engine on its path still has the default activation scales."""
         check_outputs(getattr(self, "outputs", "all"))  # (an attribute: it may have been set after construction)
-        if self.arithmetic not in ops.RANGE_SCALED or not self.auto_calibrate:
-            return self._forward(*args, **kwargs)
+        if self.arithmetic not in ops.RANGE_SCALED or not self.auto_calibrate or self._calib_pinned is not None:
+            return self._watched(self._forward(*args, **kwargs))  # (a pinned state is written when an engine is packed)
         try:
             with ops.require_calibrated():
-                return self._forward(*args, **kwargs)
+                return self._watched(self._forward(*args, **kwargs))
         except ops.NeedsCalibration:
             self.calibrate(*args, **kwargs)
-            return self._forward(*args, **kwargs)
+            return self._watched(self._forward(*args, **kwargs))
+
+    # ---- the ranges as data
+    def _calibration_sites(self) -> Dict[str, "ops.ScaleSite"]:
+        """{module path: site} of the engines a forward of this model calibrates; the model classes add theirs in front."""
+        return {"update_block": self.update_block.calibration_site()}
+
+    def _encoder_site(self, cache: "ops.ParamCache", output_dim: int, cnet_dim: int) -> "ops.ScaleSite":
+        names = ops.EncoderEngine(output_dim, self.fnet.norm_fn, cnet_dim, self.arithmetic).scale_names()  # descriptor only: host work
+        return ops.ScaleSite(names, lambda: cache.value, cache)
+
+    def calibration_state(self) -> dict:
+        return calibration_state(self)
+
+    def load_calibration_state(self, state: dict):
+        return load_calibration_state(self, state)
+
+    def clear_calibration_state(self):
+        return clear_calibration_state(self)
+
+    def save_calibration(self, path: str) -> None:
+        save_calibration(self, path)
+
+    def load_calibration(self, path: str):
+        return load_calibration(self, path)
+
+    # ---- overflow
+    def _watched(self, outs):
+        if self.watch_range:
+            final = outs if torch.is_tensor(outs) else outs[-1]["up_disp"]
+            if self._range_word is None or self._range_word.device != final.device:
+                self._range_word = torch.zeros(1, dtype=torch.int32, device=final.device)
+            ops.nonfinite_flag(final, self._range_word)
+            self._range_forwards += 1
+        return outs
+
+    def range_status(self) -> dict:
+        """{"overflow": an inf / NaN reached the final output of a watched forward since the last reset, "forwards": how many were
+        watched (calls of forward(): the replays of a captured graph are not counted)}.  One synchronisation."""
+        word = 0 if self._range_word is None else int(self._range_word.item())
+        return {"overflow": bool(word & 1), "forwards": self._range_forwards}
+
+    def reset_range_status(self) -> None:
+        if self._range_word is not None:
+            self._range_word.zero_()
+        self._range_forwards = 0
+
+    def range_report(self, *args, **kwargs) -> Dict[str, Dict[str, float]]:
+        """{layer: {"seen": the largest |x| the layer stages on these frames, "limit": 65504 / 2^xs, what it can represent}} — one forward
+        that records (NND_FLAG_CALIBRATE) and whose records are read and cleared instead of being turned into scales: no scale
+        changes.  seen > limit: that layer is exceeded (behind it the values are inf / NaN).  Layers off this forward's path: seen 0."""
+        require_eval(self)
+        if self.arithmetic not in ops.RANGE_SCALED:
+            return {}
+        try:
+            with self._all_outputs(), ops.calibration(finish=False), torch.no_grad():
+                self._forward(*args, **kwargs)
+        finally:  # the records never stay behind: they would join the next calibration's
+            sites = [(p, s, _site_engine(s)) for p, s in calibration_sites(self).items() if s.names]
+            sites = [(p, s, e) for p, s, e in sites if e is not None]
+            got = [(p, s, e.read_scales(), e.read_records(clear=True)) for p, s, e in sites]
+        report = {}
+        for path, site, xs, seen in got:
+            for n, e, m in zip(site.names, xs.cpu().tolist(), seen.cpu().tolist()):
+                report[_layer_key(path, n)] = {"seen": float(m), "limit": 65504.0 / 2.0 ** e}
+        return report
 
     def activation_ranges(self):
         eng = self.update_block.engine
@@ -171,6 +379,13 @@ class BaseRAFTStereo(AutoCalibrate, nn.Module):
             eng = ops.EncoderEngine(self.fnet_dim, self.fnet.norm_fn, self.context_dim + self.hidden_dim, self.arithmetic)
             return eng.load(self.fnet.state_dict(), self.cnet_proj.state_dict(), eps=1e-5, device=device)
         return self._enc_cache.get((self.fnet, self.cnet_proj), device, build)
+
+    def _calibration_sites(self):
+        sites = {}
+        if self.hip_encoder and hip_encoder_blocker(self.fnet, ("batch", "none")) is None:  # fnet + cnet_proj: one engine, one blob
+            sites["fnet"] = self._encoder_site(self._enc_cache, self.fnet_dim, self.context_dim + self.hidden_dim)
+        sites.update(super()._calibration_sites())
+        return sites
 
     def forward_fnet(self, frame1, frame2):
         if self.hip_encoder:
