@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define NND_VERSION 105 /* 0.1.5: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning); 105 the single-output EPE criterion's two symbols (the entry point and its workspace query) are removed: nnd_stereo_eval with one output is that criterion (nnd_igev_init_disparity_dev — any G <= 64, D <= 4096, parameters read from device memory — with its queries nnd_igev_init_disparity_supported / _chunk / _kernel, and nnd_resize_nearest_scaled are additions within 105: nothing existing changed its signature or meaning) */
+#define NND_VERSION 105 /* 0.1.5: 102 descriptors carry struct_size and flags, per-layer fp16x2 activation scales + calibration; 103 group-RAFT entry points; 104 nnd_profile_mfma16_peak (the nnd_midas_* entry points are additions within 104: nothing existing changed its signature or meaning); 105 the single-output EPE criterion's two symbols (the entry point and its workspace query) are removed: nnd_stereo_eval with one output is that criterion (nnd_igev_init_disparity_dev — any G <= 64, D <= 4096, parameters read from device memory — with its queries nnd_igev_init_disparity_supported / _chunk / _kernel, nnd_resize_nearest_scaled and the stereo-geometry entry points nnd_disparity_to_depth ... nnd_pair_both_views are additions within 105: nothing existing changed its signature or meaning) */
 
 /* Descriptors start with `struct_size` = sizeof(the descriptor type) of the header the caller was compiled against; every entry
  * point that takes one refuses another size (NND_ERR_INVALID), so a caller and a library of different versions cannot
@@ -776,6 +776,52 @@ int nnd_resize_bilinear(const void* src, int src_is_u8, float* dst, unsigned cha
                         int planes, int h, int w, int H, int W, int align_corners, int rescale, float mul, float div, void* stream);
 int nnd_depth_inverse(const float* src, float* dst, int64_t n, float eps, int has_max, float clip_max, int has_min, float clip_min,
                       void* stream);
+
+/* ------------------------------------------------------------- stereo geometry on the device (additions within 105)
+ * What a caller does with a disparity map next: metric depth, 3-D points, a left-right occlusion mask (csrc/geometry.hip).  The
+ * reference stores the fields this consumes — Disparity.baseline (nndepth/scene/disparity.py:79-108), Camera.intrinsic
+ * (nndepth/scene/camera.py:5-8), Disparity.occlusion (filled from ground truth only, kitti_stereo_2015.py:188-194: 1 = no valid
+ * disparity) — and has one conversion of this kind, TartanAir's disparity = -BASELINE * FX / (depth + 1e-8)
+ * (nndepth/data/datasets/tartanair_dataset.py:30,239-241).
+ * Maps are (B,1,H,W) fp32 with dense rows; `*_bstride` = floats between batch elements (H*W when contiguous; a channel slice of a
+ * (B,2,H,W) tensor has 2*H*W).  Outputs are contiguous.  Masks are bytes (B,H,W), non-zero = set.  `cam` = device floats
+ * {fx, fy, cx, cy} per batch element, cam_stride floats apart (0: one camera for the whole batch).  `negative` != 0: the map's
+ * sign convention is "negative" (m = -d), else m = d.  Every launch on `stream`; no allocation, no synchronisation.
+ * nnd_disparity_to_depth : z = (float)((double)fx * baseline / (double)m); valid = mask_in (NULL: set) && isfinite(m) &&
+ *     m > min_disp && (!has_max || z <= max_depth); depth = valid ? z : 0; valid_out = valid (0 / 1).
+ * nnd_depth_to_disparity : the TartanAir line in its fp32 order: c = (float)(-baseline * (double)fx); d = c / (depth +
+ *     (float)eps), both fp32; "positive" (negative == 0): d = -d.
+ * nnd_depth_to_points    : points (B,3,H,W): X = (float)(((double)u - cx) * Z / fx), Y = (float)(((double)v - cy) * Z / fy), Z
+ *     copied; u = column, v = row; all three 0 where `valid` (optional) is 0.
+ * nnd_points_compact     : the same points for the valid pixels only, as rows {X, Y, Z} of `points` (B*H*W rows of 3 floats,
+ *     worst case): sample b's valid pixels in row-major order are rows offsets[b] .. offsets[b+1] (offsets: B+1 int64; rows past
+ *     offsets[B] are not written).  `features` (optional, (B,C,H,W) contiguous, with `feats_out` (B*H*W rows of C floats)) is
+ *     gathered into the same rows.  Three launches — per-workgroup counts (wave ballot + popcount), one exclusive scan of
+ *     the counts, the writes — in integer arithmetic: no atomics, no workgroup waits on another, the same bytes every run.
+ *     `workspace` = nnd_points_compact_workspace_bytes(B,H,W) device bytes, 8-byte aligned.
+ * nnd_lr_consistency     : occluded (B,H,W) bytes, 1 = occluded / inconsistent (the polarity of the KITTI mask).  Per pixel, each
+ *     step one rounded fp32 operation: mL = +-dL; !isfinite(mL) || mL < 0 -> 1; xr = (float)x - mL; xr < 0 || xr > W-1 -> 1;
+ *     i0 = floor(xr), i1 = min(i0+1, W-1), f = xr - i0; s = mR(i0) * (1 - f) + mR(i1) * f (mul, mul, add); err = |mL - s|;
+ *     occluded = !(err <= threshold).  right_flipped: disp_right is stored mirrored in W, mR(i) reads column W-1-i.  `err_out`
+ *     (optional, (B,H,W) floats): err, +inf where an earlier test decided.
+ * nnd_pair_both_views    : frames1 (2B,C,H,W) = [left ; flipW(right)], frames2 = [right ; flipW(left)] in one launch: the second
+ *     half is a rectified pair whose "left" disparity is the right view's, mirrored.                                          */
+int nnd_disparity_to_depth(const float* disp, int64_t disp_bstride, const unsigned char* mask_in, const float* cam, int cam_stride,
+                           double baseline, int negative, float min_disp, int has_max, float max_depth, float* depth,
+                           unsigned char* valid_out, int B, int H, int W, void* stream);
+int nnd_depth_to_disparity(const float* depth, int64_t depth_bstride, const float* cam, int cam_stride, double baseline, int negative,
+                           double eps, float* disp, int B, int H, int W, void* stream);
+int nnd_depth_to_points(const float* depth, int64_t depth_bstride, const unsigned char* valid, const float* cam, int cam_stride,
+                        float* points, int B, int H, int W, void* stream);
+int64_t nnd_points_compact_workspace_bytes(int B, int H, int W);
+int nnd_points_compact(const float* depth, int64_t depth_bstride, const unsigned char* valid, const float* cam, int cam_stride,
+                       const float* features, int C, float* points, float* feats_out, int64_t* offsets, void* workspace,
+                       int64_t workspace_bytes, int B, int H, int W, void* stream);
+int nnd_lr_consistency(const float* disp_left, int64_t left_bstride, const float* disp_right, int64_t right_bstride, int left_negative,
+                       int right_negative, int right_flipped, float threshold, unsigned char* occluded, float* err_out, int B, int H,
+                       int W, void* stream);
+int nnd_pair_both_views(const float* left, const float* right, float* frames1, float* frames2, int B, int C, int H, int W,
+                        void* stream);
 
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58

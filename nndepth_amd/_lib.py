@@ -222,6 +222,13 @@ SIGNATURES = {
     "nnd_pool_abs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_resize_bilinear": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "nnd_depth_inverse": (_I, [_P, _P, C.c_int64, C.c_float, _I, C.c_float, _I, C.c_float, _P]),
+    "nnd_disparity_to_depth": (_I, [_P, C.c_int64, _P, _P, _I, C.c_double, _I, C.c_float, _I, C.c_float, _P, _P, _I, _I, _I, _P]),
+    "nnd_depth_to_disparity": (_I, [_P, C.c_int64, _P, _I, C.c_double, _I, C.c_double, _P, _I, _I, _I, _P]),
+    "nnd_depth_to_points": (_I, [_P, C.c_int64, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "nnd_points_compact_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "nnd_points_compact": (_I, [_P, C.c_int64, _P, _P, _I, _P, _I, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
+    "nnd_lr_consistency": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, C.c_float, _P, _P, _I, _I, _I, _P]),
+    "nnd_pair_both_views": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "nnd_loftr_packed_floats": (C.c_int64, [_I, _I]),
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),

@@ -1,0 +1,235 @@
+"""Stereo geometry on the device (csrc/geometry.hip): what a caller does with a disparity map next, without a `.cpu()`.
+
+The reference stores `Disparity.baseline` (nndepth/scene/disparity.py:79-108) and `Camera.intrinsic` (camera.py:5-8) and never
+consumes them; its `Disparity.occlusion` is only ever filled from ground truth (kitti_stereo_2015.py:188-194, 1 = no valid
+disparity); its one conversion is TartanAir's `disparity = -BASELINE * FX / (depth + 1e-8)` (tartanair_dataset.py:30,239-241).
+Here:
+
+    disparity_to_depth / depth_to_disparity    (Disparity.to_depth, Depth.to_disparity of scene.py)
+    depth_to_points / points_compact           (Depth.to_points_map, Depth.points_tensor, Depth.to_points)
+    lr_consistency, both_views, occlusion      a left-right check of a PREDICTED map -> an occlusion mask, 1 = occluded
+
+Maps are (B,1,H,W) fp32 on the HIP device; a batch stride is read where it lies (a channel slice of CREStereo's 2-channel
+output, half of a stacked batch).  Masks are torch.bool or torch.uint8, (B,1,H,W) or (B,H,W).  Camera values come from
+`Camera.intrinsic`, (3,3) or (B,3,3): fx [0,0], fy [1,1], cx [0,2], cy [1,2]; the kernels read them from a small device array
+(a host tensor is copied once per Camera and device, and no call synchronises on it).  Nothing falls back to PyTorch: a CPU map
+is refused.  No function here synchronises with the host except `Depth.to_points`, which says so."""
+from typing import Callable, Optional, Tuple
+
+import torch
+
+from ._lib import NndError, check, lib
+from .ops import _p, _stream
+
+_SIGNS = ("negative", "positive")
+
+
+def _map4(t, what: str, mask=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The (B,1,H,W) fp32 device map `t` with dense rows (its batch stride is kept; anything else is made contiguous) and its
+    bool / uint8 mask, (B,1,H,W) or (B,H,W), as contiguous bytes (None stays None)."""
+    if not torch.is_tensor(t):
+        raise NndError(f"{what}: the map must be a tensor on the HIP device; got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise NndError(f"{what}: maps are torch.float32; got {t.dtype}")
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise NndError(f"{what}: masks are torch.bool or torch.uint8; got {getattr(mask, 'dtype', type(mask).__name__)}")
+    if t.device.type != "cuda":
+        raise NndError(f"{what}: the map must be on the HIP device (got {t.device}); there is no CPU fallback")
+    if t.ndim != 4 or t.shape[1] != 1 or t.numel() == 0:
+        raise NndError(f"{what}: a map is (B,1,H,W); got {tuple(t.shape)}")
+    B, _, H, W = t.shape
+    if not (t.stride(3) == 1 and t.stride(2) == W and (B == 1 or t.stride(0) >= H * W)):
+        t = t.contiguous()
+    if mask is not None:
+        if mask.device != t.device:
+            raise NndError(f"{what}: the mask is on {mask.device}, the map on {t.device} (no CPU fallback exists)")
+        if tuple(mask.shape) not in ((B, 1, H, W), (B, H, W)):
+            raise NndError(f"{what}: the mask is {tuple(mask.shape)}, the map {tuple(t.shape)}")
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    return t, mask
+
+
+def _bstride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[2] * t.shape[3]
+
+
+def _sign(sign: str, what: str) -> int:
+    if sign not in _SIGNS:
+        raise NndError(f"{what}: disp_sign must be either 'positive' or 'negative'; got {sign!r}")
+    return int(sign == "negative")
+
+
+def camera_params(camera_or_fx, B: int, device: torch.device, what: str = "camera_params",
+                  fx_only: bool = True) -> Tuple[torch.Tensor, int]:
+    """(device floats {fx, fy, cx, cy} per camera, stride between batch elements: 0 = one camera for all B) of a `scene.Camera`,
+    a (3,3) / (B,3,3) intrinsic tensor, or a number (fx alone: what the disparity conversions read).  The device copy of a
+    Camera's intrinsic is kept on the Camera (until the tensor is replaced or edited in place)."""
+    K = getattr(camera_or_fx, "intrinsic", camera_or_fx)
+    if K is None:
+        raise NndError(f"{what}: the camera has no intrinsic")
+    if isinstance(K, (int, float)):
+        if not fx_only:
+            raise NndError(f"{what}: fx alone does not back-project; pass a scene.Camera or an intrinsic tensor")
+        return torch.empty((1, 4), dtype=torch.float32, device=device).fill_(float(K)), 0  # a fill on the device: no copy
+    if not torch.is_tensor(K):
+        raise NndError(f"{what}: a scene.Camera, an intrinsic tensor or fx as a number; got {type(K).__name__}")
+    if K.ndim not in (2, 3) or tuple(K.shape[-2:]) != (3, 3) or (K.ndim == 3 and K.shape[0] not in (1, B)):
+        raise NndError(f"{what}: the intrinsic is (3,3) or (B,3,3) with B = {B}; got {tuple(K.shape)}")
+    key = (K.data_ptr(), K._version, str(device))
+    cached = getattr(camera_or_fx, "_device_params", None) if camera_or_fx is not K else None
+    if cached is not None and cached[0] == key:
+        par = cached[1]
+    else:
+        K3 = K.reshape(-1, 3, 3)
+        par = torch.stack([K3[:, 0, 0], K3[:, 1, 1], K3[:, 0, 2], K3[:, 1, 2]], dim=1).to(torch.float32).contiguous()
+        par = par.to(device, non_blocking=True)
+        if camera_or_fx is not K:
+            camera_or_fx._device_params = (key, par)
+    return par, (4 if par.shape[0] > 1 else 0)
+
+
+def disparity_to_depth(disp: torch.Tensor, camera_or_fx, baseline: float, disp_sign: str = "negative", min_disp: float = 0.0,
+                       max_depth: Optional[float] = None, valid_mask: Optional[torch.Tensor] = None):
+    """(depth (B,1,H,W) fp32, valid (B,1,H,W) uint8).  m = -d for "negative"; z = fp32(double(fx_b) * double(baseline) /
+    double(m)); valid = valid_mask && isfinite(m) && m > min_disp && (max_depth is None || z <= max_depth); depth = valid ? z : 0."""
+    what = "disparity_to_depth"
+    neg = _sign(disp_sign, what)
+    if baseline is None:
+        raise NndError(f"{what}: no baseline (pass one, or construct the Disparity with its baseline)")
+    d, m = _map4(disp, what, valid_mask)
+    B, _, H, W = d.shape
+    cam, cs = camera_params(camera_or_fx, B, d.device, what)
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
+    valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib.nnd_disparity_to_depth(_p(d), _bstride(d), _p(m), _p(cam), cs, float(baseline), neg, float(min_disp),
+                                         int(max_depth is not None), float(max_depth or 0.0), _p(depth), _p(valid), B, H, W,
+                                         _stream(d.device)), what)
+    return depth, valid
+
+
+def depth_to_disparity(depth: torch.Tensor, camera_or_fx, baseline: float, disp_sign: str = "negative", eps: float = 1e-8) -> torch.Tensor:
+    """The reference's TartanAir line in its fp32 order: fp32(-baseline * fx) / (depth + fp32(eps)); negated for "positive"."""
+    what = "depth_to_disparity"
+    neg = _sign(disp_sign, what)
+    if baseline is None:
+        raise NndError(f"{what}: no baseline")
+    z, _ = _map4(depth, what)
+    B, _, H, W = z.shape
+    cam, cs = camera_params(camera_or_fx, B, z.device, what)
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        check(lib.nnd_depth_to_disparity(_p(z), _bstride(z), _p(cam), cs, float(baseline), neg, float(eps), _p(out), B, H, W,
+                                         _stream(z.device)), what)
+    return out
+
+
+def depth_to_points(depth: torch.Tensor, camera, valid_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,3,H,W): X = fp32((u - cx) * Z / fx), Y = fp32((v - cy) * Z / fy) in double, Z copied; 0 where valid_mask is 0."""
+    what = "depth_to_points"
+    z, m = _map4(depth, what, valid_mask)
+    B, _, H, W = z.shape
+    cam, cs = camera_params(camera, B, z.device, what, fx_only=False)
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        check(lib.nnd_depth_to_points(_p(z), _bstride(z), _p(m), _p(cam), cs, _p(out), B, H, W, _stream(z.device)), what)
+    return out
+
+
+def points_compact(depth: torch.Tensor, camera, valid_mask: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None):
+    """(points (B*H*W,3) fp32, feats (B*H*W,C) or None, offsets (B+1,) int64), all on the device, no host synchronisation.
+    The valid points of sample b are rows offsets[b]:offsets[b+1] in row-major pixel order; rows past offsets[B] are
+    unspecified.  `features` (B,C,H,W) fp32 is gathered into the same rows.  The same bytes on every run."""
+    what = "points_compact"
+    z, m = _map4(depth, what, valid_mask)
+    B, _, H, W = z.shape
+    feats = None
+    Cf = 0
+    if features is not None:
+        if not torch.is_tensor(features) or features.dtype != torch.float32:
+            raise NndError(f"{what}: features are torch.float32; got {getattr(features, 'dtype', type(features).__name__)}")
+        if features.device != z.device:
+            raise NndError(f"{what}: the features are on {features.device}, the map on {z.device} (no CPU fallback exists)")
+        if features.ndim != 4 or features.shape[0] != B or tuple(features.shape[2:]) != (H, W) or features.shape[1] < 1:
+            raise NndError(f"{what}: features are (B,C,H,W) = ({B},C,{H},{W}); got {tuple(features.shape)}")
+        features = features.contiguous()
+        Cf = features.shape[1]
+        feats = torch.empty((B * H * W, Cf), dtype=torch.float32, device=z.device)
+    cam, cs = camera_params(camera, B, z.device, what, fx_only=False)
+    nbytes = int(lib.nnd_points_compact_workspace_bytes(B, H, W))
+    if nbytes < 0:
+        check(nbytes, what)
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=z.device)
+    points = torch.empty((B * H * W, 3), dtype=torch.float32, device=z.device)
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=z.device)
+    with torch.cuda.device(z.device):
+        check(lib.nnd_points_compact(_p(z), _bstride(z), _p(m), _p(cam), cs, _p(features), Cf, _p(points), _p(feats), _p(offsets),
+                                     _p(ws), ws.numel() * 8, B, H, W, _stream(z.device)), what)
+    return points, feats, offsets
+
+
+def lr_consistency(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold: float = 1.0, left_sign: str = "negative",
+                   right_sign: str = "negative", right_flipped: bool = False, return_error: bool = False):
+    """The occlusion mask of a left disparity map from the right view's: uint8 of disp_left's shape, 1 = occluded / inconsistent
+    (the polarity of the reference's KITTI mask).  `disp_right` is the disparity of the RIGHT view; right_flipped: it is stored
+    mirrored in W (the second output of `both_views`) and read in place.  Per pixel (y,x), each step one rounded fp32 operation:
+
+        mL = sL * dL[y,x]                      !isfinite(mL) or mL < 0 -> occluded
+        xr = float(x) - mL                     xr < 0 or xr > W-1      -> occluded
+        i0 = floor(xr); i1 = min(i0+1, W-1); f = xr - i0
+        s = mR(i0) * (1-f) + mR(i1) * f ;  err = |mL - s| ;  occluded = !(err <= threshold)      (a NaN gives occluded)
+
+    return_error: also the (B,1,H,W) fp32 err, +inf where an earlier test decided."""
+    what = "lr_consistency"
+    nl, nr = _sign(left_sign, what), _sign(right_sign, what)
+    dl, dr = _map4(disp_left, what)[0], _map4(disp_right, what)[0]
+    if dl.shape != dr.shape or dl.device != dr.device:
+        raise NndError(f"{what}: disp_left is {tuple(dl.shape)} on {dl.device}, disp_right {tuple(dr.shape)} on {dr.device}")
+    B, _, H, W = dl.shape
+    occ = torch.empty((B, 1, H, W), dtype=torch.uint8, device=dl.device)
+    err = torch.empty((B, 1, H, W), dtype=torch.float32, device=dl.device) if return_error else None
+    with torch.cuda.device(dl.device):
+        check(lib.nnd_lr_consistency(_p(dl), _bstride(dl), _p(dr), _bstride(dr), nl, nr, int(bool(right_flipped)), float(threshold),
+                                     _p(occ), _p(err), B, H, W, _stream(dl.device)), what)
+    return (occ, err) if return_error else occ
+
+
+def pair_both_views(left: torch.Tensor, right: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """frames1 = [left ; flipW(right)], frames2 = [right ; flipW(left)], batch 2B, in one launch."""
+    what = "both_views"
+    for t in (left, right):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise NndError(f"{what}: frames are torch.float32; got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.device.type != "cuda":
+            raise NndError(f"{what}: the frames must be on the HIP device (got {t.device}); there is no CPU fallback")
+    if left.ndim != 4 or left.shape != right.shape or left.device != right.device or left.numel() == 0:
+        raise NndError(f"{what}: two (B,C,H,W) frames of one shape on one device; got {tuple(left.shape)} and {tuple(right.shape)}")
+    left, right = left.contiguous(), right.contiguous()
+    B, Cc, H, W = left.shape
+    f1 = torch.empty((2 * B, Cc, H, W), dtype=torch.float32, device=left.device)
+    f2 = torch.empty_like(f1)
+    with torch.cuda.device(left.device):
+        check(lib.nnd_pair_both_views(_p(left), _p(right), _p(f1), _p(f2), B, Cc, H, W, _stream(left.device)), what)
+    return f1, f2
+
+
+def both_views(forward: Callable, left: torch.Tensor, right: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(disp_left, disp_right_flipped) from ONE call of `forward` (a model or a `GraphedForward`) at batch 2B.  The flipped,
+    swapped pair [flipW(right), flipW(left)] is a rectified pair whose "left" disparity is the right view's, mirrored in W:
+    feed it to `lr_consistency(..., right_flipped=True)` as it is.  Only outputs[-1]["up_disp"] is used; the two halves come
+    back as views of it (channel 0 of a 2-channel map)."""
+    f1, f2 = pair_both_views(left, right)
+    up = forward(f1, f2)[-1]["up_disp"]
+    B = left.shape[0]
+    if up.ndim != 4 or up.shape[0] != 2 * B:
+        raise NndError(f"both_views: the forward returned up_disp {tuple(up.shape)} for a batch of {2 * B}")
+    return up[:B, :1], up[B:, :1]
+
+
+def occlusion(forward: Callable, left: torch.Tensor, right: torch.Tensor, threshold: float = 1.0):
+    """scene.Disparity(data=disp_left, disp_sign="negative", occlusion=mask): `both_views`, then `lr_consistency`."""
+    from .scene import Disparity
+    dl, dr = both_views(forward, left, right)
+    mask = lr_consistency(dl, dr, threshold, "negative", "negative", right_flipped=True)
+    return Disparity(data=dl, disp_sign="negative", occlusion=mask)

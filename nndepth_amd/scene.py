@@ -9,7 +9,9 @@ The tail of every inference script of the reference,
 is written here without the `.cpu()`: the map stays where the model left it, the HIP kernels of csrc/scene.hip colour it, and
 the only device-to-host copy is the finished uint8 picture.  `get_view_tensor` returns that picture as a device tensor with no
 host synchronisation (what a serving loop chains after `GraphedForward`).  The resizes of the dataloaders (`interpolate`,
-`maxpool`, `minpool`) run on the device as well.  Nothing falls back to PyTorch: a CPU tensor is refused.
+`maxpool`, `minpool`) run on the device as well.  Nothing falls back to PyTorch: a CPU tensor is refused.  Beyond the reference:
+`Disparity.to_depth`, `Depth.to_disparity`, `Depth.to_points_map`, `Depth.points_tensor` and `Depth.to_points` consume the
+`baseline` and `Camera.intrinsic` the reference only stores (geometry.py, csrc/geometry.hip).
 
 Constructor arguments, attributes, method names, defaults and the ranks of what comes back are the reference's, its quirks
 included (Q9, the pooled occlusion of every batch element is gathered from plane 0; `resize` leaves `self.data`
@@ -229,6 +231,20 @@ class Disparity:
     get_view.__doc__ = get_view_tensor.__doc__ = """The coloured |disparity| (occluded pixels, occlusion == 1, at 0).
 """ + _VIEW_DOC
 
+    def to_depth(self, camera_or_fx, baseline: Optional[float] = None, min_disp: float = 0.0, max_depth: Optional[float] = None,
+                 valid_mask: Optional[torch.Tensor] = None) -> "Depth":
+        """Metric depth on the device (geometry.disparity_to_depth): z = fp32(double(fx) * double(baseline) / double(m)) with
+        m = -data for disp_sign "negative".  `camera_or_fx`: a Camera, an intrinsic tensor ((3,3) or (B,3,3)) or fx as a number;
+        `baseline` defaults to self.baseline.  The returned Depth carries valid_mask (uint8, 1 = valid): `valid_mask` given here
+        && isfinite(m) && m > min_disp && (max_depth is None || z <= max_depth); invalid pixels have depth 0.  (B,1,H,W) maps; not a
+        method of the reference."""
+        from . import geometry
+        baseline = self.baseline if baseline is None else baseline
+        if baseline is None:
+            raise NndError("Disparity.to_depth: no baseline: pass one, or construct the Disparity with its baseline")
+        depth, valid = geometry.disparity_to_depth(self.data, camera_or_fx, baseline, self.disp_sign, min_disp, max_depth, valid_mask)
+        return Depth(data=depth, valid_mask=valid)
+
 
 class Depth:
     def __init__(self, data: torch.Tensor, valid_mask: Optional[torch.Tensor] = None, is_inverse: bool = False):
@@ -287,6 +303,37 @@ class Depth:
     get_view.__doc__ = get_view_tensor.__doc__ = """The coloured depth; pixels with valid_mask != 1 take the smallest valid depth
         of their batch element (a batch element without a valid pixel raises in the reference and is outside the contract).
 """ + _VIEW_DOC
+
+    # ---- geometry on the device (geometry.py, csrc/geometry.hip); not methods of the reference
+    def to_disparity(self, camera_or_fx, baseline: float, disp_sign: Literal["negative", "positive"] = "negative",
+                     eps: float = 1e-8) -> Disparity:
+        """The reference's TartanAir line (tartanair_dataset.py:239-241) in its own fp32 order:
+        fp32(-baseline * fx) / (data + fp32(eps)), negated for "positive"; `baseline` is stored on the result."""
+        from . import geometry
+        disp = geometry.depth_to_disparity(self.data, camera_or_fx, baseline, disp_sign, eps)
+        return Disparity(data=disp, disp_sign=disp_sign, baseline=baseline)
+
+    def to_points_map(self, camera) -> torch.Tensor:
+        """(B,3,H,W): X = fp32((u - cx) * Z / fx), Y = fp32((v - cy) * Z / fy), arithmetic in double, Z copied;
+        pixels with valid_mask == 0 become 0."""
+        from . import geometry
+        return geometry.depth_to_points(self.data, camera, self.valid_mask)
+
+    def points_tensor(self, camera, features: Optional[torch.Tensor] = None):
+        """(points (B*H*W,3) fp32, feats (B*H*W,C) or None, offsets (B+1,) int64) on the device, no host synchronisation: the
+        valid points of sample b are rows offsets[b]:offsets[b+1] in row-major pixel order, `features` ((B,C,H,W) fp32, e.g.
+        the frame's colours) gathered into the same rows; rows past offsets[B] are unspecified.  Deterministic."""
+        from . import geometry
+        return geometry.points_compact(self.data, camera, self.valid_mask, features)
+
+    def to_points(self, camera, features: Optional[torch.Tensor] = None):
+        """`points_tensor`, then ONE host synchronisation to read `offsets`: a list of per-sample (n_b,3) views, or of
+        ((n_b,3), (n_b,C)) pairs when features are given."""
+        points, feats, offsets = self.points_tensor(camera, features)
+        off = offsets.tolist()
+        if feats is None:
+            return [points[off[b]:off[b + 1]] for b in range(len(off) - 1)]
+        return [(points[off[b]:off[b + 1]], feats[off[b]:off[b + 1]]) for b in range(len(off) - 1)]
 
 
 class Camera:
