@@ -835,6 +835,22 @@ int nnd_loftr_pack(int d_model, int nhead, const float* const* tensors_host, flo
 int nnd_loftr_layer_forward(int d_model, int nhead, const float* packed_dev, const float* x, const float* source, float* out,
                             float* workspace, int N, int H, int W, void* stream);
 
+/* ------------------------------------------------------------- LoFTR full (softmax) attention, opt-in (csrc/attention.hip)
+ * nnd_full_attention replaces FullAttention.forward  nndepth/blocks/attn_block.py:59-97  (no masks, no dropout), head
+ * dimension 32, on channel-major maps: q, out (N, nhead*32, L), k, v (N, nhead*32, S); L and S may differ:
+ *   out[n, 32h+d, l] = sum_s softmax_s( (sum_d q[n,32h+d,l] k[n,32h+d,s]) / sqrt(32) ) v[n,32h+d,s]
+ * Exact fp32 on the MFMA with an online softmax: the scores never reach memory; no atomics, one evaluation order, the same
+ * bits run to run.  q_bs / kv_bs / out_bs are batch strides in floats (>= nhead*32*L, nhead*32*S, nhead*32*L).
+ * nnd_loftr_full_layer_forward replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66  of a layer built
+ * with attention = "full" (transformer.py:9-27): nnd_loftr_layer_forward with the attention above in place of the linear
+ * one; same maps, same blob (nnd_loftr_pack: FullAttention has no parameters), its own workspace size
+ * nnd_loftr_full_workspace_floats = 6 * N * d_model * H * W.                                                              */
+int nnd_full_attention(const float* q, const float* k, const float* v, float* out, int N, int nhead, int L, int S, int64_t q_bs,
+                       int64_t kv_bs, int64_t out_bs, void* stream);
+int64_t nnd_loftr_full_workspace_floats(int d_model, int nhead, int N, int H, int W);
+int nnd_loftr_full_layer_forward(int d_model, int nhead, const float* packed_dev, const float* x, const float* source, float* out,
+                                 float* workspace, int N, int H, int W, void* stream);
+
 /* ------------------------------------------------------------- 3x3x3 Conv3d (IGEV cost-volume regulariser, row a15)
  * ConvBn3D / the conv of Upsampler3D:  nndepth/models/igev_stereo/cost_volume.py:101-130
  *   y = LeakyReLU_slope( BatchNorm3d_eval( conv3d(cat(x0, x1); w, stride, padding 1) + bias ) )        (norm / bias optional)

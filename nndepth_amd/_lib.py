@@ -233,6 +233,9 @@ SIGNATURES = {
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),
     "nnd_loftr_layer_forward": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_full_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "nnd_loftr_full_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
+    "nnd_loftr_full_layer_forward": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "nnd_conv3d_packed_floats": (C.c_int64, [C.POINTER(Conv3dDesc)]),
     "nnd_conv3d_pack": (_I, [C.POINTER(Conv3dDesc), _P, _P, _P, _P, _P, _P, C.c_float, _P]),
     "nnd_conv3d_forward": (_I, [C.POINTER(Conv3dDesc), _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, _P]),

@@ -33,12 +33,14 @@ from .upsample import convex_upsample
 
 # ------------------------------------------------------------------ adjacent PyTorch pieces (not the replaced path)
 class LoFTREncoderLayer(nn.Module):
-    """One LoFTR layer with linear attention (reference nndepth/blocks/transformer.py:8-66,
-    nndepth/blocks/attn_block.py:16-58); parameter names match the reference."""
+    """One LoFTR layer with linear or full (softmax) attention (reference nndepth/blocks/transformer.py:8-66,
+    nndepth/blocks/attn_block.py:16-97); parameter names match the reference and are the same for both kinds."""
 
-    def __init__(self, d_model: int, nhead: int):
+    def __init__(self, d_model: int, nhead: int, attention: str = "linear"):
         super().__init__()
-        self.dim, self.nhead = d_model // nhead, nhead
+        if attention not in ("linear", "full"):
+            raise ValueError(f"attention {attention!r}: the reference's layer has 'linear' and 'full'")
+        self.dim, self.nhead, self.attention = d_model // nhead, nhead, attention
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
         self.v_proj = nn.Linear(d_model, d_model, bias=False)
@@ -48,15 +50,22 @@ class LoFTREncoderLayer(nn.Module):
         self.norm1 = nn.LayerNorm(d_model)
         self.norm2 = nn.LayerNorm(d_model)
 
-    def forward(self, x: torch.Tensor, source: torch.Tensor) -> torch.Tensor:
-        n = x.size(0)
-        q = F.elu(self.q_proj(x).view(n, -1, self.nhead, self.dim)) + 1
-        k = F.elu(self.k_proj(source).view(n, -1, self.nhead, self.dim)) + 1
-        v = self.v_proj(source).view(n, -1, self.nhead, self.dim)
-        s = v.size(1)
+    def _attend(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """(N, L, H, D), (N, S, H, D) x 2 -> (N, L, H, D)."""
+        if self.attention == "full":  # attn_block.py:59-97 without masks and dropout
+            a = torch.softmax(torch.einsum("nlhd,nshd->nlsh", q, k) * (1.0 / q.size(3) ** 0.5), dim=2)
+            return torch.einsum("nlsh,nshd->nlhd", a, v)
+        q, k, s = F.elu(q) + 1, F.elu(k) + 1, v.size(1)
         kv = torch.einsum("nshd,nshv->nhdv", k, v / s)
         z = 1 / (torch.einsum("nlhd,nhd->nlh", q, k.sum(dim=1)) + 1e-6)
-        msg = (torch.einsum("nlhd,nhdv,nlh->nlhv", q, kv, z) * s).reshape(n, -1, self.nhead * self.dim)
+        return torch.einsum("nlhd,nhdv,nlh->nlhv", q, kv, z) * s
+
+    def forward(self, x: torch.Tensor, source: torch.Tensor) -> torch.Tensor:
+        n = x.size(0)
+        q = self.q_proj(x).view(n, -1, self.nhead, self.dim)
+        k = self.k_proj(source).view(n, -1, self.nhead, self.dim)
+        v = self.v_proj(source).view(n, -1, self.nhead, self.dim)
+        msg = self._attend(q, k, v).reshape(n, -1, self.nhead * self.dim)
         msg = self.norm1(self.merge(msg))
         msg = self.norm2(self.mlp(torch.cat([x, msg], dim=2)))
         return x + msg
@@ -65,14 +74,15 @@ class LoFTREncoderLayer(nn.Module):
 class LocalFeatureTransformer(nn.Module):
     """`forward(feat0, feat1)` takes (N, L, C) tokens like the reference (PyTorch path).  `forward_maps(map0, map1)` is the
     same computation on (N, C, H, W) maps — the tokens transposed — and runs in HIP (csrc/loftr.hip: every Linear is a 1x1
-    conv of the map, the linear attention and the LayerNorms are small kernels); CREStereoBase and AGCL use it on the GPU."""
+    conv of the map, the linear attention and the LayerNorms are small kernels; attention = "full" runs the softmax attention
+    of csrc/attention.hip in its place); CREStereoBase and AGCL use it on the GPU."""
 
     def __init__(self, d_model: int, nhead: int, layer_names, attention: str = "linear"):
         super().__init__()
-        if attention != "linear":
-            raise ValueError("only the linear attention of CREStereo is provided")
-        self.d_model, self.nhead, self.layer_names = d_model, nhead, list(layer_names)
-        self.layers = nn.ModuleList([LoFTREncoderLayer(d_model, nhead) for _ in self.layer_names])
+        if attention not in ("linear", "full"):
+            raise ValueError(f"attention {attention!r}: the reference's transformer has 'linear' and 'full'")
+        self.d_model, self.nhead, self.layer_names, self.attention = d_model, nhead, list(layer_names), attention
+        self.layers = nn.ModuleList([LoFTREncoderLayer(d_model, nhead, attention) for _ in self.layer_names])
         self._engines = ops.ParamCache()
 
     def _layer_step(self, run, feat0, feat1):
@@ -98,7 +108,7 @@ class LocalFeatureTransformer(nn.Module):
             a, b = self.forward(map0.permute(0, 2, 3, 1).reshape(n, h * w, c), map1.permute(0, 2, 3, 1).reshape(n, h * w, c))
             return a.reshape(n, h, w, c).permute(0, 3, 1, 2), b.reshape(n, h, w, c).permute(0, 3, 1, 2)
         engines = self._engines.get((self,), map0.device, lambda: [
-            ops.LoftrEngine(self.d_model, self.nhead).load(layer.state_dict(), device=map0.device) for layer in self.layers])
+            ops.LoftrEngine(self.d_model, self.nhead, self.attention).load(layer.state_dict(), device=map0.device) for layer in self.layers])
         return self._layer_step(lambda i, a, b: engines[i].forward(a.float(), b.float()), map0, map1)
 
 
@@ -108,8 +118,10 @@ class CREStereoBase(AutoCalibrate, nn.Module):
                  max_disp: int = 192, num_fnet_channels: int = 256, hidden_dim: int = 128, context_dim: int = 128,
                  search_num: int = 9, mixed_precision: bool = False, test_mode: bool = False, tracing: bool = False,
                  include_preprocessing: bool = False, weights: Optional[str] = None, strict_load: bool = True,
-                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", **kwargs):
+                 fused_loop: bool = True, hip_encoder: bool = True, arithmetic: str = "fp16x2", outputs: str = "all", attention: str = "linear",
+                 **kwargs):
         super().__init__()
+        self.attention = attention  # self / cross attention of the 1/32 stage: "linear" (the reference model's) or "full" (softmax, opt-in); same parameters
         self.arithmetic = arithmetic  # update-block / encoder convolutions: "fp16x2" (default; 2 fp16 pieces, parity-gated), "bf16x3" (3 bf16 pieces), "fp32" (exact fp32 MFMA) or "fp16" (opt-in: ONE range-scaled fp16 piece, 11 significand bits, finite up to 32 x the calibrated maximum)
         # "all": every iteration's up_disp; "last": [{"up_disp": final}] (raft_stereo.check_outputs).  test_mode (the reference's switch,
         # returns the final flow tensor) runs last-only as well
@@ -130,8 +142,8 @@ class CREStereoBase(AutoCalibrate, nn.Module):
         self.fnet_ds = 8
         self.update_block = BasicUpdateBlock(hidden_dim=hidden_dim, cor_planes=4 * 9, flow_channel=2,
                                              context_dim=context_dim, spatial_scale=self.fnet_ds, arithmetic=arithmetic)
-        self.self_att_fn = LocalFeatureTransformer(num_fnet_channels, 8, ["self"], "linear")
-        self.cross_att_fn = LocalFeatureTransformer(num_fnet_channels, 8, ["cross"], "linear")
+        self.self_att_fn = LocalFeatureTransformer(num_fnet_channels, 8, ["self"], attention)
+        self.cross_att_fn = LocalFeatureTransformer(num_fnet_channels, 8, ["cross"], attention)
         self.conv_offset_16 = nn.Conv2d(num_fnet_channels, 2 * search_num, 3, padding=1)
         self.conv_offset_8 = nn.Conv2d(num_fnet_channels, 2 * search_num, 3, padding=1)
         self.range_16 = self.range_8 = 1

@@ -194,6 +194,54 @@ static int run_lin(const ConvLayer& L, const float* base, const float* x0, int c
     return launch_conv(L, base, io, relu ? EPI_RELU : EPI_LINEAR, N, H, W, s);
 }
 
+// The layer with either attention: `full` replaces the three linear-attention launches by nnd_full_attention (attention.hip);
+// the projections, the merge, the MLP and the two LayerNorms are the same launches on the same workspace slots.
+static int loftr_layer(bool full, int d_model, int nhead, const float* packed, const float* x, const float* source, float* out,
+                       float* workspace, int N, int H, int W, void* stream) {
+    LoftrPlan p;
+    int rc = make_loftr_plan(d_model, nhead, &p);
+    if (rc != NND_OK) return rc;
+    NND_REQUIRE(packed && x && source && out && workspace && N > 0 && H > 0 && W > 0, "loftr_layer_forward: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int C = d_model, L = H * W;
+    const int64_t bs = (int64_t)C * L, map = (int64_t)N * bs;
+    float* q = workspace;
+    float* k = q + map;
+    float* v = k + map;
+    float* msg = v + map;
+    float* t = msg + map;  // 2 maps wide
+    NND_TRY(run_lin(p.q, packed + p.bq, x, C, nullptr, 0, bs, 0, q, bs, false, N, H, W, s));
+    NND_TRY(run_lin(p.k, packed + p.bk, source, C, nullptr, 0, bs, 0, k, bs, false, N, H, W, s));
+    NND_TRY(run_lin(p.v, packed + p.bv, source, C, nullptr, 0, bs, 0, v, bs, false, N, H, W, s));
+    if (full) {
+        NND_TRY(nnd_full_attention(q, k, v, msg, N, nhead, L, L, bs, bs, bs, stream));
+    } else {
+        const int nchunks = (int)cdiv64(L, KV_PIX);
+        float* partial = t + 2 * map;
+        float* kv = partial + (int64_t)N * nhead * nchunks * (32 * 32 + 32);
+        hipLaunchKernelGGL(attn_kv_partial_kernel, dim3(nchunks, nhead, N), dim3(256), 0, s, k, v, (long)bs, L, 1.0f / (float)L,
+                           partial, nchunks);
+        NND_LAUNCH_CHECK();
+        hipLaunchKernelGGL(attn_kv_final_kernel, dim3(nhead, N), dim3(256), 0, s, (const float*)partial, nchunks, kv);
+        NND_LAUNCH_CHECK();
+        hipLaunchKernelGGL(attn_msg_kernel, dim3(cdiv(L, 256), nhead, N), dim3(256), 0, s, q, (long)bs, (const float*)kv, L, (float)L,
+                           1e-6f, msg, (long)bs);
+        NND_LAUNCH_CHECK();
+    }
+    // merge + norm1 (q is free again: holds the merged message, then its normalised version in place)
+    NND_TRY(run_lin(p.merge, packed + p.bm, msg, C, nullptr, 0, bs, 0, q, bs, false, N, H, W, s));
+    hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(L, 32), N), dim3(256), 0, s, (const float*)q, (long)bs, packed + p.ln1,
+                       packed + p.ln1 + C, (const float*)nullptr, 0L, q, (long)bs, C, L, 1e-5f);
+    NND_LAUNCH_CHECK();
+    // mlp on the virtual concat [x | message]
+    NND_TRY(run_lin(p.mlp0, packed + p.b0, x, C, q, C, bs, bs, t, 2 * bs, true, N, H, W, s));
+    NND_TRY(run_lin(p.mlp2, packed + p.b2, t, 2 * C, nullptr, 0, 2 * bs, 0, k, bs, false, N, H, W, s));
+    hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(L, 32), N), dim3(256), 0, s, (const float*)k, (long)bs, packed + p.ln2,
+                       packed + p.ln2 + C, x, (long)bs, out, (long)bs, C, L, 1e-5f);
+    NND_LAUNCH_CHECK();
+    return NND_OK;
+}
+
 }  // namespace nnd
 
 using namespace nnd;
@@ -242,44 +290,19 @@ int nnd_loftr_pack(int d_model, int nhead, const float* const* t, float* packed_
 // x, source, out: (N, d_model, H, W) maps (= the reference's (N, H*W, C) tokens, transposed); out may alias neither input.
 int nnd_loftr_layer_forward(int d_model, int nhead, const float* packed, const float* x, const float* source, float* out,
                             float* workspace, int N, int H, int W, void* stream) {
+    return loftr_layer(false, d_model, nhead, packed, x, source, out, workspace, N, H, W, stream);
+}
+
+// the full-attention layer needs no reduction partials: floats = q, k, v, msg and the 2C-wide mlp hidden map
+int64_t nnd_loftr_full_workspace_floats(int d_model, int nhead, int N, int H, int W) {
     LoftrPlan p;
-    int rc = make_loftr_plan(d_model, nhead, &p);
-    if (rc != NND_OK) return rc;
-    NND_REQUIRE(packed && x && source && out && workspace && N > 0 && H > 0 && W > 0, "loftr_layer_forward: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int C = d_model, L = H * W;
-    const int64_t bs = (int64_t)C * L, map = (int64_t)N * bs;
-    float* q = workspace;
-    float* k = q + map;
-    float* v = k + map;
-    float* msg = v + map;
-    float* t = msg + map;  // 2 maps wide
-    const int nchunks = (int)cdiv64(L, KV_PIX);
-    float* partial = t + 2 * map;
-    float* kv = partial + (int64_t)N * nhead * nchunks * (32 * 32 + 32);
-    NND_TRY(run_lin(p.q, packed + p.bq, x, C, nullptr, 0, bs, 0, q, bs, false, N, H, W, s));
-    NND_TRY(run_lin(p.k, packed + p.bk, source, C, nullptr, 0, bs, 0, k, bs, false, N, H, W, s));
-    NND_TRY(run_lin(p.v, packed + p.bv, source, C, nullptr, 0, bs, 0, v, bs, false, N, H, W, s));
-    hipLaunchKernelGGL(attn_kv_partial_kernel, dim3(nchunks, nhead, N), dim3(256), 0, s, k, v, (long)bs, L, 1.0f / (float)L, partial,
-                       nchunks);
-    NND_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_kv_final_kernel, dim3(nhead, N), dim3(256), 0, s, (const float*)partial, nchunks, kv);
-    NND_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_msg_kernel, dim3(cdiv(L, 256), nhead, N), dim3(256), 0, s, q, (long)bs, (const float*)kv, L, (float)L, 1e-6f,
-                       msg, (long)bs);
-    NND_LAUNCH_CHECK();
-    // merge + norm1 (q is free again: holds the merged message, then its normalised version in place)
-    NND_TRY(run_lin(p.merge, packed + p.bm, msg, C, nullptr, 0, bs, 0, q, bs, false, N, H, W, s));
-    hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(L, 32), N), dim3(256), 0, s, (const float*)q, (long)bs, packed + p.ln1,
-                       packed + p.ln1 + C, (const float*)nullptr, 0L, q, (long)bs, C, L, 1e-5f);
-    NND_LAUNCH_CHECK();
-    // mlp on the virtual concat [x | message]
-    NND_TRY(run_lin(p.mlp0, packed + p.b0, x, C, q, C, bs, bs, t, 2 * bs, true, N, H, W, s));
-    NND_TRY(run_lin(p.mlp2, packed + p.b2, t, 2 * C, nullptr, 0, 2 * bs, 0, k, bs, false, N, H, W, s));
-    hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(L, 32), N), dim3(256), 0, s, (const float*)k, (long)bs, packed + p.ln2,
-                       packed + p.ln2 + C, x, (long)bs, out, (long)bs, C, L, 1e-5f);
-    NND_LAUNCH_CHECK();
-    return NND_OK;
+    if (make_loftr_plan(d_model, nhead, &p) != NND_OK || N <= 0 || H <= 0 || W <= 0) return NND_ERR_INVALID;
+    return 6 * (int64_t)N * d_model * H * W;
+}
+
+int nnd_loftr_full_layer_forward(int d_model, int nhead, const float* packed, const float* x, const float* source, float* out,
+                                 float* workspace, int N, int H, int W, void* stream) {
+    return loftr_layer(true, d_model, nhead, packed, x, source, out, workspace, N, H, W, stream);
 }
 
 }  // extern "C"

@@ -1846,11 +1846,31 @@ LOFTR_KEYS = ("q_proj.weight", "k_proj.weight", "v_proj.weight", "merge.weight",
               "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
 
 
-class LoftrEngine:
-    """One LoFTR encoder layer (linear attention) on (N, d_model, H, W) maps (csrc/loftr.hip)."""
+def full_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, nhead: int) -> torch.Tensor:
+    """Softmax attention with 32 channels per head on channel-major maps (csrc/attention.hip; reference FullAttention,
+    nndepth/blocks/attn_block.py:59-97, no masks): q (N, nhead*32, L), k and v (N, nhead*32, S) -> (N, nhead*32, L)."""
+    d = _dev(q, k, v)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or k.shape[:2] != q.shape[:2] or q.shape[1] != 32 * int(nhead):
+        raise NndError(f"full_attention: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} must be (N, {32 * int(nhead)}, L) "
+                       f"and twice (N, {32 * int(nhead)}, S)")
+    N, Cc, L = q.shape
+    S = k.shape[2]
+    out = torch.empty_like(q)
+    with torch.cuda.device(d):
+        check(lib.nnd_full_attention(_p(q), _p(k), _p(v), _p(out), N, int(nhead), L, S, Cc * L, Cc * S, Cc * L, _stream(d)),
+              "full_attention")
+    return out
 
-    def __init__(self, d_model: int, nhead: int):
-        self.d_model, self.nhead = int(d_model), int(nhead)
+
+class LoftrEngine:
+    """One LoFTR encoder layer on (N, d_model, H, W) maps (csrc/loftr.hip): attention = "linear" (the elu feature map) or
+    "full" (softmax, csrc/attention.hip).  Both kinds pack the same blob: the attention has no parameters."""
+
+    def __init__(self, d_model: int, nhead: int, attention: str = "linear"):
+        if attention not in ("linear", "full"):
+            raise NndError(f"LoftrEngine: attention {attention!r} is neither 'linear' nor 'full'")
+        self.d_model, self.nhead, self.attention = int(d_model), int(nhead), attention
         n = int(lib.nnd_loftr_packed_floats(self.d_model, self.nhead))
         if n <= 0:
             check(n, "loftr_packed_floats")
@@ -1874,13 +1894,16 @@ class LoftrEngine:
         N, Cc, H, W = x.shape
         if Cc != self.d_model or source.shape != x.shape:
             raise NndError(f"loftr: x {tuple(x.shape)} / source {tuple(source.shape)} must both be (N, {self.d_model}, H, W)")
-        need = int(lib.nnd_loftr_workspace_floats(self.d_model, self.nhead, N, H, W))
+        full = self.attention == "full"
+        ws_floats, run = ((lib.nnd_loftr_full_workspace_floats, lib.nnd_loftr_full_layer_forward) if full else
+                          (lib.nnd_loftr_workspace_floats, lib.nnd_loftr_layer_forward))
+        need = int(ws_floats(self.d_model, self.nhead, N, H, W))
         if self._ws is None or self._ws.numel() < need or self._ws.device != d:
             self._ws = torch.empty(need, dtype=torch.float32, device=d)
         out = torch.empty_like(x)
         with torch.cuda.device(d):
-            check(lib.nnd_loftr_layer_forward(self.d_model, self.nhead, _p(self.packed), _p(x), _p(source), _p(out), _p(self._ws),
-                                              N, H, W, _stream(d)), "loftr_layer_forward")
+            check(run(self.d_model, self.nhead, _p(self.packed), _p(x), _p(source), _p(out), _p(self._ws), N, H, W, _stream(d)),
+                  "loftr_full_layer_forward" if full else "loftr_layer_forward")
         return out
 
 
