@@ -10,6 +10,7 @@
 //       y  = ReLU(norm1(conv1 3x3 (stride s)(x)))        EPI_AFFINE | relu
 //       sc = norm3(conv 1x1 (stride s)(x))               EPI_AFFINE
 //       x' = ReLU(sc + ReLU(norm2(conv2 3x3(y))))        EPI_AFFINE | relu | residual | relu
+//     (layer1.0 / layer1.1 in fp16x2 / fp16 with a folded or no norm: the three as ONE launch, enc_block.hip — the same bits)
 //   conv2 1x1 (128 -> output_dim)                    conv_mfma, writes the NCHW result
 //   cnet_proj 3x3 (output_dim -> ctx + hid) + ReLU   conv_mfma on the first half of the batch (the left frames)
 //
@@ -726,7 +727,13 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed, cons
         float* y = buf[(cur + 1) & 3];
         float* sc = buf[(cur + 2) & 3];
         float* o = buf[(cur + 3) & 3];
-        if (!inorm) {
+        // A stride-1 64 -> 64 block in fp16x2 / fp16 (layer1.0, layer1.1) is ONE launch (enc_block.hip): y and the shortcut stay on the
+        // chip, the same bits.  A calibrating call keeps the three launches: conv2's range is recorded from the y it stages.
+        // NND_NO_FUSED_ENC_BLOCK: the three launches always.
+        const bool fused = !inorm && c4 && st == 1 && !calibrating() && !switches().no_fused_enc_block && enc_block_supported(p.c1[i], p.c2[i], p.ds[i]);
+        if (fused) {
+            NND_TRY(enc_block_launch(p.c1[i], packed + p.base1[i], p.c2[i], packed + p.base2[i], p.ds[i], packed + p.based[i], x, o, N, h, w, s));
+        } else if (!inorm) {
             NND_TRY(run_conv_norm(p.c1[i], packed + p.base1[i], x, cin * pin, true, nullptr, 0, y, dim * pout, true, 1, N, h, w, s, c4, c4));
             NND_TRY(run_conv_norm(p.ds[i], packed + p.based[i], x, cin * pin, true, nullptr, 0, sc, dim * pout, true, 0, N, h, w, s, c4, c4));
             NND_TRY(run_conv_norm(p.c2[i], packed + p.base2[i], y, dim * pout, true, sc, dim * pout, o, dim * pout, true, 3, N, ho, wo, s, c4, c4));

@@ -44,6 +44,7 @@ static void load_switches() {
     s.enc_no_c4 = on("NND_ENC_NO_C4");
     s.no_slab3d = on("NND_NO_SLAB3D");
     s.slab3d_rounds = getenv("NND_SLAB3D_ROUNDS") ? atoi(getenv("NND_SLAB3D_ROUNDS")) : 0;
+    s.no_fused_enc_block = on("NND_NO_FUSED_ENC_BLOCK");
     g_sw = s;
 }
 namespace {
