@@ -33,7 +33,7 @@
  *     arithmetic = 2 through the round-2 formulations instead of the depth-marching MFMA kernel csrc/slab3d.hip),
  *     NND_SLAB3D_ROUNDS (depth segments of that kernel: grid of about this many resident sets), NND_NO_C4 (planar instead of 4-channel-
  *     interleaved layout of the update block's conv-only workspace tensors), NND_ENC_NO_C4 (the same for the encoder's activations
- *     with a split arithmetic), NND_NO_FUSED_ENC_BLOCK (the encoder's stride-1 64 -> 64 residual blocks as conv1, shortcut and
+ *     with a split arithmetic), NND_NO_FUSED_ENC_BLOCK (the encoder's layer1 and layer2 residual blocks as conv1, shortcut and
  *     conv2 + add launches instead of the one launch of csrc/enc_block.hip).
  */
 #ifndef NNDEPTH_AMD_H

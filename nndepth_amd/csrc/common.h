@@ -70,7 +70,7 @@ struct Switches {
     bool enc_no_c4;                   // NND_ENC_NO_C4: the encoder's activations planar tile-major also with a split arithmetic
     bool no_slab3d;                   // NND_NO_SLAB3D: thin Conv3d layers on the round-2 formulations (conv_split / thin3d)
     int slab3d_rounds;                // NND_SLAB3D_ROUNDS: depth segments so that the grid is about this many resident sets
-    bool no_fused_enc_block;          // NND_NO_FUSED_ENC_BLOCK: the encoder's stride-1 64 -> 64 residual blocks as three launches each
+    bool no_fused_enc_block;          // NND_NO_FUSED_ENC_BLOCK: the encoder's residual blocks of layer1 and layer2 as three launches each
 };
 const Switches& switches();
 
@@ -229,6 +229,8 @@ void pack_conv(const ConvLayer& L, int nparts, const float* const* w, const floa
 // launch_conv / pack_conv dispatch to these.
 bool conv_split_supported(int KH, int KW, int Cin, int stride, int arith, int Cout = 0);  // Cout matters for stride 2 only
 int launch_conv_split(const ConvLayer& L, const float* blob, const ConvIO& io, int epi, int B, int H, int W, hipStream_t stream);
+// the plan launch_conv_split would pick for L on one source at (B, H, W) output pixels has ks == 1 (no split K)
+bool conv_split_no_split_k(const ConvLayer& L, int B, int H, int W);
 // motion encoder flow branch in one launch (conv_split.hip): f2 = convf2's split-packed layer, w7t = convf1's weights tap-major
 // ([fc*49][128]), b7 its bias
 bool flow_branch_supported(const ConvLayer& f2, int fc);
@@ -237,11 +239,13 @@ int launch_flow_branch(const ConvLayer& f2, const float* blob, const float* w7t,
 void pack_conv_split(const ConvLayer& L, int nparts, const float* const* w, const float* const* b, const int* cout, float* blob,
                      const int* ci_map, int cin_src);
 
-// enc_block.hip: a stride-1 residual block of the encoder's first stage (conv1 3x3 -> ReLU -> conv2 3x3, + the 1x1 shortcut) as one
-// launch that computes the bits of the three launches it replaces; x / out: (N, 64, H, W) tile-major, 4 channels interleaved
+// enc_block.hip: a residual block of the encoder's first two stages (conv1 3x3 -> ReLU -> conv2 3x3, + the 1x1 shortcut; 64 -> 64:
+// layer1.0 / layer1.1, 64 -> 96 with stride 2: layer2.0, 96 -> 96: layer2.1) as one launch that computes the bits of the three
+// launches it replaces where those run without split K; x: (N, Cin, Hx, Wx), out: (N, Cout, Hx / stride, Wx / stride) rounded up,
+// tile-major, 4 channels interleaved
 bool enc_block_supported(const ConvLayer& c1, const ConvLayer& c2, const ConvLayer& ds);
 int enc_block_launch(const ConvLayer& c1, const float* blob1, const ConvLayer& c2, const float* blob2, const ConvLayer& ds, const float* blobd,
-                     const float* x, float* out, int N, int H, int W, hipStream_t stream);
+                     const float* x, float* out, int N, int Hx, int Wx, hipStream_t stream);
 
 // thin3d.hip: direct fp32 VALU Conv3d for the regulariser's 8- / 16-output-channel layers (depth-major volumes)
 bool thin3d_supported(int Cout, int stride);

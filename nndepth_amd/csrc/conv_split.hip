@@ -195,6 +195,12 @@ void print_split_plan(const ConvLayer& L, const ConvIO& io, const SplitCfg& cfg)
 }
 }  // namespace
 
+// Would a launch of L on one source at (B, H, W) run without split K?  The picker's own answer (enc_block.hip reproduces that K order).
+bool conv_split_no_split_k(const ConvLayer& L, int B, int H, int W) {
+    SplitCfg cfg;
+    return pick_split(L, L.Cin, 0, B, H, W, split_fast_ok(L), &cfg) && cfg.ks == 1;
+}
+
 // the kernel instantiations live in conv_split_ns1.hip / conv_split_ns2.hip / conv_split_ns3.hip
 extern template int launch_split_ns<1>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);
 extern template int launch_split_ns<2>(const ConvArgs&, const SplitCfg&, int, int, hipStream_t);

@@ -10,7 +10,8 @@
 //       y  = ReLU(norm1(conv1 3x3 (stride s)(x)))        EPI_AFFINE | relu
 //       sc = norm3(conv 1x1 (stride s)(x))               EPI_AFFINE
 //       x' = ReLU(sc + ReLU(norm2(conv2 3x3(y))))        EPI_AFFINE | relu | residual | relu
-//     (layer1.0 / layer1.1 in fp16x2 / fp16 with a folded or no norm: the three as ONE launch, enc_block.hip — the same bits)
+//     (layer1 and layer2 in fp16x2 / fp16 with a folded or no norm: the three as ONE launch, enc_block.hip — the same bits;
+//      layer2 only where its 96 -> 96 launches would run without split K)
 //   conv2 1x1 (128 -> output_dim)                    conv_mfma, writes the NCHW result
 //   cnet_proj 3x3 (output_dim -> ctx + hid) + ReLU   conv_mfma on the first half of the batch (the left frames)
 //
@@ -727,10 +728,14 @@ int nnd_encoder_forward2(const nnd_encoder_desc* desc, const float* packed, cons
         float* y = buf[(cur + 1) & 3];
         float* sc = buf[(cur + 2) & 3];
         float* o = buf[(cur + 3) & 3];
-        // A stride-1 64 -> 64 block in fp16x2 / fp16 (layer1.0, layer1.1) is ONE launch (enc_block.hip): y and the shortcut stay on the
-        // chip, the same bits.  A calibrating call keeps the three launches: conv2's range is recorded from the y it stages.
-        // NND_NO_FUSED_ENC_BLOCK: the three launches always.
-        const bool fused = !inorm && c4 && st == 1 && !calibrating() && !switches().no_fused_enc_block && enc_block_supported(p.c1[i], p.c2[i], p.ds[i]);
+        // A block of layer1 or layer2 in fp16x2 / fp16 (64 -> 64, 64 -> 96 with stride 2, 96 -> 96) is ONE launch (enc_block.hip): y and
+        // the shortcut stay on the chip, the same bits.  The block sums over K in conv_split's order without split K, so it is taken
+        // only where the picker gives every split-arithmetic launch of the block that plan at this shape (64 input channels:
+        // always; 96: from about 512 workgroup columns).  A calibrating call keeps the three launches: the ranges are recorded from
+        // what each launch stages.  NND_NO_FUSED_ENC_BLOCK: the three launches always.
+        const bool fused = !inorm && c4 && !calibrating() && !switches().no_fused_enc_block && enc_block_supported(p.c1[i], p.c2[i], p.ds[i]) &&
+                           conv_split_no_split_k(p.c1[i], N, ho, wo) && conv_split_no_split_k(p.c2[i], N, ho, wo) &&
+                           (p.ds[i].arith == 0 || conv_split_no_split_k(p.ds[i], N, ho, wo));
         if (fused) {
             NND_TRY(enc_block_launch(p.c1[i], packed + p.base1[i], p.c2[i], packed + p.base2[i], p.ds[i], packed + p.based[i], x, o, N, h, w, s));
         } else if (!inorm) {
