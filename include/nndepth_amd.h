@@ -824,6 +824,42 @@ int nnd_lr_consistency(const float* disp_left, int64_t left_bstride, const float
 int nnd_pair_both_views(const float* left, const float* right, float* frames1, float* frames2, int B, int C, int H, int W,
                         void* stream);
 
+/* ------------------------------------------------------------- connected regions and the speckle filter (additions within 105)
+ * The step after the left-right check: small connected patches whose values hang together but do not belong to the surface around
+ * them are removed on the device (csrc/speckle.hip).  Beyond the reference, which has no such step; the shape of OpenCV's
+ * filterSpeckles, on fp32 with a mask (no parity with it is claimed).  Maps, strides and masks as above; per sample:
+ *   valid[p]   = (mask == NULL || (mask[p] != 0) == (mask_valid_is_one != 0)) && isfinite(d[p])
+ *                (mask_valid_is_one == 0: the mask is an occlusion mask, 1 = invalid; != 0: a valid mask, 1 = valid)
+ *   p ~ q      for neighbours p, q: both valid && fabsf(d[p] - d[q]) <= max_diff, ONE rounded fp32 subtraction (so a difference
+ *                equal to max_diff joins, -0.0 joins 0.0, and with max_diff = +inf an overflowing difference joins too).
+ *                Neighbours: left / right / up / down (connectivity 4), and the four diagonals as well (8); a diagonal edge
+ *                depends on its own two pixels only.
+ *   regions    = the connected components of that graph (the relation is not transitive in value: a ramp of step max_diff is one).
+ *   labels[p]  = the smallest row-major index y*W + x of p's region; -1 where !valid[p]
+ *   sizes[p]   = the number of pixels of p's region; 0 where !valid[p]
+ *   speckle[p] = valid[p] && sizes[p] <= max_size
+ *   filtered[p] = speckle[p] ? fill : d[p]     (every other pixel copied bit for bit, invalid ones and NaNs included)
+ *   mask_out[p] = in the polarity of mask_valid_is_one: invalid = !valid[p] || speckle[p]  (0: 1 = invalid; != 0: 1 = valid).  A
+ *                non-finite pixel counts as invalid here, as it does in valid[p].
+ *   speckle_out[p] = speckle[p] (0 / 1)
+ * nnd_connected_regions writes labels and / or sizes ((B,H,W) int32, either may be NULL, not both); nnd_speckle_filter is
+ * regions + apply in one enqueue: filtered, mask_out, speckle_out (one of them at least) and sizes are optional.  Both enqueue the
+ * same four launches whatever the data: the call neither synchronises nor reads anything back, and can be captured into a graph.
+ * Only integer atomics (min, add): the same bytes on every run; nothing depends on what the workspace or the outputs held.
+ * `workspace` = nnd_connected_regions_workspace_bytes(B,H,W) device bytes (9 per pixel, rounded up), 8-byte aligned, the
+ * caller's.  Refused before any HIP call: a null map / workspace / no output, B, H, W out of range (1 <= B <= 65535,
+ * H*W < 2^31), a batch stride below H*W, max_diff negative or NaN, connectivity other than 4 or 8, max_size < 0, a workspace too
+ * small or misaligned.  nnd_connected_regions_tile: height (which = 0) / width (1) of the tile one workgroup labels in LDS.      */
+int64_t nnd_connected_regions_workspace_bytes(int B, int H, int W);
+int nnd_connected_regions_tile(int which);
+int nnd_connected_regions(const float* map, int64_t map_bstride, const unsigned char* mask, int mask_valid_is_one, float max_diff,
+                          int connectivity, int32_t* labels, int32_t* sizes, void* workspace, int64_t workspace_bytes, int B, int H,
+                          int W, void* stream);
+int nnd_speckle_filter(const float* map, int64_t map_bstride, const unsigned char* mask, int mask_valid_is_one, float max_diff,
+                       int connectivity, int max_size, float fill, float* filtered, unsigned char* mask_out,
+                       unsigned char* speckle_out, int32_t* sizes, void* workspace, int64_t workspace_bytes, int B, int H, int W,
+                       void* stream);
+
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58
  * (no masks).  The reference's (N, H*W, C) tokens are the (N,C,H,W) maps transposed, so every nn.Linear is a 1x1 conv of

@@ -229,6 +229,10 @@ SIGNATURES = {
     "nnd_points_compact": (_I, [_P, C.c_int64, _P, _P, _I, _P, _I, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
     "nnd_lr_consistency": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _I, _I, C.c_float, _P, _P, _I, _I, _I, _P]),
     "nnd_pair_both_views": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "nnd_connected_regions_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "nnd_connected_regions_tile": (_I, [_I]),
+    "nnd_connected_regions": (_I, [_P, C.c_int64, _P, _I, C.c_float, _I, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
+    "nnd_speckle_filter": (_I, [_P, C.c_int64, _P, _I, C.c_float, _I, _I, C.c_float, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
     "nnd_loftr_packed_floats": (C.c_int64, [_I, _I]),
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),

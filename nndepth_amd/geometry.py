@@ -8,6 +8,7 @@ Here:
     disparity_to_depth / depth_to_disparity    (Disparity.to_depth, Depth.to_disparity of scene.py)
     depth_to_points / points_compact           (Depth.to_points_map, Depth.points_tensor, Depth.to_points)
     lr_consistency, both_views, occlusion      a left-right check of a PREDICTED map -> an occlusion mask, 1 = occluded
+    connected_regions, speckle_mask, speckle_filter    (csrc/speckle.hip; Disparity.remove_speckles, Depth.remove_speckles)
 
 Maps are (B,1,H,W) fp32 on the HIP device; a batch stride is read where it lies (a channel slice of CREStereo's 2-channel
 output, half of a stacked batch).  Masks are torch.bool or torch.uint8, (B,1,H,W) or (B,H,W).  Camera values come from
@@ -193,6 +194,101 @@ def lr_consistency(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold:
         check(lib.nnd_lr_consistency(_p(dl), _bstride(dl), _p(dr), _bstride(dr), nl, nr, int(bool(right_flipped)), float(threshold),
                                      _p(occ), _p(err), B, H, W, _stream(dl.device)), what)
     return (occ, err) if return_error else occ
+
+
+def _regions_workspace(d: torch.Tensor, workspace: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    B, _, H, W = d.shape
+    nbytes = int(lib.nnd_connected_regions_workspace_bytes(B, H, W))
+    if nbytes < 0:
+        check(nbytes, what)
+    if workspace is None:
+        return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=d.device)
+    if not torch.is_tensor(workspace) or workspace.device != d.device or not workspace.is_contiguous():
+        raise NndError(f"{what}: the workspace must be a contiguous tensor on {d.device}")
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise NndError(f"{what}: a workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed "
+                       "(regions_workspace_bytes)")
+    return workspace
+
+
+def regions_workspace_bytes(B: int, H: int, W: int) -> int:
+    """Device bytes `connected_regions` / `speckle_filter` need for a (B,1,H,W) map (9 per pixel); 8-byte aligned."""
+    nbytes = int(lib.nnd_connected_regions_workspace_bytes(int(B), int(H), int(W)))
+    if nbytes < 0:
+        check(nbytes, "regions_workspace_bytes")
+    return nbytes
+
+
+def regions_tile() -> Tuple[int, int]:
+    """(height, width) of the tile one workgroup labels on chip; regions that cross its borders are merged in a second launch."""
+    return int(lib.nnd_connected_regions_tile(0)), int(lib.nnd_connected_regions_tile(1))
+
+
+def _connectivity(connectivity, what: str) -> int:
+    if connectivity not in (4, 8):
+        raise NndError(f"{what}: connectivity must be 4 or 8; got {connectivity!r}")
+    return int(connectivity)
+
+
+def _max_diff(max_diff, what: str) -> float:
+    max_diff = float(max_diff)
+    if not max_diff >= 0.0:
+        raise NndError(f"{what}: max_diff must be >= 0 (+inf is allowed); got {max_diff}")
+    return max_diff
+
+
+def connected_regions(map: torch.Tensor, max_diff: float, valid_mask: Optional[torch.Tensor] = None, connectivity: int = 4,
+                      workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(labels, sizes), both (B,1,H,W) int32 on the device.  Per sample: valid = valid_mask (1 = valid; None: set) &&
+    isfinite(d); two neighbours (4- or 8-neighbourhood) are joined iff both are valid and fabsf(d[p] - d[q]) <= max_diff, one
+    rounded fp32 subtraction; a region is a connected component of that graph.  labels[p] = the smallest row-major index y*W + x
+    of p's region, -1 where invalid; sizes[p] = the region's pixel count, 0 where invalid.  Four launches whatever the data, no
+    host synchronisation, the same bytes on every run.  `workspace`: a device tensor of `regions_workspace_bytes(B,H,W)` bytes
+    to reuse across calls (what a graph capture wants); allocated per call if None."""
+    what = "connected_regions"
+    conn, md = _connectivity(connectivity, what), _max_diff(max_diff, what)
+    d, m = _map4(map, what, valid_mask)
+    B, _, H, W = d.shape
+    ws = _regions_workspace(d, workspace, what)
+    labels = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device)
+    sizes = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib.nnd_connected_regions(_p(d), _bstride(d), _p(m), 1, md, conn, _p(labels), _p(sizes), _p(ws),
+                                        ws.numel() * ws.element_size(), B, H, W, _stream(d.device)), what)
+    return labels, sizes
+
+
+def speckle_filter(map: torch.Tensor, max_size: int, max_diff: float = 1.0, mask: Optional[torch.Tensor] = None,
+                   mask_is_valid: bool = True, connectivity: int = 4, fill: float = 0.0, return_sizes: bool = False,
+                   workspace: Optional[torch.Tensor] = None):
+    """(filtered (B,1,H,W) fp32, mask_out (B,1,H,W) uint8, speckle (B,1,H,W) uint8[, sizes int32]) in one enqueue.  `mask` is a
+    valid mask (mask_is_valid, 1 = valid) or an occlusion mask (1 = invalid); speckle = valid && region size <= max_size (regions
+    as in `connected_regions`); filtered = speckle ? fill : map, every other pixel bit for bit; mask_out, in the polarity of
+    `mask`, flags as invalid what was invalid (masked out or not finite) or is a speckle."""
+    what = "speckle_filter"
+    conn, md = _connectivity(connectivity, what), _max_diff(max_diff, what)
+    if isinstance(max_size, bool) or not isinstance(max_size, int) or max_size < 0:
+        raise NndError(f"{what}: max_size must be an integer >= 0; got {max_size!r}")
+    d, m = _map4(map, what, mask)
+    B, _, H, W = d.shape
+    ws = _regions_workspace(d, workspace, what)
+    filtered = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
+    mask_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    speckle = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    sizes = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device) if return_sizes else None
+    with torch.cuda.device(d.device):
+        check(lib.nnd_speckle_filter(_p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), md, conn, max_size, float(fill),
+                                     _p(filtered), _p(mask_out), _p(speckle), _p(sizes), _p(ws), ws.numel() * ws.element_size(),
+                                     B, H, W, _stream(d.device)), what)
+    return (filtered, mask_out, speckle, sizes) if return_sizes else (filtered, mask_out, speckle)
+
+
+def speckle_mask(map: torch.Tensor, max_size: int, max_diff: float = 1.0, valid_mask: Optional[torch.Tensor] = None,
+                 connectivity: int = 4, return_sizes: bool = False):
+    """The (B,1,H,W) uint8 mask of the speckles, 1 = a valid pixel whose region (see `connected_regions`) has at most `max_size`
+    pixels; with return_sizes also the (B,1,H,W) int32 region sizes."""
+    out = speckle_filter(map, max_size, max_diff, valid_mask, True, connectivity, 0.0, return_sizes)
+    return (out[2], out[3]) if return_sizes else out[2]
 
 
 def pair_both_views(left: torch.Tensor, right: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

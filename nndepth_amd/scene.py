@@ -11,7 +11,8 @@ the only device-to-host copy is the finished uint8 picture.  `get_view_tensor` r
 host synchronisation (what a serving loop chains after `GraphedForward`).  The resizes of the dataloaders (`interpolate`,
 `maxpool`, `minpool`) run on the device as well.  Nothing falls back to PyTorch: a CPU tensor is refused.  Beyond the reference:
 `Disparity.to_depth`, `Depth.to_disparity`, `Depth.to_points_map`, `Depth.points_tensor` and `Depth.to_points` consume the
-`baseline` and `Camera.intrinsic` the reference only stores (geometry.py, csrc/geometry.hip).
+`baseline` and `Camera.intrinsic` the reference only stores (geometry.py, csrc/geometry.hip); `Disparity.remove_speckles` and
+`Depth.remove_speckles` drop small connected patches (csrc/speckle.hip).
 
 Constructor arguments, attributes, method names, defaults and the ranks of what comes back are the reference's, its quirks
 included (Q9, the pooled occlusion of every batch element is gathered from plane 0; `resize` leaves `self.data`
@@ -245,6 +246,17 @@ class Disparity:
         depth, valid = geometry.disparity_to_depth(self.data, camera_or_fx, baseline, self.disp_sign, min_disp, max_depth, valid_mask)
         return Depth(data=depth, valid_mask=valid)
 
+    def remove_speckles(self, max_size: int, max_diff: float = 1.0, connectivity: int = 4, fill: float = 0.0) -> "Disparity":
+        """A new Disparity without its speckles, on the device (geometry.speckle_filter, csrc/speckle.hip): a speckle is a pixel
+        whose connected region has at most `max_size` pixels, where two neighbours (4- or 8-neighbourhood) hang together iff
+        neither is occluded, both are finite and |d[p] - d[q]| <= max_diff.  Speckles take the value `fill`; every other pixel is
+        copied bit for bit.  The returned occlusion (1 = invalid, in the dtype of self.occlusion, uint8 if there was none) is the
+        old one, the non-finite pixels and the removed ones.  (B,1,H,W) maps; not a method of the reference."""
+        from . import geometry
+        data, occ, _ = geometry.speckle_filter(self.data, max_size, max_diff, self.occlusion, False, connectivity, fill)
+        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+
 
 class Depth:
     def __init__(self, data: torch.Tensor, valid_mask: Optional[torch.Tensor] = None, is_inverse: bool = False):
@@ -312,6 +324,15 @@ class Depth:
         from . import geometry
         disp = geometry.depth_to_disparity(self.data, camera_or_fx, baseline, disp_sign, eps)
         return Disparity(data=disp, disp_sign=disp_sign, baseline=baseline)
+
+    def remove_speckles(self, max_size: int, max_diff: float = 1.0, connectivity: int = 4, fill: float = 0.0) -> "Depth":
+        """`Disparity.remove_speckles` on a depth map: pixels with valid_mask == 0 (or a non-finite depth) belong to no region,
+        speckles take `fill`, and the returned valid_mask (1 = valid, in the dtype of self.valid_mask, uint8 if there was none)
+        no longer holds them."""
+        from . import geometry
+        data, valid, _ = geometry.speckle_filter(self.data, max_size, max_diff, self.valid_mask, True, connectivity, fill)
+        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
+        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
 
     def to_points_map(self, camera) -> torch.Tensor:
         """(B,3,H,W): X = fp32((u - cx) * Z / fx), Y = fp32((v - cy) * Z / fy), arithmetic in double, Z copied;
