@@ -860,6 +860,59 @@ int nnd_speckle_filter(const float* map, int64_t map_bstride, const unsigned cha
                        unsigned char* speckle_out, int32_t* sizes, void* workspace, int64_t workspace_bytes, int B, int H, int W,
                        void* stream);
 
+/* ------------------------------------------------------------- view warp, warp occlusion and hole filling (additions within 105)
+ * What one disparity map says about the OTHER view, and a dense map from one with holes (csrc/warp.hip).  Beyond the reference,
+ * which has neither step.  Maps, strides and masks as above; `negative` != 0: m = -d, else m = d.
+ *
+ * nnd_warp_disparity: a z-buffered forward warp along the row, nearest column.  Per sample and row y, every step one rounded fp32
+ * operation:
+ *   m      = (negative ? -d[y,x] : d[y,x]) + 0.0f                        (-0.0 counts as +0.0)
+ *   src_ok = (mask == NULL || (mask[y,x] != 0) == (mask_valid_is_one != 0)) && isfinite(m) && m >= 0
+ *   xr     = to_right ? (float)x - m : (float)x + m ;  t = rintf(xr)     (ties to even: 1.5 and 2.5 both land on column 2)
+ *   lands  = src_ok && t >= 0.0f && t <= (float)(W-1)                    (xr in [-0.5, 0] lands on column 0)
+ *   winner of (y,t): among the sources that land there the largest m; among equal m the smallest x
+ *   a target with a winner : disp_other = negative ? -m_win : m_win, source = x_win, features_other[:,y,t] = features[:,y,x_win]
+ *                            bit for bit; a target without one (a hole): disp_other = fill, source = -1, features 0
+ *   valid_other[y,t] = in the polarity of mask_valid_is_one: has a winner (!= 0: 1 = has one; 0: 1 = hole)
+ *   occluded[y,x]    = !(lands && (m_win(y,t) - m) <= threshold): 1 = occluded, out of frame or invalid (the polarity of
+ *                      nnd_lr_consistency and of the KITTI mask)
+ * to_right == 0 takes a right-view map and writes the left view.  threshold >= 0, +inf allowed (only invalid pixels and those that
+ * leave the frame are occluded then).  Outputs: disp_other (B,H,W) floats, valid_other / occluded (B,H,W) bytes, source (B,H,W)
+ * int32; each may be NULL, not all.  features (B,C,H,W) contiguous, features_other and C > 0 go together.  ONE launch, no
+ * workspace: a workgroup per row keeps a 64-bit key per column, bits(m) << 32 | (W - x), in LDS and takes integer maxima, so the
+ * result does not depend on the order of arrival and a run gives the same bytes every time.  Refused before any HIP call: a null
+ * map, no output, B, H, W out of range (1 <= B <= 65535, H*W < 2^31, B*H <= 2^25), W above nnd_warp_disparity_limit(0), a batch
+ * stride below H*W, a negative or NaN threshold, features without C or the other way round.
+ * nnd_warp_disparity_limit: the largest width (which = 0); the columns a workgroup handles per pass (1).
+ * What the occlusion is NOT: a nearest-column splat leaves one-pixel cracks in a surface that stretches in the other view, and a
+ * hidden pixel behind a crack wins that column and counts as visible; it is not the definition of nnd_lr_consistency.
+ *
+ * nnd_fill_holes: ok[p] = mask-valid[p] && isfinite(map[p]).  rule: 0 min_abs, 1 max_abs, 2 nearest.  A value is always copied bit
+ * for bit from a neighbour; nothing is interpolated.
+ *   row pass, rows with an ok pixel: a pixel that is not ok has L / R, the nearest ok column to its left / right; with one of them
+ *     it takes that one's value; with both, min_abs takes L if fabsf(v_L) <= fabsf(v_R) else R, max_abs L if fabsf(v_L) >=
+ *     fabsf(v_R) else R, nearest L if x-L <= R-x else R.
+ *   column pass (vertical != 0), rows without an ok pixel: U / D = the nearest rows above / below that have one; the pixel takes the
+ *     row-pass result of U or D at its column by the same rule (U on a tie; y-U <= D-y for nearest).
+ *   a sample without an ok pixel, and with vertical == 0 every empty row, keeps `fill`.
+ *   filled (B,H,W) floats, required, not the input; was_filled (optional bytes): 1 where a value was copied in; mask_out (optional
+ *   bytes): in the polarity of mask_valid_is_one, invalid = still without a value.  Pixels that were ok are copied bit for bit.
+ * THREE launches whatever the data (the first ok column at or after every chunk of a row, from the right; the row pass, from the left,
+ * and for empty rows the search for U and D; the column pass), no atomics.  `workspace` = nnd_fill_holes_workspace_bytes(B,H,W)
+ * device bytes (a word per row and chunk of nnd_fill_holes_chunk() columns, two per row), 4-byte aligned, the caller's.  Refused
+ * before any HIP call: a null map / workspace / filled, filled == map, B, H, W out of range, a batch stride below H*W, an unknown
+ * rule, a workspace too small or misaligned.                                                                                    */
+int nnd_warp_disparity_limit(int which);
+int nnd_warp_disparity(const float* disp, int64_t disp_bstride, const unsigned char* mask, int mask_valid_is_one, int negative,
+                       int to_right, float threshold, float fill, const float* features, int C, float* disp_other,
+                       unsigned char* valid_other, unsigned char* occluded, int32_t* source, float* features_other, int B, int H, int W,
+                       void* stream);
+int nnd_fill_holes_chunk(void);
+int64_t nnd_fill_holes_workspace_bytes(int B, int H, int W);
+int nnd_fill_holes(const float* map, int64_t map_bstride, const unsigned char* mask, int mask_valid_is_one, int rule, int vertical,
+                   float fill, float* filled, unsigned char* was_filled, unsigned char* mask_out, void* workspace,
+                   int64_t workspace_bytes, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58
  * (no masks).  The reference's (N, H*W, C) tokens are the (N,C,H,W) maps transposed, so every nn.Linear is a 1x1 conv of

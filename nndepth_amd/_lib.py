@@ -233,6 +233,11 @@ SIGNATURES = {
     "nnd_connected_regions_tile": (_I, [_I]),
     "nnd_connected_regions": (_I, [_P, C.c_int64, _P, _I, C.c_float, _I, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
     "nnd_speckle_filter": (_I, [_P, C.c_int64, _P, _I, C.c_float, _I, _I, C.c_float, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
+    "nnd_warp_disparity_limit": (_I, [_I]),
+    "nnd_warp_disparity": (_I, [_P, C.c_int64, _P, _I, _I, _I, C.c_float, C.c_float, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_fill_holes_chunk": (_I, []),
+    "nnd_fill_holes_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "nnd_fill_holes": (_I, [_P, C.c_int64, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
     "nnd_loftr_packed_floats": (C.c_int64, [_I, _I]),
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),

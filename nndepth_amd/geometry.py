@@ -9,6 +9,8 @@ Here:
     depth_to_points / points_compact           (Depth.to_points_map, Depth.points_tensor, Depth.to_points)
     lr_consistency, both_views, occlusion      a left-right check of a PREDICTED map -> an occlusion mask, 1 = occluded
     connected_regions, speckle_mask, speckle_filter    (csrc/speckle.hip; Disparity.remove_speckles, Depth.remove_speckles)
+    warp_disparity, occlusion_from_warp, fill_holes    (csrc/warp.hip; Disparity.to_other_view / warp_occlusion / fill_holes,
+                                                        Depth.fill_holes): the other view and an occlusion mask from ONE map
 
 Maps are (B,1,H,W) fp32 on the HIP device; a batch stride is read where it lies (a channel slice of CREStereo's 2-channel
 output, half of a stacked batch).  Masks are torch.bool or torch.uint8, (B,1,H,W) or (B,H,W).  Camera values come from
@@ -289,6 +291,145 @@ def speckle_mask(map: torch.Tensor, max_size: int, max_diff: float = 1.0, valid_
     pixels; with return_sizes also the (B,1,H,W) int32 region sizes."""
     out = speckle_filter(map, max_size, max_diff, valid_mask, True, connectivity, 0.0, return_sizes)
     return (out[2], out[3]) if return_sizes else out[2]
+
+
+# ---------------------------------------------------------------------------------- view warp and hole filling (csrc/warp.hip)
+_RULES = ("min_abs", "max_abs", "nearest")
+_VIEWS = ("left", "right")
+
+
+def warp_max_width() -> int:
+    """The widest map `warp_disparity` accepts: a row's 64-bit keys live in LDS."""
+    return int(lib.nnd_warp_disparity_limit(0))
+
+
+def warp_chunk() -> int:
+    """The columns of a row a `warp_disparity` workgroup handles per pass."""
+    return int(lib.nnd_warp_disparity_limit(1))
+
+
+def fill_chunk() -> int:
+    """The columns of a row a `fill_holes` wave scans per step."""
+    return int(lib.nnd_fill_holes_chunk())
+
+
+def fill_workspace_bytes(B: int, H: int, W: int) -> int:
+    """Device bytes `fill_holes` needs for a (B,1,H,W) map (a word per row and chunk, two per row); 4-byte aligned."""
+    nbytes = int(lib.nnd_fill_holes_workspace_bytes(int(B), int(H), int(W)))
+    if nbytes < 0:
+        check(nbytes, "fill_workspace_bytes")
+    return nbytes
+
+
+def _shape_first(t, what: str):
+    """A wrong shape is named as such whatever the device (`_map4` names the device first)."""
+    if torch.is_tensor(t) and t.dtype == torch.float32 and (t.ndim != 4 or t.shape[1] != 1 or t.numel() == 0):
+        raise NndError(f"{what}: a map is (B,1,H,W); got {tuple(t.shape)}")
+
+
+def _warp(what: str, disp, disp_sign, to_view, threshold, mask, mask_is_valid, features, fill, want_source):
+    """(disp_other, valid_other in the polarity of the mask, occluded, source or None, features_other or None)"""
+    neg = _sign(disp_sign, what)
+    if to_view not in _VIEWS:
+        raise NndError(f"{what}: to_view must be 'right' or 'left'; got {to_view!r}")
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise NndError(f"{what}: threshold must be >= 0 (+inf is allowed); got {threshold}")
+    _shape_first(disp, what)
+    d, m = _map4(disp, what, mask)
+    B, _, H, W = d.shape
+    if W > warp_max_width():
+        raise NndError(f"{what}: a width of {W} is above the maximum width {warp_max_width()} (warp_max_width)")
+    Cf = 0
+    feats = None
+    if features is not None:
+        if not torch.is_tensor(features) or features.dtype != torch.float32:
+            raise NndError(f"{what}: features are torch.float32; got {getattr(features, 'dtype', type(features).__name__)}")
+        if features.device != d.device:
+            raise NndError(f"{what}: the features are on {features.device}, the map on {d.device} (no CPU fallback exists)")
+        if features.ndim != 4 or features.shape[0] != B or tuple(features.shape[2:]) != (H, W) or features.shape[1] < 1:
+            raise NndError(f"{what}: features are (B,C,H,W) = ({B},C,{H},{W}); got {tuple(features.shape)}")
+        features = features.contiguous()
+        Cf = features.shape[1]
+        feats = torch.empty((B, Cf, H, W), dtype=torch.float32, device=d.device)
+    other = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
+    valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    occ = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    src = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device) if want_source else None
+    with torch.cuda.device(d.device):
+        check(lib.nnd_warp_disparity(_p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), neg, int(to_view == "right"), threshold,
+                                     float(fill), _p(features), Cf, _p(other), _p(valid), _p(occ), _p(src), _p(feats), B, H, W,
+                                     _stream(d.device)), what)
+    return other, valid, occ, src, feats
+
+
+def warp_disparity(disp: torch.Tensor, disp_sign: str = "negative", to_view: str = "right", threshold: float = 1.0,
+                   valid_mask: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None, fill: float = 0.0,
+                   return_source: bool = False):
+    """(disp_other (B,1,H,W) fp32, valid_other uint8, occluded uint8[, source int32][, features_other (B,C,H,W) fp32]): the map
+    seen from the other view by a z-buffered forward warp to the nearest column, in one launch.  Per row, each step one rounded
+    fp32 operation:
+
+        m      = (negative ? -d[y,x] : d[y,x]) + 0.0f
+        src_ok = valid_mask[y,x] (None: 1) && isfinite(m) && m >= 0
+        xr     = to_view == "right" ? float(x) - m : float(x) + m ;  t = rintf(xr)  (ties to even)
+        lands  = src_ok && 0 <= t <= W-1
+
+    Of the sources that land on (y,t) the largest m wins, among equal m the smallest x: disp_other[y,t] = the winner's value in
+    the same sign, valid_other = 1, source = x_win, features_other[:,y,t] = features[:,y,x_win] bit for bit.  A target without a
+    source is a hole: `fill`, 0, -1, features 0.  occluded[y,x] = !(lands && m_win(y,t) - m <= threshold): 1 = occluded, out of
+    frame or invalid, the polarity of `lr_consistency`.  to_view="left" takes a right-view map.  It is NOT `lr_consistency`: a
+    surface that stretches in the other view has one-pixel cracks, and a hidden pixel behind a crack counts as visible."""
+    out = _warp("warp_disparity", disp, disp_sign, to_view, threshold, valid_mask, True, features, fill, return_source)
+    return tuple(t for t in out if t is not None)
+
+
+def fill_holes(map: torch.Tensor, mask: Optional[torch.Tensor] = None, mask_is_valid: bool = True, rule: str = "min_abs",
+               vertical: bool = True, fill: float = 0.0, workspace: Optional[torch.Tensor] = None):
+    """(filled (B,1,H,W) fp32, was_filled uint8, mask_out uint8 in the polarity of `mask`).  ok = mask-valid && isfinite(map).  In a
+    row with an ok pixel, a pixel that is not ok takes the value of L or R, its nearest ok columns: the one that exists, else by
+    `rule`: "min_abs" L if |v_L| <= |v_R| (the background of a disparity map: the KITTI devkit's rule), "max_abs" L if |v_L| >=
+    |v_R|, "nearest" L if x-L <= R-x.  With `vertical`, a row without an ok pixel takes, column by column, the row-pass result of
+    the nearest non-empty row above or below by the same rule (above on a tie).  What is left (a sample without an ok pixel; empty
+    rows when not vertical) is `fill`.  Values are copied bit for bit, ok pixels too; was_filled = 1 where a value was copied in;
+    mask_out flags what is still invalid.  Three launches whatever the data; `workspace`: `fill_workspace_bytes(B,H,W)` device
+    bytes to reuse across calls, allocated per call if None."""
+    what = "fill_holes"
+    if rule not in _RULES:
+        raise NndError(f"{what}: rule must be one of {_RULES}; got {rule!r}")
+    _shape_first(map, what)
+    d, m = _map4(map, what, mask)
+    B, _, H, W = d.shape
+    nbytes = fill_workspace_bytes(B, H, W)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=d.device)
+    elif not torch.is_tensor(workspace) or workspace.device != d.device or not workspace.is_contiguous():
+        raise NndError(f"{what}: the workspace must be a contiguous tensor on {d.device}")
+    elif workspace.numel() * workspace.element_size() < nbytes:
+        raise NndError(f"{what}: a workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed "
+                       "(fill_workspace_bytes)")
+    filled = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
+    was = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    mask_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib.nnd_fill_holes(_p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), _RULES.index(rule), int(bool(vertical)),
+                                 float(fill), _p(filled), _p(was), _p(mask_out), _p(workspace),
+                                 workspace.numel() * workspace.element_size(), B, H, W, _stream(d.device)), what)
+    return filled, was, mask_out
+
+
+def occlusion_from_warp(forward: Callable, left: torch.Tensor, right: torch.Tensor, threshold: float = 1.0):
+    """scene.Disparity(data=disp_left, disp_sign="negative", occlusion=mask) from ONE call of `forward` at batch B: the `occluded`
+    mask of `warp_disparity` on outputs[-1]["up_disp"][:, :1].  The single-forward counterpart of `occlusion`; not the same
+    definition (see `warp_disparity`)."""
+    from .scene import Disparity
+    up = forward(left, right)[-1]["up_disp"]
+    if not torch.is_tensor(up) or up.ndim != 4 or up.shape[0] != left.shape[0]:
+        raise NndError(f"occlusion_from_warp: the forward returned up_disp {tuple(getattr(up, 'shape', ()))} for a batch of "
+                       f"{left.shape[0]}")
+    dl = up[:, :1]
+    mask = _warp("occlusion_from_warp", dl, "negative", "right", threshold, None, True, None, 0.0, False)[2]
+    return Disparity(data=dl, disp_sign="negative", occlusion=mask)
 
 
 def pair_both_views(left: torch.Tensor, right: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -12,7 +12,8 @@ host synchronisation (what a serving loop chains after `GraphedForward`).  The r
 `maxpool`, `minpool`) run on the device as well.  Nothing falls back to PyTorch: a CPU tensor is refused.  Beyond the reference:
 `Disparity.to_depth`, `Depth.to_disparity`, `Depth.to_points_map`, `Depth.points_tensor` and `Depth.to_points` consume the
 `baseline` and `Camera.intrinsic` the reference only stores (geometry.py, csrc/geometry.hip); `Disparity.remove_speckles` and
-`Depth.remove_speckles` drop small connected patches (csrc/speckle.hip).
+`Depth.remove_speckles` drop small connected patches (csrc/speckle.hip); `Disparity.to_other_view`, `Disparity.warp_occlusion` and the
+two `fill_holes` warp a map into the other view, find the occlusion that warp reveals and fill holes (csrc/warp.hip).
 
 Constructor arguments, attributes, method names, defaults and the ranks of what comes back are the reference's, its quirks
 included (Q9, the pooled occlusion of every batch element is gathered from plane 0; `resize` leaves `self.data`
@@ -257,6 +258,45 @@ class Disparity:
         occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
         return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
 
+    _FILL_RULES = {"background": "min_abs", "foreground": "max_abs", "nearest": "nearest"}
+
+    def to_other_view(self, to: str = "right", threshold: float = 1.0, features: Optional[torch.Tensor] = None):
+        """This map seen from the other view (geometry.warp_disparity, csrc/warp.hip): a z-buffered forward warp to the nearest
+        column; `to="left"` for a right-view map.  Occluded pixels (self.occlusion == 1) are no sources.  The returned Disparity
+        has the same disp_sign and baseline; its occlusion is 1 in the holes (targets no source lands on, value 0), in the dtype of
+        self.occlusion, uint8 if there was none.  With `features` ((B,C,H,W) fp32, e.g. the left picture) returns (Disparity,
+        features seen from the other view, 0 in the holes).  (B,1,H,W) maps; not a method of the reference."""
+        from . import geometry
+        data, hole, _, _, feats = geometry._warp("Disparity.to_other_view", self.data, self.disp_sign, to, threshold, self.occlusion,
+                                                 False, features, 0.0, False)
+        hole = hole if self.occlusion is None else _as_dtype(hole, self.occlusion.dtype)
+        out = Disparity(data=data, disp_sign=self.disp_sign, occlusion=hole, baseline=self.baseline)
+        return out if features is None else (out, feats)
+
+    def warp_occlusion(self, threshold: float = 1.0) -> "Disparity":
+        """The same map with the occlusion that its own warp into the other view reveals (geometry.warp_disparity): a pixel is
+        occluded if it was (self.occlusion == 1), is not finite or of the wrong sign, leaves the frame, or loses its target column
+        to a surface more than `threshold` nearer.  One map, no second forward; not the definition of `lr_consistency` (a hidden
+        pixel behind a one-pixel crack of a stretching surface counts as visible).  The mask keeps its dtype, uint8 if there was
+        none."""
+        from . import geometry
+        occ = geometry._warp("Disparity.warp_occlusion", self.data, self.disp_sign, "right", threshold, self.occlusion, False, None,
+                             0.0, False)[2]
+        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
+        return Disparity(data=self.data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+
+    def fill_holes(self, rule: str = "background", vertical: bool = True) -> "Disparity":
+        """A dense map (geometry.fill_holes): occluded or non-finite pixels take the value of the nearest valid pixel of their row
+        to the left or right, "background": the one of smaller |disparity| (the KITTI devkit's rule), "foreground": the larger,
+        "nearest": the nearer; rows without a valid pixel are filled from the rows above and below when `vertical`.  Values are
+        copied, never interpolated.  The returned occlusion (dtype kept, uint8 if there was none) is what remains invalid."""
+        from . import geometry
+        if rule not in self._FILL_RULES:
+            raise NndError(f"Disparity.fill_holes: rule must be one of {tuple(self._FILL_RULES)}; got {rule!r}")
+        data, _, occ = geometry.fill_holes(self.data, self.occlusion, False, self._FILL_RULES[rule], vertical)
+        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+
 
 class Depth:
     def __init__(self, data: torch.Tensor, valid_mask: Optional[torch.Tensor] = None, is_inverse: bool = False):
@@ -331,6 +371,19 @@ class Depth:
         no longer holds them."""
         from . import geometry
         data, valid, _ = geometry.speckle_filter(self.data, max_size, max_diff, self.valid_mask, True, connectivity, fill)
+        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
+        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
+
+    def fill_holes(self, rule: str = "background", vertical: bool = True) -> "Depth":
+        """`Disparity.fill_holes` on a depth map: "background" is the LARGER depth (the smaller value when is_inverse),
+        "foreground" the other one, "nearest" the nearer pixel.  The returned valid_mask (dtype kept, uint8 if there was none)
+        is 1 wherever the map now has a value."""
+        from . import geometry
+        far, near = ("min_abs", "max_abs") if self.is_inverse else ("max_abs", "min_abs")
+        rules = {"background": far, "foreground": near, "nearest": "nearest"}
+        if rule not in rules:
+            raise NndError(f"Depth.fill_holes: rule must be one of {tuple(rules)}; got {rule!r}")
+        data, _, valid = geometry.fill_holes(self.data, self.valid_mask, True, rules[rule], vertical)
         valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
         return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
 
