@@ -913,6 +913,42 @@ int nnd_fill_holes(const float* map, int64_t map_bstride, const unsigned char* m
                    float fill, float* filled, unsigned char* was_filled, unsigned char* mask_out, void* workspace,
                    int64_t workspace_bytes, int B, int H, int W, void* stream);
 
+/* ------------------------------------------------------------- masked median and guided weighted median (additions within 105)
+ * The edge-preserving step that ends the clean-up chain (csrc/median.hip): a (2r+1) x (2r+1) median over the ok pixels, or a
+ * weighted median whose weights come from a picture.  Beyond the reference, which has no such step.  A SELECTION: every output is
+ * a copy of input bits.
+ * Inputs: map (B,1,H,W) fp32, its batch stride read where it lies; mask: optional bytes, polarity mask_valid_is_one as in
+ * nnd_speckle_filter and nnd_fill_holes; radius r; min_count; fill_invalid; fill.  Guide, optional: guide (B,C,H,W) fp32,
+ * contiguous, 1 <= C <= 4; inv_step finite and > 0; weights: 256 uint16_t in HOST memory, copied into the launch's arguments: no
+ * device table, no host synchronisation, and the call can be captured into a graph.
+ *   1  ok[q] = mask-valid[q] && isfinite(map[q]).
+ *   2  The window of p = (y,x): the in-frame q with |qy-y| <= r and |qx-x| <= r.  Clipped at the border, no padding.
+ *   3  Order on values: key(v) = bits(v) ^ (sign ? 0xFFFFFFFF : 0x80000000), compared as unsigned: -0.0 < +0.0, and denormals are
+ *      ordinary values.
+ *   4  Tap weight w(p,q): without a guide 1.  With a guide, every step one rounded fp32 operation:
+ *        dist = |g0[p]-g0[q]|, then + |g1[p]-g1[q]|, and so on in channel order;  s = dist * inv_step;
+ *        b = (s < 255.0f) ? (int)s : 255   (a NaN from a non-finite guide value gives 255);  w = weights[b].
+ *   5  Over the ok taps of the window: n their count, T = sum of w, S(v) = sum of w over the ok taps with key <= key(v).  The
+ *      weighted lower median v* is the tap value of smallest key with 2 S(v*) >= T; all of it integer arithmetic.  With unit
+ *      weights v* is the element of rank (n-1)/2.
+ *   6  produced[p] = (ok[p] || fill_invalid) && n >= min_count && T > 0.
+ *   7  filtered[p] = v* bit for bit if produced[p]; else map[p] bit for bit if ok[p]; else fill.
+ *   8  mask_out[p] (optional bytes), in the polarity of the input mask: valid = ok[p] || produced[p].
+ *   9  changed[p] (optional bytes) = 1 where the output bits differ from the input bits, or where a pixel that was not ok got a
+ *      value.
+ * ONE launch, no workspace, no atomics, the same bytes on every run; nothing depends on what the outputs held before.  Refused
+ * before any HIP call: a null map or filtered, filtered == map, B, H, W out of range (as nnd_fill_holes), a batch stride below
+ * H*W, a radius outside 1 .. nnd_median_filter_limit(0), min_count outside 1 .. (2r+1)^2, guide, C and weights not given
+ * together, C outside 1 .. 4, inv_step not finite or <= 0, weights[0] == 0 (the centre tap must count, or an ok pixel could have
+ * T = 0).
+ * nnd_median_filter_limit: the largest radius (which = 0; >= 7), the height (1) and width (2) of the output tile of one
+ * workgroup; anything else: < 0.                                                                                               */
+int nnd_median_filter_limit(int which);
+int nnd_median_filter(const float* map, int64_t map_bstride, const unsigned char* mask, int mask_valid_is_one, int radius,
+                      int min_count, int fill_invalid, float fill, const float* guide, int C, float inv_step,
+                      const uint16_t* weights, float* filtered, unsigned char* mask_out, unsigned char* changed, int B, int H, int W,
+                      void* stream);
+
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58
  * (no masks).  The reference's (N, H*W, C) tokens are the (N,C,H,W) maps transposed, so every nn.Linear is a 1x1 conv of

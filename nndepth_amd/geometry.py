@@ -11,6 +11,8 @@ Here:
     connected_regions, speckle_mask, speckle_filter    (csrc/speckle.hip; Disparity.remove_speckles, Depth.remove_speckles)
     warp_disparity, occlusion_from_warp, fill_holes    (csrc/warp.hip; Disparity.to_other_view / warp_occlusion / fill_holes,
                                                         Depth.fill_holes): the other view and an occlusion mask from ONE map
+    median_filter, range_weights                       (csrc/median.hip; Disparity.median_filter, Depth.median_filter): a masked
+                                                        k x k median, or a weighted median guided by a picture
 
 Maps are (B,1,H,W) fp32 on the HIP device; a batch stride is read where it lies (a channel slice of CREStereo's 2-channel
 output, half of a stacked batch).  Masks are torch.bool or torch.uint8, (B,1,H,W) or (B,H,W).  Camera values come from
@@ -416,6 +418,110 @@ def fill_holes(map: torch.Tensor, mask: Optional[torch.Tensor] = None, mask_is_v
                                  float(fill), _p(filled), _p(was), _p(mask_out), _p(workspace),
                                  workspace.numel() * workspace.element_size(), B, H, W, _stream(d.device)), what)
     return filled, was, mask_out
+
+
+# ------------------------------------------------------------------ masked median and guided weighted median (csrc/median.hip)
+_KINDS = ("exp", "gauss", "box")
+
+
+def median_max_radius() -> int:
+    """The largest radius `median_filter` accepts."""
+    return int(lib.nnd_median_filter_limit(0))
+
+
+def median_tile() -> Tuple[int, int]:
+    """(height, width) of the output tile of one `median_filter` workgroup."""
+    return int(lib.nnd_median_filter_limit(1)), int(lib.nnd_median_filter_limit(2))
+
+
+def range_weights(sigma: float, step: Optional[float] = None, kind: str = "exp"):
+    """(numpy uint16[256], inv_step) for `median_filter`: w[b] = floor(65535 * f(b * step) + 0.5) in float64 with f(d) =
+    exp(-d / sigma) ("exp"), exp(-d^2 / (2 sigma^2)) ("gauss") or d <= sigma ("box"); `step`, the guide distance one entry of the
+    table stands for, defaults to sigma / 32; inv_step = float32(1 / step)."""
+    import numpy as np
+    what = "range_weights"
+    if kind not in _KINDS:
+        raise NndError(f"{what}: kind must be one of {_KINDS}; got {kind!r}")
+    sigma = float(sigma)
+    if not (sigma > 0.0 and sigma < float("inf")):
+        raise NndError(f"{what}: sigma must be finite and > 0; got {sigma}")
+    step = sigma / 32 if step is None else float(step)
+    if not (step > 0.0 and step < float("inf")):
+        raise NndError(f"{what}: step must be finite and > 0; got {step}")
+    d = np.arange(256, dtype=np.float64) * step
+    f = np.exp(-d / sigma) if kind == "exp" else np.exp(-d * d / (2.0 * sigma * sigma)) if kind == "gauss" else (d <= sigma).astype(np.float64)
+    return np.floor(65535.0 * f + 0.5).astype(np.uint16), float(np.float32(1.0 / step))
+
+
+def median_filter(map: torch.Tensor, radius: int = 1, valid_mask: Optional[torch.Tensor] = None, mask_is_valid: bool = True,
+                  guide: Optional[torch.Tensor] = None, sigma: float = 0.2, step: Optional[float] = None, kind: str = "exp",
+                  weights=None, min_count: int = 1, fill_invalid: bool = False, fill: float = 0.0, return_changed: bool = False):
+    """(filtered (B,1,H,W) fp32, mask_out uint8 in the polarity of the mask[, changed uint8]): a masked (2r+1) x (2r+1) median, or
+    with `guide` ((B,C,H,W) fp32, 1 <= C <= 4, e.g. the left picture) a weighted median that keeps the map's edges on the guide's,
+    in one launch (csrc/median.hip).  A selection: every output is a copy of input bits.
+
+      1  ok[q] = mask-valid[q] && isfinite(map[q]).
+      2  The window of p = (y,x): the in-frame q with |qy-y| <= r and |qx-x| <= r.  Clipped at the border, no padding.
+      3  Order on values: key(v) = bits(v) ^ (sign ? 0xFFFFFFFF : 0x80000000), compared as unsigned: -0.0 < +0.0, and denormals are
+         ordinary values.
+      4  Tap weight w(p,q): without a guide 1.  With a guide, every step one rounded fp32 operation: dist = |g0[p]-g0[q]|, then
+         + |g1[p]-g1[q]|, and so on in channel order; s = dist * inv_step; b = (s < 255.0f) ? (int)s : 255 (a NaN from a non-finite
+         guide value gives 255); w = weights[b].
+      5  Over the ok taps of the window: n their count, T = sum of w, S(v) = sum of w over the ok taps with key <= key(v).  The
+         weighted lower median v* is the tap value of smallest key with 2 S(v*) >= T; all of it integer arithmetic.  With unit
+         weights v* is the element of rank (n-1)/2.
+      6  produced[p] = (ok[p] || fill_invalid) && n >= min_count && T > 0.
+      7  filtered[p] = v* bit for bit if produced[p]; else map[p] bit for bit if ok[p]; else `fill`.
+      8  mask_out[p]: valid = ok[p] || produced[p].
+      9  changed[p] = 1 where the output bits differ from the input bits, or where a pixel that was not ok got a value.
+
+    The weights are `range_weights(sigma, step, kind)`, or `weights` (256 uint16 values, weights[0] > 0) with `step` (default
+    sigma / 32); they travel in the launch's arguments: no device table, no host synchronisation, and the call can be captured
+    into a graph.  radius 1 .. `median_max_radius()`, min_count 1 .. (2r+1)^2.  No CPU fallback."""
+    import numpy as np
+    what = "median_filter"
+    _shape_first(map, what)
+    if guide is not None and torch.is_tensor(map) and map.dtype == torch.float32:  # named whatever the device, like a wrong shape
+        if not torch.is_tensor(guide) or guide.dtype != torch.float32:
+            raise NndError(f"{what}: the guide is torch.float32; got {guide.dtype if torch.is_tensor(guide) else type(guide).__name__}")
+        B, _, H, W = map.shape
+        if guide.ndim != 4 or guide.shape[0] != B or tuple(guide.shape[2:]) != (H, W) or not 1 <= guide.shape[1] <= 4:
+            raise NndError(f"{what}: the guide is (B,C,H,W) = ({B},1..4,{H},{W}); got {tuple(guide.shape)}")
+    d, m = _map4(map, what, valid_mask)
+    B, _, H, W = d.shape
+    radius, min_count = int(radius), int(min_count)
+    if not 1 <= radius <= median_max_radius():
+        raise NndError(f"{what}: radius {radius} is outside 1 .. {median_max_radius()} (median_max_radius)")
+    if not 1 <= min_count <= (2 * radius + 1) ** 2:
+        raise NndError(f"{what}: min_count {min_count} is outside 1 .. {(2 * radius + 1) ** 2} = (2 radius + 1)^2")
+    C, inv_step, table = 0, 1.0, None
+    if guide is not None:
+        if guide.device != d.device:
+            raise NndError(f"{what}: the guide is on {guide.device}, the map on {d.device} (no CPU fallback exists)")
+        guide = guide.contiguous()
+        C = guide.shape[1]
+        if weights is None:
+            table, inv_step = range_weights(sigma, step, kind)
+        else:
+            table = np.ascontiguousarray(weights)
+            if table.dtype != np.uint16 or table.shape != (256,):
+                raise NndError(f"{what}: weights are 256 uint16 values; got {table.dtype} {table.shape}")
+            if table[0] == 0:
+                raise NndError(f"{what}: weights[0] is 0: the centre tap must count")
+            step = float(sigma) / 32 if step is None else float(step)
+            if not (step > 0.0 and step < float("inf")):
+                raise NndError(f"{what}: step must be finite and > 0; got {step}")
+            inv_step = float(np.float32(1.0 / step))
+    elif weights is not None:
+        raise NndError(f"{what}: weights without a guide")
+    filtered = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
+    mask_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    changed = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device) if return_changed else None
+    with torch.cuda.device(d.device):
+        check(lib.nnd_median_filter(_p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), radius, min_count, int(bool(fill_invalid)),
+                                    float(fill), _p(guide), C, inv_step, None if table is None else table.ctypes.data, _p(filtered),
+                                    _p(mask_out), _p(changed), B, H, W, _stream(d.device)), what)
+    return (filtered, mask_out, changed) if return_changed else (filtered, mask_out)
 
 
 def occlusion_from_warp(forward: Callable, left: torch.Tensor, right: torch.Tensor, threshold: float = 1.0):

@@ -13,7 +13,8 @@ host synchronisation (what a serving loop chains after `GraphedForward`).  The r
 `Disparity.to_depth`, `Depth.to_disparity`, `Depth.to_points_map`, `Depth.points_tensor` and `Depth.to_points` consume the
 `baseline` and `Camera.intrinsic` the reference only stores (geometry.py, csrc/geometry.hip); `Disparity.remove_speckles` and
 `Depth.remove_speckles` drop small connected patches (csrc/speckle.hip); `Disparity.to_other_view`, `Disparity.warp_occlusion` and the
-two `fill_holes` warp a map into the other view, find the occlusion that warp reveals and fill holes (csrc/warp.hip).
+two `fill_holes` warp a map into the other view, find the occlusion that warp reveals and fill holes (csrc/warp.hip); the two
+`median_filter` end that chain with a masked median or a weighted median guided by the picture (csrc/median.hip).
 
 Constructor arguments, attributes, method names, defaults and the ranks of what comes back are the reference's, its quirks
 included (Q9, the pooled occlusion of every batch element is gathered from plane 0; `resize` leaves `self.data`
@@ -297,6 +298,29 @@ class Disparity:
         occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
         return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
 
+    def median_filter(self, radius: int = 1, guide=None, sigma: float = 0.2, fill_invalid: bool = False, min_count: int = 1,
+                      **weights_kw) -> "Disparity":
+        """A new Disparity filtered by a (2 radius + 1)^2 median over the pixels that are neither occluded nor non-finite
+        (geometry.median_filter, csrc/median.hip); with `guide` (a Frame or a (B,C,H,W) fp32 tensor, C <= 4: the picture of this
+        view) a weighted median, weight exp(-|colour difference| / sigma) (`weights_kw`: step, kind, weights of
+        geometry.median_filter), which keeps disparity edges on colour edges.  Every value is a copy of one of the map's;
+        `fill_invalid` also gives the occluded pixels the median of their valid neighbours (at least `min_count` of them).  The
+        returned occlusion (dtype kept, uint8 if there was none) is what remains invalid."""
+        from . import geometry
+        data, occ = geometry.median_filter(self.data, radius, self.occlusion, False, _guide_tensor(guide), sigma,
+                                           min_count=min_count, fill_invalid=fill_invalid, **weights_kw)
+        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+
+
+def _guide_tensor(guide):
+    """A Frame's picture, (C,H,W) or (B,C,H,W), or a tensor, as the (B,C,H,W) guide of geometry.median_filter."""
+    if isinstance(guide, Frame):
+        guide = guide.data
+        if torch.is_tensor(guide) and guide.ndim == 3:
+            guide = guide[None]
+    return guide
+
 
 class Depth:
     def __init__(self, data: torch.Tensor, valid_mask: Optional[torch.Tensor] = None, is_inverse: bool = False):
@@ -384,6 +408,16 @@ class Depth:
         if rule not in rules:
             raise NndError(f"Depth.fill_holes: rule must be one of {tuple(rules)}; got {rule!r}")
         data, _, valid = geometry.fill_holes(self.data, self.valid_mask, True, rules[rule], vertical)
+        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
+        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
+
+    def median_filter(self, radius: int = 1, guide=None, sigma: float = 0.2, fill_invalid: bool = False, min_count: int = 1,
+                      **weights_kw) -> "Depth":
+        """`Disparity.median_filter` on a depth map: the median over the pixels with valid_mask == 1 and a finite depth.  The
+        returned valid_mask (dtype kept, uint8 if there was none) is 1 wherever the map now has a value."""
+        from . import geometry
+        data, valid = geometry.median_filter(self.data, radius, self.valid_mask, True, _guide_tensor(guide), sigma,
+                                             min_count=min_count, fill_invalid=fill_invalid, **weights_kw)
         valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
         return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
 
