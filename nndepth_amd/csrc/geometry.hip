@@ -16,7 +16,7 @@
 // Bandwidth-bound element-wise kernels of a few MB.  Compiled with -ffp-contract=off: every rounding step is written out, and
 // the contracts are closed forms that the tests match bit for bit.  Every global index is checked against the element count before
 // it is used; the one computed gather index (lr_consistency) lies in [0, W-1] by the tests that precede it.
-#include "common.h"
+#include "map_ops.h"  // the contract of map, stride and mask; the masks here are valid masks
 
 namespace nnd {
 
@@ -52,10 +52,10 @@ __global__ void __launch_bounds__(GEO_BLOCK) disparity_to_depth_kernel(const flo
     const float m = negative ? -d : d;
     const double fx = (double)cam[(long)b * cam_stride];
     const float z = (float)((fx * baseline) / (double)m);
-    bool ok = (!mask_in || mask_in[(long)b * per + i] != 0) && isfinite(m) && m > min_disp;
+    bool ok = mask_valid(mask_in, (long)b * per + i, 1) && isfinite(m) && m > min_disp;
     if (has_max) ok = ok && z <= max_depth;
     depth[(long)b * per + i] = ok ? z : 0.f;
-    valid_out[(long)b * per + i] = ok ? 1 : 0;
+    valid_out[(long)b * per + i] = mask_byte(ok, 1);
 }
 
 __global__ void __launch_bounds__(GEO_BLOCK) depth_to_disparity_kernel(const float* __restrict__ depth, long dbs,
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) depth_to_points_kernel(const float*
     const int b = blockIdx.y;
     const int v = (int)(i / W), u = (int)(i - (long)v * W);
     float X = 0.f, Y = 0.f, Z = 0.f;
-    if (!valid || valid[(long)b * per + i] != 0) {
+    if (mask_valid(valid, (long)b * per + i, 1)) {
         Z = depth[(long)b * dbs + i];
         back_project(load_cam(cam, cam_stride, b), u, v, Z, X, Y);
     }
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) compact_count_kernel(const unsigned
     __shared__ int wave_n[GEO_WAVES];
     const long i = (long)blockIdx.x * GEO_BLOCK + threadIdx.x;
     const int b = blockIdx.y;
-    const bool ok = i < per && (!valid || valid[(long)b * per + i] != 0);
+    const bool ok = i < per && mask_valid(valid, (long)b * per + i, 1);
     const unsigned long long bal = __ballot(ok);
     if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(bal);
     __syncthreads();
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) compact_write_kernel(const float* _
     __shared__ int wave_n[GEO_WAVES];
     const long i = (long)blockIdx.x * GEO_BLOCK + threadIdx.x;
     const int b = blockIdx.y;
-    const bool ok = i < per && (!valid || valid[(long)b * per + i] != 0);
+    const bool ok = i < per && mask_valid(valid, (long)b * per + i, 1);
     const unsigned long long bal = __ballot(ok);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) wave_n[wave] = __popcll(bal);
@@ -215,13 +215,12 @@ __global__ void __launch_bounds__(GEO_BLOCK) pair_both_views_kernel(const float*
     f2[j] = l;
 }
 
-// shape of a (B,1,H,W) map with a batch stride; blocks.x = workgroups per sample
-static int check_map(const char* what, int B, int H, int W, int64_t bstride, unsigned& blocks) {
-    NND_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0, "%s: bad shape (%d,1,%d,%d) (1 <= B <= 65535)", what, B, H, W);
-    const int64_t per = (int64_t)H * W;
-    NND_REQUIRE(bstride >= per, "%s: batch stride %lld is less than H*W = %lld", what, (long long)bstride, (long long)per);
-    NND_REQUIRE(cdiv64(per, GEO_BLOCK) <= 0x7fffffff, "%s: map too large", what);
-    blocks = (unsigned)cdiv64(per, GEO_BLOCK);
+// check_map, and blocks.x = workgroups per sample
+static int geo_blocks(const char* what, int B, int H, int W, int64_t bstride, unsigned& blocks) {
+    int rc;
+    NND_TRY(check_map(what, B, H, W, bstride));
+    NND_REQUIRE(cdiv64((int64_t)H * W, GEO_BLOCK) <= 0x7fffffff, "%s: map too large", what);
+    blocks = (unsigned)cdiv64((int64_t)H * W, GEO_BLOCK);
     return NND_OK;
 }
 
@@ -244,7 +243,7 @@ int nnd_disparity_to_depth(const float* disp, int64_t disp_bstride, const unsign
     int rc;
     unsigned blocks;
     NND_TRY(check_cam("disparity_to_depth", cam, cam_stride));
-    NND_TRY(check_map("disparity_to_depth", B, H, W, disp_bstride, blocks));
+    NND_TRY(geo_blocks("disparity_to_depth", B, H, W, disp_bstride, blocks));
     NND_REQUIRE(baseline == baseline && min_disp == min_disp && (!has_max || max_depth == max_depth),
                 "disparity_to_depth: baseline, min_disp or max_depth is NaN");
     hipLaunchKernelGGL(disparity_to_depth_kernel, dim3(blocks, B), dim3(GEO_BLOCK), 0, (hipStream_t)stream, disp, (long)disp_bstride,
@@ -260,7 +259,7 @@ int nnd_depth_to_disparity(const float* depth, int64_t depth_bstride, const floa
     int rc;
     unsigned blocks;
     NND_TRY(check_cam("depth_to_disparity", cam, cam_stride));
-    NND_TRY(check_map("depth_to_disparity", B, H, W, depth_bstride, blocks));
+    NND_TRY(geo_blocks("depth_to_disparity", B, H, W, depth_bstride, blocks));
     NND_REQUIRE(baseline == baseline && eps == eps, "depth_to_disparity: baseline or eps is NaN");
     hipLaunchKernelGGL(depth_to_disparity_kernel, dim3(blocks, B), dim3(GEO_BLOCK), 0, (hipStream_t)stream, depth, (long)depth_bstride,
                        cam, cam_stride, baseline, negative != 0, (float)eps, disp, (long)H * W);
@@ -274,7 +273,7 @@ int nnd_depth_to_points(const float* depth, int64_t depth_bstride, const unsigne
     int rc;
     unsigned blocks;
     NND_TRY(check_cam("depth_to_points", cam, cam_stride));
-    NND_TRY(check_map("depth_to_points", B, H, W, depth_bstride, blocks));
+    NND_TRY(geo_blocks("depth_to_points", B, H, W, depth_bstride, blocks));
     hipLaunchKernelGGL(depth_to_points_kernel, dim3(blocks, B), dim3(GEO_BLOCK), 0, (hipStream_t)stream, depth, (long)depth_bstride, valid,
                        cam, cam_stride, points, W, (long)H * W);
     NND_LAUNCH_CHECK();
@@ -283,7 +282,7 @@ int nnd_depth_to_points(const float* depth, int64_t depth_bstride, const unsigne
 
 // block_off (int64 per workgroup), then counts (int32 per workgroup)
 int64_t nnd_points_compact_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return (int64_t)NND_ERR_INVALID;
+    if (!map_shape_ok(B, H, W)) return (int64_t)NND_ERR_INVALID;
     return (int64_t)B * cdiv64((int64_t)H * W, GEO_BLOCK) * 12;
 }
 
@@ -294,12 +293,10 @@ int nnd_points_compact(const float* depth, int64_t depth_bstride, const unsigned
     int rc;
     unsigned blocks;
     NND_TRY(check_cam("points_compact", cam, cam_stride));
-    NND_TRY(check_map("points_compact", B, H, W, depth_bstride, blocks));
+    NND_TRY(geo_blocks("points_compact", B, H, W, depth_bstride, blocks));
     NND_REQUIRE((features == nullptr) == (feats_out == nullptr), "points_compact: features and feats_out go together");
     NND_REQUIRE(!features || C > 0, "points_compact: features of %d channels", C);
-    NND_REQUIRE(workspace_bytes >= nnd_points_compact_workspace_bytes(B, H, W), "points_compact: workspace of %lld bytes, %lld needed",
-                (long long)workspace_bytes, (long long)nnd_points_compact_workspace_bytes(B, H, W));
-    NND_REQUIRE(((size_t)workspace & 7) == 0, "points_compact: the workspace is not 8-byte aligned");
+    NND_TRY(check_workspace("points_compact", workspace, workspace_bytes, nnd_points_compact_workspace_bytes(B, H, W), 8));
     const long n = (long)B * blocks;
     long long* block_off = (long long*)workspace;
     int* counts = (int*)(block_off + n);
@@ -322,8 +319,8 @@ int nnd_lr_consistency(const float* disp_left, int64_t left_bstride, const float
     NND_REQUIRE(disp_left && disp_right && occluded, "lr_consistency: null pointer");
     int rc;
     unsigned blocks;
-    NND_TRY(check_map("lr_consistency", B, H, W, left_bstride, blocks));
-    NND_TRY(check_map("lr_consistency", B, H, W, right_bstride, blocks));
+    NND_TRY(geo_blocks("lr_consistency", B, H, W, left_bstride, blocks));
+    NND_TRY(geo_blocks("lr_consistency", B, H, W, right_bstride, blocks));
     NND_REQUIRE(W < (1 << 24), "lr_consistency: W = %d columns are not exact in fp32", W);
     NND_REQUIRE(threshold == threshold, "lr_consistency: the threshold is NaN");
     hipLaunchKernelGGL(lr_consistency_kernel, dim3(blocks, B), dim3(GEO_BLOCK), 0, (hipStream_t)stream, disp_left, (long)left_bstride,

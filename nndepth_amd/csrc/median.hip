@@ -29,7 +29,7 @@
 // (+ (2R+1)^2 * 512 bytes of tap weights for the large guided windows), which is what the launch asks for (med_lds_bytes); a weight
 // index is 0 .. 255 by construction (s < 255.0f ? (int)s : 255 with s >= 0 or NaN).
 #include <cstring>
-#include "common.h"
+#include "map_ops.h"  // the contract of map, stride, mask and its polarity, in and out
 
 namespace nnd {
 
@@ -259,7 +259,6 @@ __global__ void __launch_bounds__(MED_BLOCK, 2) median_kernel(const float* __res
     const int y0 = ((int)blockIdx.x / tiles_x) * MED_TH, x0 = ((int)blockIdx.x % tiles_x) * MED_TW;
     const long per = (long)H * W;
     const float* mp = map + (long)b * mbs;
-    const unsigned char* mk = mask ? mask + (long)b * per : nullptr;
 
     for (int i = tid; i < PA; i += MED_BLOCK) {
         const int gy = y0 - R + i / PW, gx = x0 - R + i % PW;
@@ -268,7 +267,7 @@ __global__ void __launch_bounds__(MED_BLOCK, 2) median_kernel(const float* __res
         if (in) {
             const long p = (long)gy * W + gx;
             const float v = mp[p];
-            if ((!mk || (mk[p] != 0) == (valid_is_one != 0)) && isfinite(v)) k = med_key(__float_as_uint(v));
+            if (map_ok(v, mask, (long)b * per + p, valid_is_one)) k = med_key(__float_as_uint(v));
             if (GUIDED)
                 for (int c = 0; c < C; ++c) gl[c * PA + i] = guide[((long)b * C + c) * per + p];
         } else if (GUIDED) {
@@ -298,17 +297,12 @@ __global__ void __launch_bounds__(MED_BLOCK, 2) median_kernel(const float* __res
         const unsigned out = produced ? med_unkey(sel) : ok ? med_unkey(centre) : __float_as_uint(fill);
         const long o = (long)b * per + (long)y * W + x;
         filtered[o] = __uint_as_float(out);
-        if (mask_out) mask_out[o] = ((ok || produced) == (valid_is_one != 0)) ? 1 : 0;
+        if (mask_out) mask_out[o] = mask_byte(ok || produced, valid_is_one);
         if (changed) {
             const unsigned was = ok ? med_unkey(centre) : __float_as_uint(mp[(long)y * W + x]);
             changed[o] = (out != was || (!ok && produced)) ? 1 : 0;
         }
     }
-}
-
-// B * H <= 2^25 as for the other map operations; the grid's x holds the tiles of a sample: < 2^31 for H * W < 2^31
-static bool med_shape_ok(int B, int H, int W) {
-    return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffff && (int64_t)B * H <= (1 << 25);
 }
 
 template <int R, bool GUIDED>
@@ -344,9 +338,10 @@ int nnd_median_filter(const float* map, int64_t map_bstride, const unsigned char
     const char* what = "median_filter";
     NND_REQUIRE(map && filtered, "%s: null pointer: no map or no filtered map", what);
     NND_REQUIRE(filtered != map, "%s: the filtered map must not be the input map", what);
-    NND_REQUIRE(med_shape_ok(B, H, W), "%s: bad shape (%d,1,%d,%d) (1 <= B <= 65535, H*W < 2^31, B*H <= 2^25)", what, B, H, W);
-    NND_REQUIRE(map_bstride >= (int64_t)H * W, "%s: batch stride %lld is less than H*W = %lld", what, (long long)map_bstride,
-                (long long)H * W);
+    int rc;
+    NND_TRY(check_map(what, B, H, W, map_bstride));
+    NND_REQUIRE((int64_t)H * W <= 0x7fffffff && (int64_t)B * H <= (1 << 25), "%s: bad shape (%d,1,%d,%d) (H*W < 2^31, B*H <= 2^25)", what,
+                B, H, W);  // the grid's x holds the tiles of a sample: < 2^31; B*H as for the operations by rows (warp.hip)
     NND_REQUIRE(radius >= 1 && radius <= MED_MAX_R, "%s: radius %d is outside 1 .. %d (nnd_median_filter_limit)", what, radius, MED_MAX_R);
     const int taps = (2 * radius + 1) * (2 * radius + 1);
     NND_REQUIRE(min_count >= 1 && min_count <= taps, "%s: min_count %d is outside 1 .. %d = (2 radius + 1)^2", what, min_count, taps);

@@ -32,7 +32,7 @@
 // Bounds.  A tile kernel thread touches global memory only at (y, x) with y < H and 0 <= x < W, checked where the index is formed.
 // An edge bit is only ever set between two pixels inside the image (a pixel outside it is staged as "invalid"), so the neighbour
 // index a set bit leads to needs no second check.  Labels are indices of valid pixels of the sample, or -1, which is never followed.
-#include "common.h"
+#include "map_ops.h"  // the contract of map, stride, mask and its polarity, in and out
 
 namespace nnd {
 
@@ -121,7 +121,6 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_tile_kernel(const float* __restri
     const int x0 = blockIdx.x * CC_TW, y0 = blockIdx.y * CC_TH;
     const long per = (long)H * W, base = (long)blockIdx.z * per;
     const float* m = map + (long)blockIdx.z * mbs;
-    const unsigned char* mk = mask ? mask + base : nullptr;
 
     for (int i = t; i < CC_VH * CC_VW; i += CC_BLOCK) {
         const int vy = i / CC_VW, vx = i - vy * CC_VW;
@@ -130,7 +129,7 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_tile_kernel(const float* __restri
         if (x >= 0 && x < W && y < H) {
             const long p = (long)y * W + x;
             const float d = m[p];
-            if (isfinite(d) && (!mk || (mk[p] != 0) == (valid_is_one != 0))) v = d;
+            if (map_ok(d, mask, base + p, valid_is_one)) v = d;
         }
         val[i] = v;
     }
@@ -295,7 +294,7 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_apply_kernel(const float* __restr
     if (speckle_out) speckle_out[p] = speckle ? 1 : 0;
     if (mask_out) {
         const bool keep = valid && !speckle;
-        mask_out[p] = (keep == (valid_is_one != 0)) ? 1 : 0;
+        mask_out[p] = mask_byte(keep, valid_is_one);
     }
 }
 
@@ -303,17 +302,14 @@ static int64_t cc_workspace_bytes(int64_t n) { return 8 * n + (n + 15) / 16 * 16
 
 static int cc_check(const char* what, const float* map, int64_t bstride, float max_diff, int connectivity, const void* workspace,
                     int64_t workspace_bytes, int B, int H, int W) {
+    int rc;
     NND_REQUIRE(map && workspace, "%s: null pointer", what);
-    NND_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffff && cdiv(H, CC_TH) <= 65535,
-                "%s: bad shape (%d,1,%d,%d) (1 <= B <= 65535, H <= %d, H*W < 2^31)", what, B, H, W, 65535 * CC_TH);
-    NND_REQUIRE(bstride >= (int64_t)H * W, "%s: batch stride %lld is less than H*W = %lld", what, (long long)bstride,
-                (long long)H * W);
+    NND_TRY(check_map(what, B, H, W, bstride));
+    NND_REQUIRE((int64_t)H * W <= 0x7fffffff, "%s: bad shape (%d,1,%d,%d): labels are int32, H*W < 2^31", what, B, H, W);
+    NND_REQUIRE(cdiv(H, CC_TH) <= 65535, "%s: bad shape (%d,1,%d,%d): 65535 tile rows, H <= %d", what, B, H, W, 65535 * CC_TH);
     NND_REQUIRE(max_diff >= 0.f, "%s: max_diff is negative or NaN", what);  // false for a NaN
     NND_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity %d is neither 4 nor 8", what, connectivity);
-    const int64_t need = cc_workspace_bytes((int64_t)B * H * W);
-    NND_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", what, (long long)workspace_bytes, (long long)need);
-    NND_REQUIRE(((size_t)workspace & 7) == 0, "%s: the workspace is not 8-byte aligned", what);
-    return NND_OK;
+    return check_workspace(what, workspace, workspace_bytes, cc_workspace_bytes((int64_t)B * H * W), 8);
 }
 
 static int cc_run(const float* map, int64_t bstride, const unsigned char* mask, int valid_is_one, float max_diff, int connectivity,
@@ -346,7 +342,7 @@ extern "C" {
 int nnd_connected_regions_tile(int which) { return which == 0 ? CC_TH : which == 1 ? CC_TW : (int)NND_ERR_INVALID; }
 
 int64_t nnd_connected_regions_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffff) return (int64_t)NND_ERR_INVALID;
+    if (!map_shape_ok(B, H, W) || (int64_t)H * W > 0x7fffffff) return (int64_t)NND_ERR_INVALID;
     return cc_workspace_bytes((int64_t)B * H * W);
 }
 

@@ -24,7 +24,7 @@
 //
 // Bounds.  Every global index is formed from (b, y, x) with b < B, y < H, x < W checked where it is formed; a column index read
 // from the keys, from `next` or from a ballot is the index of a pixel of the row that was found ok, or is not followed (-1 / 0).
-#include "common.h"
+#include "map_ops.h"  // the contract of map, stride, mask and its polarity, in and out
 
 namespace nnd {
 
@@ -45,7 +45,7 @@ __device__ __forceinline__ WarpSrc warp_source(const float* __restrict__ row, co
     WarpSrc s;
     const float d = row[x];
     s.m = (negative ? -d : d) + 0.0f;
-    const bool src_ok = (!mrow || (mrow[x] != 0) == (valid_is_one != 0)) && isfinite(s.m) && s.m >= 0.f;
+    const bool src_ok = mask_valid(mrow, x, valid_is_one) && isfinite(s.m) && s.m >= 0.f;
     const float xr = to_right ? (float)x - s.m : (float)x + s.m;
     const float t = rintf(xr);  // ties to even
     s.lands = src_ok && t >= 0.0f && t <= (float)(W - 1);
@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(WARP_BLOCK) warp_row_kernel(const float* __res
             const float mw = __uint_as_float((unsigned)(k >> 32));
             disp_other[o + x] = won ? (negative ? -mw : mw) : fill;
         }
-        if (valid_other) valid_other[o + x] = (won == (valid_is_one != 0)) ? 1 : 0;
+        if (valid_other) valid_other[o + x] = mask_byte(won, valid_is_one);
         if (source) source[o + x] = xs;
         if (features_other) {
             const long fo = (long)b * C * per + (long)y * W;
@@ -106,7 +106,7 @@ __device__ __forceinline__ bool fill_ok(const float* __restrict__ row, const uns
     v = 0.f;
     if (x >= W) return false;
     v = row[x];
-    return (!mrow || (mrow[x] != 0) == (valid_is_one != 0)) && isfinite(v);
+    return map_ok(v, mrow, x, valid_is_one);
 }
 
 // launch 1.  One wave per row, from the right.
@@ -136,7 +136,7 @@ __device__ __forceinline__ void fill_store(float* __restrict__ filled, unsigned 
                                            int valid_is_one, long p, float v, bool copied, bool valid) {
     filled[p] = v;
     if (was_filled) was_filled[p] = copied ? 1 : 0;
-    if (mask_out) mask_out[p] = (valid == (valid_is_one != 0)) ? 1 : 0;
+    if (mask_out) mask_out[p] = mask_byte(valid, valid_is_one);
 }
 
 // launch 2.  One wave per row, from the left.  ud[row] = {nearest non-empty row above, below} (-1: none) for an empty row.
@@ -227,10 +227,8 @@ __global__ void __launch_bounds__(FILL_BLOCK) fill_col_kernel(int valid_is_one, 
     fill_store(filled, was_filled, mask_out, valid_is_one, base + i, v, copied, copied);
 }
 
-// B * H <= 2^25: a launch with one wave (or one workgroup) per row stays below 2^32 threads
-static bool map_shape_ok(int B, int H, int W) {
-    return B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= 0x7fffffff && (int64_t)B * H <= (1 << 25);
-}
+// beyond check_map: a pixel index of a sample is an int, and a launch of one wave (or one workgroup) per row stays below 2^32 threads
+static bool rows_ok(int B, int H, int W) { return (int64_t)H * W <= 0x7fffffff && (int64_t)B * H <= (1 << 25); }
 
 static int64_t fill_workspace_bytes(int B, int H, int W) {  // next: a word per row and chunk; ud: two words per row
     const int64_t words = (int64_t)B * H * (cdiv(W, FILL_CHUNK) + 2);
@@ -250,11 +248,11 @@ int nnd_warp_disparity(const float* disp, int64_t disp_bstride, const unsigned c
                        unsigned char* valid_other, unsigned char* occluded, int32_t* source, float* features_other, int B, int H, int W,
                        void* stream) {
     const char* what = "warp_disparity";
+    int rc;
     NND_REQUIRE(disp, "%s: null pointer: no map", what);
-    NND_REQUIRE(map_shape_ok(B, H, W), "%s: bad shape (%d,1,%d,%d) (1 <= B <= 65535, H*W < 2^31, B*H <= 2^25)", what, B, H, W);
+    NND_TRY(check_map(what, B, H, W, disp_bstride));
+    NND_REQUIRE(rows_ok(B, H, W), "%s: bad shape (%d,1,%d,%d) (H*W < 2^31, B*H <= 2^25)", what, B, H, W);
     NND_REQUIRE(W <= WARP_MAX_W, "%s: a width of %d is above the maximum width %d (nnd_warp_disparity_limit)", what, W, WARP_MAX_W);
-    NND_REQUIRE(disp_bstride >= (int64_t)H * W, "%s: batch stride %lld is less than H*W = %lld", what, (long long)disp_bstride,
-                (long long)H * W);
     NND_REQUIRE(threshold >= 0.f, "%s: threshold is negative or NaN", what);  // false for a NaN
     NND_REQUIRE(disp_other || valid_other || occluded || source || features_other, "%s: null pointer: no output is asked for", what);
     NND_REQUIRE(C >= 0 && (int64_t)C * H * W <= 0x7fffffff, "%s: bad feature channels %d (0 <= C, C*H*W < 2^31)", what, C);
@@ -270,7 +268,7 @@ int nnd_warp_disparity(const float* disp, int64_t disp_bstride, const unsigned c
 int nnd_fill_holes_chunk(void) { return FILL_CHUNK; }
 
 int64_t nnd_fill_holes_workspace_bytes(int B, int H, int W) {
-    if (!map_shape_ok(B, H, W)) return (int64_t)NND_ERR_INVALID;
+    if (!map_shape_ok(B, H, W) || !rows_ok(B, H, W)) return (int64_t)NND_ERR_INVALID;
     return fill_workspace_bytes(B, H, W);
 }
 
@@ -280,14 +278,12 @@ int nnd_fill_holes(const float* map, int64_t map_bstride, const unsigned char* m
     const char* what = "fill_holes";
     NND_REQUIRE(map && workspace, "%s: null pointer: no map or no workspace", what);
     NND_REQUIRE(filled, "%s: null pointer: no filled map (the column pass reads it)", what);
-    NND_REQUIRE(map_shape_ok(B, H, W), "%s: bad shape (%d,1,%d,%d) (1 <= B <= 65535, H*W < 2^31, B*H <= 2^25)", what, B, H, W);
-    NND_REQUIRE(map_bstride >= (int64_t)H * W, "%s: batch stride %lld is less than H*W = %lld", what, (long long)map_bstride,
-                (long long)H * W);
+    int rc;
+    NND_TRY(check_map(what, B, H, W, map_bstride));
+    NND_REQUIRE(rows_ok(B, H, W), "%s: bad shape (%d,1,%d,%d) (H*W < 2^31, B*H <= 2^25)", what, B, H, W);
     NND_REQUIRE(rule == RULE_MIN_ABS || rule == RULE_MAX_ABS || rule == RULE_NEAREST, "%s: unknown rule %d (0 min_abs, 1 max_abs, 2 nearest)",
                 what, rule);
-    const int64_t need = fill_workspace_bytes(B, H, W);
-    NND_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", what, (long long)workspace_bytes, (long long)need);
-    NND_REQUIRE(((size_t)workspace & 3) == 0, "%s: the workspace is not 4-byte aligned", what);
+    NND_TRY(check_workspace(what, workspace, workspace_bytes, fill_workspace_bytes(B, H, W), 4));
     NND_REQUIRE(filled != map, "%s: the filled map must not be the input map", what);
     const hipStream_t s = (hipStream_t)stream;
     const int nch = cdiv(W, FILL_CHUNK);

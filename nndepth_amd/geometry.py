@@ -29,18 +29,25 @@ from .ops import _p, _stream
 _SIGNS = ("negative", "positive")
 
 
-def _map4(t, what: str, mask=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+def _is_map(t: torch.Tensor) -> bool:
+    return t.ndim == 4 and t.shape[1] == 1 and t.numel() > 0
+
+
+def _map4(t, what: str, mask=None, shape_first: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The (B,1,H,W) fp32 device map `t` with dense rows (its batch stride is kept; anything else is made contiguous) and its
-    bool / uint8 mask, (B,1,H,W) or (B,H,W), as contiguous bytes (None stays None)."""
+    bool / uint8 mask, (B,1,H,W) or (B,H,W), as contiguous bytes (None stays None).  The refusals come in this order; with
+    `shape_first` (the warp, fill and median families) a wrong shape is named as such whatever the mask and the device."""
     if not torch.is_tensor(t):
         raise NndError(f"{what}: the map must be a tensor on the HIP device; got {type(t).__name__}")
     if t.dtype != torch.float32:
         raise NndError(f"{what}: maps are torch.float32; got {t.dtype}")
+    if shape_first and not _is_map(t):
+        raise NndError(f"{what}: a map is (B,1,H,W); got {tuple(t.shape)}")
     if mask is not None and (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8)):
         raise NndError(f"{what}: masks are torch.bool or torch.uint8; got {getattr(mask, 'dtype', type(mask).__name__)}")
     if t.device.type != "cuda":
         raise NndError(f"{what}: the map must be on the HIP device (got {t.device}); there is no CPU fallback")
-    if t.ndim != 4 or t.shape[1] != 1 or t.numel() == 0:
+    if not _is_map(t):
         raise NndError(f"{what}: a map is (B,1,H,W); got {tuple(t.shape)}")
     B, _, H, W = t.shape
     if not (t.stride(3) == 1 and t.stride(2) == W and (B == 1 or t.stride(0) >= H * W)):
@@ -55,8 +62,40 @@ def _map4(t, what: str, mask=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]
     return t, mask
 
 
+def _nbytes(sizer: str, B: int, H: int, W: int, what: str) -> int:
+    """What the library's `sizer` asks for a (B,1,H,W) map; a shape it refuses is refused here under the name `what`."""
+    nbytes = int(getattr(lib, sizer)(int(B), int(H), int(W)))
+    if nbytes < 0:
+        check(nbytes, what)
+    return nbytes
+
+
 def _bstride(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else t.shape[2] * t.shape[3]
+
+
+def _features(features, B: int, H: int, W: int, device: torch.device, what: str) -> Tuple[Optional[torch.Tensor], int]:
+    """(the (B,C,H,W) fp32 features beside a (B,1,H,W) map on `device`, contiguous; C), or (None, 0)"""
+    if features is None:
+        return None, 0
+    if not torch.is_tensor(features) or features.dtype != torch.float32:
+        raise NndError(f"{what}: features are torch.float32; got {getattr(features, 'dtype', type(features).__name__)}")
+    if features.device != device:
+        raise NndError(f"{what}: the features are on {features.device}, the map on {device} (no CPU fallback exists)")
+    if features.ndim != 4 or features.shape[0] != B or tuple(features.shape[2:]) != (H, W) or features.shape[1] < 1:
+        raise NndError(f"{what}: features are (B,C,H,W) = ({B},C,{H},{W}); got {tuple(features.shape)}")
+    return features.contiguous(), features.shape[1]
+
+
+def _workspace(nbytes: int, workspace, dtype: torch.dtype, device: torch.device, what: str, sizer_name: str) -> torch.Tensor:
+    """The caller's workspace if it holds `nbytes` device bytes, a fresh one of `dtype` words if there is none."""
+    if workspace is None:
+        return torch.empty(-(-nbytes // dtype.itemsize), dtype=dtype, device=device)
+    if not torch.is_tensor(workspace) or workspace.device != device or not workspace.is_contiguous():
+        raise NndError(f"{what}: the workspace must be a contiguous tensor on {device}")
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise NndError(f"{what}: a workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed ({sizer_name})")
+    return workspace
 
 
 def _sign(sign: str, what: str) -> int:
@@ -149,22 +188,10 @@ def points_compact(depth: torch.Tensor, camera, valid_mask: Optional[torch.Tenso
     what = "points_compact"
     z, m = _map4(depth, what, valid_mask)
     B, _, H, W = z.shape
-    feats = None
-    Cf = 0
-    if features is not None:
-        if not torch.is_tensor(features) or features.dtype != torch.float32:
-            raise NndError(f"{what}: features are torch.float32; got {getattr(features, 'dtype', type(features).__name__)}")
-        if features.device != z.device:
-            raise NndError(f"{what}: the features are on {features.device}, the map on {z.device} (no CPU fallback exists)")
-        if features.ndim != 4 or features.shape[0] != B or tuple(features.shape[2:]) != (H, W) or features.shape[1] < 1:
-            raise NndError(f"{what}: features are (B,C,H,W) = ({B},C,{H},{W}); got {tuple(features.shape)}")
-        features = features.contiguous()
-        Cf = features.shape[1]
-        feats = torch.empty((B * H * W, Cf), dtype=torch.float32, device=z.device)
+    features, Cf = _features(features, B, H, W, z.device, what)
+    feats = torch.empty((B * H * W, Cf), dtype=torch.float32, device=z.device) if Cf else None
     cam, cs = camera_params(camera, B, z.device, what, fx_only=False)
-    nbytes = int(lib.nnd_points_compact_workspace_bytes(B, H, W))
-    if nbytes < 0:
-        check(nbytes, what)
+    nbytes = _nbytes("nnd_points_compact_workspace_bytes", B, H, W, what)
     ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=z.device)
     points = torch.empty((B * H * W, 3), dtype=torch.float32, device=z.device)
     offsets = torch.empty(B + 1, dtype=torch.int64, device=z.device)
@@ -200,27 +227,9 @@ def lr_consistency(disp_left: torch.Tensor, disp_right: torch.Tensor, threshold:
     return (occ, err) if return_error else occ
 
 
-def _regions_workspace(d: torch.Tensor, workspace: Optional[torch.Tensor], what: str) -> torch.Tensor:
-    B, _, H, W = d.shape
-    nbytes = int(lib.nnd_connected_regions_workspace_bytes(B, H, W))
-    if nbytes < 0:
-        check(nbytes, what)
-    if workspace is None:
-        return torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=d.device)
-    if not torch.is_tensor(workspace) or workspace.device != d.device or not workspace.is_contiguous():
-        raise NndError(f"{what}: the workspace must be a contiguous tensor on {d.device}")
-    if workspace.numel() * workspace.element_size() < nbytes:
-        raise NndError(f"{what}: a workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed "
-                       "(regions_workspace_bytes)")
-    return workspace
-
-
 def regions_workspace_bytes(B: int, H: int, W: int) -> int:
     """Device bytes `connected_regions` / `speckle_filter` need for a (B,1,H,W) map (9 per pixel); 8-byte aligned."""
-    nbytes = int(lib.nnd_connected_regions_workspace_bytes(int(B), int(H), int(W)))
-    if nbytes < 0:
-        check(nbytes, "regions_workspace_bytes")
-    return nbytes
+    return _nbytes("nnd_connected_regions_workspace_bytes", B, H, W, "regions_workspace_bytes")
 
 
 def regions_tile() -> Tuple[int, int]:
@@ -234,11 +243,11 @@ def _connectivity(connectivity, what: str) -> int:
     return int(connectivity)
 
 
-def _max_diff(max_diff, what: str) -> float:
-    max_diff = float(max_diff)
-    if not max_diff >= 0.0:
-        raise NndError(f"{what}: max_diff must be >= 0 (+inf is allowed); got {max_diff}")
-    return max_diff
+def _at_least_0(value, name: str, what: str) -> float:
+    value = float(value)
+    if not value >= 0.0:
+        raise NndError(f"{what}: {name} must be >= 0 (+inf is allowed); got {value}")
+    return value
 
 
 def connected_regions(map: torch.Tensor, max_diff: float, valid_mask: Optional[torch.Tensor] = None, connectivity: int = 4,
@@ -250,10 +259,11 @@ def connected_regions(map: torch.Tensor, max_diff: float, valid_mask: Optional[t
     host synchronisation, the same bytes on every run.  `workspace`: a device tensor of `regions_workspace_bytes(B,H,W)` bytes
     to reuse across calls (what a graph capture wants); allocated per call if None."""
     what = "connected_regions"
-    conn, md = _connectivity(connectivity, what), _max_diff(max_diff, what)
+    conn, md = _connectivity(connectivity, what), _at_least_0(max_diff, "max_diff", what)
     d, m = _map4(map, what, valid_mask)
     B, _, H, W = d.shape
-    ws = _regions_workspace(d, workspace, what)
+    nbytes = _nbytes("nnd_connected_regions_workspace_bytes", B, H, W, what)
+    ws = _workspace(nbytes, workspace, torch.int64, d.device, what, "regions_workspace_bytes")
     labels = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device)
     sizes = torch.empty((B, 1, H, W), dtype=torch.int32, device=d.device)
     with torch.cuda.device(d.device):
@@ -270,12 +280,13 @@ def speckle_filter(map: torch.Tensor, max_size: int, max_diff: float = 1.0, mask
     as in `connected_regions`); filtered = speckle ? fill : map, every other pixel bit for bit; mask_out, in the polarity of
     `mask`, flags as invalid what was invalid (masked out or not finite) or is a speckle."""
     what = "speckle_filter"
-    conn, md = _connectivity(connectivity, what), _max_diff(max_diff, what)
+    conn, md = _connectivity(connectivity, what), _at_least_0(max_diff, "max_diff", what)
     if isinstance(max_size, bool) or not isinstance(max_size, int) or max_size < 0:
         raise NndError(f"{what}: max_size must be an integer >= 0; got {max_size!r}")
     d, m = _map4(map, what, mask)
     B, _, H, W = d.shape
-    ws = _regions_workspace(d, workspace, what)
+    nbytes = _nbytes("nnd_connected_regions_workspace_bytes", B, H, W, what)
+    ws = _workspace(nbytes, workspace, torch.int64, d.device, what, "regions_workspace_bytes")
     filtered = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
     mask_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
     speckle = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
@@ -317,16 +328,7 @@ def fill_chunk() -> int:
 
 def fill_workspace_bytes(B: int, H: int, W: int) -> int:
     """Device bytes `fill_holes` needs for a (B,1,H,W) map (a word per row and chunk, two per row); 4-byte aligned."""
-    nbytes = int(lib.nnd_fill_holes_workspace_bytes(int(B), int(H), int(W)))
-    if nbytes < 0:
-        check(nbytes, "fill_workspace_bytes")
-    return nbytes
-
-
-def _shape_first(t, what: str):
-    """A wrong shape is named as such whatever the device (`_map4` names the device first)."""
-    if torch.is_tensor(t) and t.dtype == torch.float32 and (t.ndim != 4 or t.shape[1] != 1 or t.numel() == 0):
-        raise NndError(f"{what}: a map is (B,1,H,W); got {tuple(t.shape)}")
+    return _nbytes("nnd_fill_holes_workspace_bytes", B, H, W, "fill_workspace_bytes")
 
 
 def _warp(what: str, disp, disp_sign, to_view, threshold, mask, mask_is_valid, features, fill, want_source):
@@ -334,26 +336,13 @@ def _warp(what: str, disp, disp_sign, to_view, threshold, mask, mask_is_valid, f
     neg = _sign(disp_sign, what)
     if to_view not in _VIEWS:
         raise NndError(f"{what}: to_view must be 'right' or 'left'; got {to_view!r}")
-    threshold = float(threshold)
-    if not threshold >= 0.0:
-        raise NndError(f"{what}: threshold must be >= 0 (+inf is allowed); got {threshold}")
-    _shape_first(disp, what)
-    d, m = _map4(disp, what, mask)
+    threshold = _at_least_0(threshold, "threshold", what)
+    d, m = _map4(disp, what, mask, shape_first=True)
     B, _, H, W = d.shape
     if W > warp_max_width():
         raise NndError(f"{what}: a width of {W} is above the maximum width {warp_max_width()} (warp_max_width)")
-    Cf = 0
-    feats = None
-    if features is not None:
-        if not torch.is_tensor(features) or features.dtype != torch.float32:
-            raise NndError(f"{what}: features are torch.float32; got {getattr(features, 'dtype', type(features).__name__)}")
-        if features.device != d.device:
-            raise NndError(f"{what}: the features are on {features.device}, the map on {d.device} (no CPU fallback exists)")
-        if features.ndim != 4 or features.shape[0] != B or tuple(features.shape[2:]) != (H, W) or features.shape[1] < 1:
-            raise NndError(f"{what}: features are (B,C,H,W) = ({B},C,{H},{W}); got {tuple(features.shape)}")
-        features = features.contiguous()
-        Cf = features.shape[1]
-        feats = torch.empty((B, Cf, H, W), dtype=torch.float32, device=d.device)
+    features, Cf = _features(features, B, H, W, d.device, what)
+    feats = torch.empty((B, Cf, H, W), dtype=torch.float32, device=d.device) if Cf else None
     other = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
     valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
     occ = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
@@ -399,17 +388,9 @@ def fill_holes(map: torch.Tensor, mask: Optional[torch.Tensor] = None, mask_is_v
     what = "fill_holes"
     if rule not in _RULES:
         raise NndError(f"{what}: rule must be one of {_RULES}; got {rule!r}")
-    _shape_first(map, what)
-    d, m = _map4(map, what, mask)
+    d, m = _map4(map, what, mask, shape_first=True)
     B, _, H, W = d.shape
-    nbytes = fill_workspace_bytes(B, H, W)
-    if workspace is None:
-        workspace = torch.empty(nbytes // 4, dtype=torch.int32, device=d.device)
-    elif not torch.is_tensor(workspace) or workspace.device != d.device or not workspace.is_contiguous():
-        raise NndError(f"{what}: the workspace must be a contiguous tensor on {d.device}")
-    elif workspace.numel() * workspace.element_size() < nbytes:
-        raise NndError(f"{what}: a workspace of {workspace.numel() * workspace.element_size()} bytes, {nbytes} needed "
-                       "(fill_workspace_bytes)")
+    workspace = _workspace(fill_workspace_bytes(B, H, W), workspace, torch.int32, d.device, what, "fill_workspace_bytes")
     filled = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)
     was = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
     mask_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
@@ -434,6 +415,13 @@ def median_tile() -> Tuple[int, int]:
     return int(lib.nnd_median_filter_limit(1)), int(lib.nnd_median_filter_limit(2))
 
 
+def _step(sigma, step, what: str) -> float:
+    step = float(sigma) / 32 if step is None else float(step)
+    if not (step > 0.0 and step < float("inf")):
+        raise NndError(f"{what}: step must be finite and > 0; got {step}")
+    return step
+
+
 def range_weights(sigma: float, step: Optional[float] = None, kind: str = "exp"):
     """(numpy uint16[256], inv_step) for `median_filter`: w[b] = floor(65535 * f(b * step) + 0.5) in float64 with f(d) =
     exp(-d / sigma) ("exp"), exp(-d^2 / (2 sigma^2)) ("gauss") or d <= sigma ("box"); `step`, the guide distance one entry of the
@@ -445,9 +433,7 @@ def range_weights(sigma: float, step: Optional[float] = None, kind: str = "exp")
     sigma = float(sigma)
     if not (sigma > 0.0 and sigma < float("inf")):
         raise NndError(f"{what}: sigma must be finite and > 0; got {sigma}")
-    step = sigma / 32 if step is None else float(step)
-    if not (step > 0.0 and step < float("inf")):
-        raise NndError(f"{what}: step must be finite and > 0; got {step}")
+    step = _step(sigma, step, what)
     d = np.arange(256, dtype=np.float64) * step
     f = np.exp(-d / sigma) if kind == "exp" else np.exp(-d * d / (2.0 * sigma * sigma)) if kind == "gauss" else (d <= sigma).astype(np.float64)
     return np.floor(65535.0 * f + 0.5).astype(np.uint16), float(np.float32(1.0 / step))
@@ -480,14 +466,13 @@ def median_filter(map: torch.Tensor, radius: int = 1, valid_mask: Optional[torch
     into a graph.  radius 1 .. `median_max_radius()`, min_count 1 .. (2r+1)^2.  No CPU fallback."""
     import numpy as np
     what = "median_filter"
-    _shape_first(map, what)
-    if guide is not None and torch.is_tensor(map) and map.dtype == torch.float32:  # named whatever the device, like a wrong shape
+    if guide is not None and torch.is_tensor(map) and map.dtype == torch.float32 and _is_map(map):  # named whatever the device
         if not torch.is_tensor(guide) or guide.dtype != torch.float32:
             raise NndError(f"{what}: the guide is torch.float32; got {guide.dtype if torch.is_tensor(guide) else type(guide).__name__}")
         B, _, H, W = map.shape
         if guide.ndim != 4 or guide.shape[0] != B or tuple(guide.shape[2:]) != (H, W) or not 1 <= guide.shape[1] <= 4:
             raise NndError(f"{what}: the guide is (B,C,H,W) = ({B},1..4,{H},{W}); got {tuple(guide.shape)}")
-    d, m = _map4(map, what, valid_mask)
+    d, m = _map4(map, what, valid_mask, shape_first=True)
     B, _, H, W = d.shape
     radius, min_count = int(radius), int(min_count)
     if not 1 <= radius <= median_max_radius():
@@ -508,10 +493,7 @@ def median_filter(map: torch.Tensor, radius: int = 1, valid_mask: Optional[torch
                 raise NndError(f"{what}: weights are 256 uint16 values; got {table.dtype} {table.shape}")
             if table[0] == 0:
                 raise NndError(f"{what}: weights[0] is 0: the centre tap must count")
-            step = float(sigma) / 32 if step is None else float(step)
-            if not (step > 0.0 and step < float("inf")):
-                raise NndError(f"{what}: step must be finite and > 0; got {step}")
-            inv_step = float(np.float32(1.0 / step))
+            inv_step = float(np.float32(1.0 / _step(sigma, step, what)))
     elif weights is not None:
         raise NndError(f"{what}: weights without a guide")
     filtered = torch.empty((B, 1, H, W), dtype=torch.float32, device=d.device)

@@ -123,8 +123,9 @@ def _align(kwargs: dict, what: str) -> bool:
     return bool(kwargs.get("align_corners", False))
 
 
-def _as_dtype(b: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    return b.view(torch.bool) if dtype == torch.bool else b
+def _mask_like(new: torch.Tensor, old: Optional[torch.Tensor]) -> torch.Tensor:
+    """The new uint8 mask in the old mask's dtype, uint8 if there was none."""
+    return new.view(torch.bool) if old is not None and old.dtype == torch.bool else new
 
 
 def _pool_kernel(HW, size, what: str) -> Tuple[int, int]:
@@ -202,7 +203,7 @@ class Disparity:
             data, _ = ops.resize_bilinear(self.data, size, align, rescale=rescale)
             if self.occlusion is not None:
                 occ = ops.resize_bilinear(self.occlusion, size, align, u8_mode=1 if self.occlusion.dtype == torch.bool else 2)
-                occlusion = _as_dtype(occ, self.occlusion.dtype)
+                occlusion = _mask_like(occ, self.occlusion)
         else:
             assert self.disp_sign in ("positive", "negative"), "disp_sign must be either 'positive' or 'negative'"
             H, W = self.data.shape[-2:]
@@ -218,7 +219,7 @@ class Disparity:
             if not exact:
                 data, _ = ops.resize_bilinear(data, size, align, rescale=rescale)
             if occ is not None:
-                occlusion = _as_dtype(occ, self.occlusion.dtype)
+                occlusion = _mask_like(occ, self.occlusion)
         for _ in range(missing_dim):
             data = data[0]
             if occlusion is not None:
@@ -256,8 +257,7 @@ class Disparity:
         old one, the non-finite pixels and the removed ones.  (B,1,H,W) maps; not a method of the reference."""
         from . import geometry
         data, occ, _ = geometry.speckle_filter(self.data, max_size, max_diff, self.occlusion, False, connectivity, fill)
-        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
-        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=_mask_like(occ, self.occlusion), baseline=self.baseline)
 
     _FILL_RULES = {"background": "min_abs", "foreground": "max_abs", "nearest": "nearest"}
 
@@ -270,8 +270,7 @@ class Disparity:
         from . import geometry
         data, hole, _, _, feats = geometry._warp("Disparity.to_other_view", self.data, self.disp_sign, to, threshold, self.occlusion,
                                                  False, features, 0.0, False)
-        hole = hole if self.occlusion is None else _as_dtype(hole, self.occlusion.dtype)
-        out = Disparity(data=data, disp_sign=self.disp_sign, occlusion=hole, baseline=self.baseline)
+        out = Disparity(data=data, disp_sign=self.disp_sign, occlusion=_mask_like(hole, self.occlusion), baseline=self.baseline)
         return out if features is None else (out, feats)
 
     def warp_occlusion(self, threshold: float = 1.0) -> "Disparity":
@@ -283,8 +282,7 @@ class Disparity:
         from . import geometry
         occ = geometry._warp("Disparity.warp_occlusion", self.data, self.disp_sign, "right", threshold, self.occlusion, False, None,
                              0.0, False)[2]
-        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
-        return Disparity(data=self.data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+        return Disparity(data=self.data, disp_sign=self.disp_sign, occlusion=_mask_like(occ, self.occlusion), baseline=self.baseline)
 
     def fill_holes(self, rule: str = "background", vertical: bool = True) -> "Disparity":
         """A dense map (geometry.fill_holes): occluded or non-finite pixels take the value of the nearest valid pixel of their row
@@ -295,8 +293,7 @@ class Disparity:
         if rule not in self._FILL_RULES:
             raise NndError(f"Disparity.fill_holes: rule must be one of {tuple(self._FILL_RULES)}; got {rule!r}")
         data, _, occ = geometry.fill_holes(self.data, self.occlusion, False, self._FILL_RULES[rule], vertical)
-        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
-        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=_mask_like(occ, self.occlusion), baseline=self.baseline)
 
     def median_filter(self, radius: int = 1, guide=None, sigma: float = 0.2, fill_invalid: bool = False, min_count: int = 1,
                       **weights_kw) -> "Disparity":
@@ -309,8 +306,7 @@ class Disparity:
         from . import geometry
         data, occ = geometry.median_filter(self.data, radius, self.occlusion, False, _guide_tensor(guide), sigma,
                                            min_count=min_count, fill_invalid=fill_invalid, **weights_kw)
-        occ = occ if self.occlusion is None else _as_dtype(occ, self.occlusion.dtype)
-        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=occ, baseline=self.baseline)
+        return Disparity(data=data, disp_sign=self.disp_sign, occlusion=_mask_like(occ, self.occlusion), baseline=self.baseline)
 
 
 def _guide_tensor(guide):
@@ -355,7 +351,7 @@ class Depth:
             data, _, _, fin = ops.pool_abs(self.data, (kh, kw), method == "minpool", False, finite=want and exact)
             if not exact:
                 data, fin = ops.resize_bilinear(data, size, align, finite=want)
-        valid_mask = _as_dtype(fin, self.valid_mask.dtype) if want else None
+        valid_mask = _mask_like(fin, self.valid_mask) if want else None
         for _ in range(missing_dim):
             data = data[0]
             if valid_mask is not None:
@@ -395,8 +391,7 @@ class Depth:
         no longer holds them."""
         from . import geometry
         data, valid, _ = geometry.speckle_filter(self.data, max_size, max_diff, self.valid_mask, True, connectivity, fill)
-        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
-        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
+        return Depth(data=data, valid_mask=_mask_like(valid, self.valid_mask), is_inverse=self.is_inverse)
 
     def fill_holes(self, rule: str = "background", vertical: bool = True) -> "Depth":
         """`Disparity.fill_holes` on a depth map: "background" is the LARGER depth (the smaller value when is_inverse),
@@ -408,8 +403,7 @@ class Depth:
         if rule not in rules:
             raise NndError(f"Depth.fill_holes: rule must be one of {tuple(rules)}; got {rule!r}")
         data, _, valid = geometry.fill_holes(self.data, self.valid_mask, True, rules[rule], vertical)
-        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
-        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
+        return Depth(data=data, valid_mask=_mask_like(valid, self.valid_mask), is_inverse=self.is_inverse)
 
     def median_filter(self, radius: int = 1, guide=None, sigma: float = 0.2, fill_invalid: bool = False, min_count: int = 1,
                       **weights_kw) -> "Depth":
@@ -418,8 +412,7 @@ class Depth:
         from . import geometry
         data, valid = geometry.median_filter(self.data, radius, self.valid_mask, True, _guide_tensor(guide), sigma,
                                              min_count=min_count, fill_invalid=fill_invalid, **weights_kw)
-        valid = valid if self.valid_mask is None else _as_dtype(valid, self.valid_mask.dtype)
-        return Depth(data=data, valid_mask=valid, is_inverse=self.is_inverse)
+        return Depth(data=data, valid_mask=_mask_like(valid, self.valid_mask), is_inverse=self.is_inverse)
 
     def to_points_map(self, camera) -> torch.Tensor:
         """(B,3,H,W): X = fp32((u - cx) * Z / fx), Y = fp32((v - cy) * Z / fy), arithmetic in double, Z copied;

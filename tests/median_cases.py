@@ -14,14 +14,11 @@ import numpy as np
 import speckle_cases as S
 
 F32 = np.float32
+bits = S.bits
 BAD = np.int64(0xFFFFFFFF)
 GOLDEN_SHAPE = (2, 1, 9, 40)
 SHAPES = [(1, 1, 1, 1), (1, 1, 1, 2), (2, 1, 3, 5), (3, 1, 6, 9), (2, 1, 9, 40)]  # + (2, 1, tileH + 3, 2 * tileW + 3), from the library
 SMALL = (2, 1, 5, 7)  # smaller than the window of radius 7 in both directions
-
-
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 def keys_of(d) -> np.ndarray:

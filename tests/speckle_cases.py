@@ -22,6 +22,11 @@ def rng(seed: int) -> np.random.Generator:
     return np.random.Generator(np.random.PCG64(seed))
 
 
+def bits(a) -> np.ndarray:
+    """The bit patterns of fp32 values: what "bit for bit" compares (warp_cases and median_cases use it under their own names)."""
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the oracle
 def valid_of(d: np.ndarray, mask=None, mask_is_valid: bool = True) -> np.ndarray:
     ok = np.isfinite(d)

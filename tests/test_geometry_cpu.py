@@ -3,49 +3,25 @@ the exports and the ctypes table agree on its names; every entry point validates
 refuses by name what the kernels do not compute; and the oracles of tests/geometry_cases.py reproduce tests/golden/geometry.npz
 (scripts/make_golden_geometry.py), whose to_disparity part is the reference's own TartanAir expression."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import geometry_cases as G
+from cabi_checks import header_exports_ctypes_table_and_makefile_rule_agree, refused
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nnd_disparity_to_depth", "nnd_depth_to_disparity", "nnd_depth_to_points", "nnd_points_compact_workspace_bytes",
          "nnd_points_compact", "nnd_lr_consistency", "nnd_pair_both_views")
 
 
 def test_header_exports_and_ctypes_table_agree_on_the_new_names():
-    from nndepth_amd import _lib
-    header = open(os.path.join(ROOT, "include", "nndepth_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        proto = re.search(rf"\b(int64_t|int)\s+{name}\s*\(([^;]*)\)\s*;", code)
-        assert proto, f"{name} is not declared in include/nndepth_amd.h"
-        assert hasattr(raw, name), f"{name} is not exported"
-        res, args = _lib.SIGNATURES[name]
-        assert res is (C.c_int64 if proto.group(1) == "int64_t" else C.c_int)
-        params = [p.strip() for p in proto.group(2).split(",")]
-        assert len(params) == len(args), f"{name}: {len(params)} parameters declared, {len(args)} in the ctypes table"
-        for p, a in zip(params, args):  # pointer / integer / floating kinds agree, parameter by parameter
-            want = C.c_void_p if "*" in p else {"int64_t": C.c_int64, "int": C.c_int, "double": C.c_double,
-                                                "float": C.c_float}[p.split()[0]]
-            assert a is want, f"{name}: `{p}` is {a.__name__} in the ctypes table"
-    mk = open(os.path.join(ROOT, "nndepth_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^OBJS\s*=.*\bgeometry\.o\b", mk, re.M)
-    rule = re.search(r"^geometry\.o:.*\n\t(.*)$", mk, re.M)
-    assert rule and "$(NOSLP)" in rule.group(1) and "-ffp-contract=off" in rule.group(1)
+    header_exports_ctypes_table_and_makefile_rule_agree(NAMES, "geometry")
 
 
 def test_entry_points_validate_before_any_device_call():
     from nndepth_amd._lib import lib
     one = C.c_void_p(16)  # never dereferenced: every call below is refused first
-
-    def refused(rc, word):
-        assert rc < 0 and word in lib.nnd_last_error(), (rc, lib.nnd_last_error())
 
     refused(lib.nnd_disparity_to_depth(None, 35, None, one, 0, 0.25, 1, 0.0, 0, 0.0, None, None, 1, 5, 7, None), b"null")
     refused(lib.nnd_disparity_to_depth(one, 35, None, None, 0, 0.25, 1, 0.0, 0, 0.0, one, one, 1, 5, 7, None), b"camera")

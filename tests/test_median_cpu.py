@@ -6,13 +6,13 @@ wrote."""
 import ctypes as C
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import median_cases as Mc
+from cabi_checks import header_exports_ctypes_table_and_makefile_rule_agree, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nnd_median_filter_limit", "nnd_median_filter")
@@ -31,27 +31,9 @@ def _same(a, b):
 
 
 def test_header_exports_ctypes_table_and_makefile_rule_agree():
-    from nndepth_amd import _lib
-    header = open(os.path.join(ROOT, "include", "nndepth_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        proto = re.search(rf"\b(int64_t|int)\s+{name}\s*\(([^;]*)\)\s*;", code)
-        assert proto, f"{name} is not declared in include/nndepth_amd.h"
-        assert hasattr(raw, name), f"{name} is not exported"
-        res, args = _lib.SIGNATURES[name]
-        assert res is (C.c_int64 if proto.group(1) == "int64_t" else C.c_int)
-        params = [p.strip() for p in proto.group(2).split(",") if p.strip() != "void"]
-        assert len(params) == len(args), f"{name}: {len(params)} parameters declared, {len(args)} in the ctypes table"
-        for p, a in zip(params, args):
-            want = C.c_void_p if "*" in p else {"int64_t": C.c_int64, "int": C.c_int, "double": C.c_double,
-                                                "float": C.c_float}[p.split()[0]]
-            assert a is want, f"{name}: `{p}` is {a.__name__} in the ctypes table"
-    mk = open(os.path.join(ROOT, "nndepth_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^OBJS\s*=.*\bmedian\.o\b", mk, re.M)
-    rule = re.search(r"^median\.o:.*\n\t(.*)$", mk, re.M)
-    assert rule and "$(NOSLP)" in rule.group(1) and "-ffp-contract=off" in rule.group(1)
-    assert _lib.lib.nnd_version() == 105
+    from nndepth_amd._lib import lib
+    header_exports_ctypes_table_and_makefile_rule_agree(NAMES, "median")
+    assert lib.nnd_version() == 105
 
 
 def test_limits_and_their_python_mirrors():
@@ -72,9 +54,6 @@ def test_entry_point_validates_before_any_device_call():
     zero0[0] = 0
     inf, nan = float("inf"), float("nan")
     rmax = lib.nnd_median_filter_limit(0)
-
-    def refused(rc, word):
-        assert rc < 0 and word in lib.nnd_last_error(), (rc, lib.nnd_last_error())
 
     def med(map=one, bstride=35, mask=None, pol=1, radius=1, min_count=1, fill_invalid=0, fill=0.0, guide=None, Cg=0, inv_step=1.0,
             weights=None, filtered=two, mask_out=None, changed=None, B=1, H=5, W=7):

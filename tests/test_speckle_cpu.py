@@ -3,40 +3,19 @@ the header, the exports, the ctypes table and the Makefile rule agree; every ent
 call; Python refuses by name what the kernels do not compute; the numpy oracle of tests/speckle_cases.py equals scipy's
 connected_components and reproduces tests/golden/speckle.npz (scripts/make_golden_speckle.py, built from scipy)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import speckle_cases as S
+from cabi_checks import header_exports_ctypes_table_and_makefile_rule_agree, refused
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nnd_connected_regions_workspace_bytes", "nnd_connected_regions_tile", "nnd_connected_regions", "nnd_speckle_filter")
 
 
 def test_header_exports_ctypes_table_and_makefile_rule_agree():
-    from nndepth_amd import _lib
-    header = open(os.path.join(ROOT, "include", "nndepth_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        proto = re.search(rf"\b(int64_t|int)\s+{name}\s*\(([^;]*)\)\s*;", code)
-        assert proto, f"{name} is not declared in include/nndepth_amd.h"
-        assert hasattr(raw, name), f"{name} is not exported"
-        res, args = _lib.SIGNATURES[name]
-        assert res is (C.c_int64 if proto.group(1) == "int64_t" else C.c_int)
-        params = [p.strip() for p in proto.group(2).split(",")]
-        assert len(params) == len(args), f"{name}: {len(params)} parameters declared, {len(args)} in the ctypes table"
-        for p, a in zip(params, args):
-            want = C.c_void_p if "*" in p else {"int64_t": C.c_int64, "int": C.c_int, "double": C.c_double,
-                                                "float": C.c_float}[p.split()[0]]
-            assert a is want, f"{name}: `{p}` is {a.__name__} in the ctypes table"
-    mk = open(os.path.join(ROOT, "nndepth_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^OBJS\s*=.*\bspeckle\.o\b", mk, re.M)
-    rule = re.search(r"^speckle\.o:.*\n\t(.*)$", mk, re.M)
-    assert rule and "$(NOSLP)" in rule.group(1) and "-ffp-contract=off" in rule.group(1)
+    header_exports_ctypes_table_and_makefile_rule_agree(NAMES, "speckle")
 
 
 def test_tile_and_workspace_size():
@@ -55,9 +34,6 @@ def test_entry_points_validate_before_any_device_call():
     from nndepth_amd._lib import lib
     one, big = C.c_void_p(16), C.c_void_p(1 << 20)  # never dereferenced: every call below is refused first
     inf, nan = float("inf"), float("nan")
-
-    def refused(rc, word):
-        assert rc < 0 and word in lib.nnd_last_error(), (rc, lib.nnd_last_error())
 
     def regions(map=one, bstride=35, mask=None, pol=1, max_diff=0.5, conn=4, labels=one, sizes=one, ws=big, ws_bytes=1 << 20, B=1,
                 H=5, W=7):

@@ -5,13 +5,13 @@ scripts/make_golden_warp.py and reproduces tests/golden/warp_fill.npz, which tho
 import ctypes as C
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import warp_cases as Wc
+from cabi_checks import header_exports_ctypes_table_and_makefile_rule_agree, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("nnd_warp_disparity_limit", "nnd_warp_disparity", "nnd_fill_holes_chunk", "nnd_fill_holes_workspace_bytes", "nnd_fill_holes")
@@ -32,27 +32,9 @@ def _same(a, b):
 
 
 def test_header_exports_ctypes_table_and_makefile_rule_agree():
-    from nndepth_amd import _lib
-    header = open(os.path.join(ROOT, "include", "nndepth_amd.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        proto = re.search(rf"\b(int64_t|int)\s+{name}\s*\(([^;]*)\)\s*;", code)
-        assert proto, f"{name} is not declared in include/nndepth_amd.h"
-        assert hasattr(raw, name), f"{name} is not exported"
-        res, args = _lib.SIGNATURES[name]
-        assert res is (C.c_int64 if proto.group(1) == "int64_t" else C.c_int)
-        params = [p.strip() for p in proto.group(2).split(",") if p.strip() != "void"]
-        assert len(params) == len(args), f"{name}: {len(params)} parameters declared, {len(args)} in the ctypes table"
-        for p, a in zip(params, args):
-            want = C.c_void_p if "*" in p else {"int64_t": C.c_int64, "int": C.c_int, "double": C.c_double,
-                                                "float": C.c_float}[p.split()[0]]
-            assert a is want, f"{name}: `{p}` is {a.__name__} in the ctypes table"
-    mk = open(os.path.join(ROOT, "nndepth_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^OBJS\s*=.*\bwarp\.o\b", mk, re.M)
-    rule = re.search(r"^warp\.o:.*\n\t(.*)$", mk, re.M)
-    assert rule and "$(NOSLP)" in rule.group(1) and "-ffp-contract=off" in rule.group(1)
-    assert _lib.lib.nnd_version() == 105
+    from nndepth_amd._lib import lib
+    header_exports_ctypes_table_and_makefile_rule_agree(NAMES, "warp")
+    assert lib.nnd_version() == 105
 
 
 def test_limits_chunks_and_workspace_size():
@@ -73,9 +55,6 @@ def test_entry_points_validate_before_any_device_call():
     one, big = C.c_void_p(16), C.c_void_p(1 << 20)  # never dereferenced: every call below is refused first
     inf, nan = float("inf"), float("nan")
     wmax = lib.nnd_warp_disparity_limit(0)
-
-    def refused(rc, word):
-        assert rc < 0 and word in lib.nnd_last_error(), (rc, lib.nnd_last_error())
 
     def warp(disp=one, bstride=35, mask=None, pol=1, neg=1, right=1, thr=1.0, fill=0.0, features=None, Cf=0, other=one, valid=one,
              occ=one, source=None, feats=None, B=1, H=5, W=7):

@@ -12,6 +12,7 @@ import numpy as np
 import speckle_cases as S
 
 F32 = np.float32
+bits = S.bits
 SHAPES = S.SHAPES  # + (2, 1, 9, 2 * chunk + 3) for each chunk the library reports
 RULES = ("min_abs", "max_abs", "nearest")
 GOLDEN_SHAPE = (2, 1, 9, 40)
@@ -112,10 +113,6 @@ def fill_holes(d, mask=None, mask_is_valid=True, rule="min_abs", vertical=True, 
         has |= reach
     out = np.where(ok, d, out)  # ok pixels bit for bit (np.where on float32 copies bits)
     return out, (has & ~ok).astype(np.uint8), (has == bool(mask_is_valid)).astype(np.uint8)
-
-
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 def collisions(d, disp_sign="negative", to_view="right", mask=None, threshold=1.0):
