@@ -949,6 +949,59 @@ int nnd_median_filter(const float* map, int64_t map_bstride, const unsigned char
                       const uint16_t* weights, float* filtered, unsigned char* mask_out, unsigned char* changed, int B, int H, int W,
                       void* stream);
 
+/* ------------------------------------------------------------- view synthesis and photometric error (additions within 105)
+ * The map held against the PICTURES (csrc/photometric.hip): the other picture sampled back into this view by the disparity, the
+ * L1 + SSIM error of that reconstruction in the Monodepth form, and its per-sample sums over the pixels that can be trusted.
+ * Beyond the reference, whose inference scripts have no such step.
+ * Inputs: target, other (B,C,H,W) fp32, contiguous, 1 <= C <= nnd_photometric_limit(0); disp (B,1,H,W) fp32, its batch stride read
+ * where it lies; mask: optional bytes, polarity mask_valid_is_one as in nnd_median_filter; negative != 0: m = -d, else m = d;
+ * target_is_left != 0: disp belongs to the left picture and `other` is the right one, else the other way round.  H, W >= 2.
+ * Per sample, row y, column x, every numbered step one rounded fp32 operation unless it says double:
+ *   1  m = (negative ? -d : d) + 0.0f;  src_ok = mask-valid && isfinite(m) && m >= 0.
+ *   2  xr = target_is_left ? (float)x - m : (float)x + m;  in = src_ok && xr >= 0 && xr <= (float)(W-1).
+ *   3  fl = floorf(xr), i0 = (int)fl, i1 = min(i0+1, W-1), f = xr - fl.  Per channel rec_c = other_c[y,i0] * (1.0f - f) +
+ *      other_c[y,i1] * f, computed as mul, mul, add (the sequence of nnd_lr_consistency).  nnd_synthesize_view writes
+ *      recon = in ? rec_c : fill and valid_out = in, and stops here.
+ *   4  The window is 3 x 3 with reflected borders: index -1 reads 1, index H reads H-2, likewise in W.  box(v) at (y,x) takes row
+ *      sums first: r(y') = (v(y',x-1) + v(y',x)) + v(y',x+1), then box = (r(y-1) + r(y)) + r(y+1).
+ *   5  Per channel, with inv9 = (float)(1.0/9.0) and t the target picture: mx = box(t)*inv9, my = box(rec)*inv9,
+ *      sx = box(t*t)*inv9 - mx*mx, sy = box(rec*rec)*inv9 - my*my, sxy = box(t*rec)*inv9 - mx*my,
+ *      n = ((2*mx)*my + c1) * (2*sxy + c2), dn = ((mx*mx + my*my) + c1) * ((sx + sy) + c2),
+ *      ds_c = clamp((1.0f - n/dn) * 0.5f, 0, 1): for every number the bits of fminf(fmaxf(v, 0), 1); a NaN stays a NaN, as in
+ *      torch.clamp, so that a non-finite picture value makes every window that holds it not valid.  `/` is the correctly rounded
+ *      fp32 division.
+ *   6  l1_c = fabsf(t_c - rec_c) * inv_range.
+ *   7  ds and l1 are the sums over the channels in channel order, times 1.0f / (float)C.
+ *   8  e = ssim_weight * ds + (1.0f - ssim_weight) * l1, computed as mul, mul, add.  With ssim_weight == 0: e = l1, ds is not
+ *      computed, dssim_out is `fill` everywhere and the sum of ds in `stats` is 0.
+ *   9  With ssim_weight > 0: valid = `in` at all nine reflected taps && isfinite(e); with ssim_weight == 0 only the centre tap
+ *      counts.  Where not valid, error, l1_out and dssim_out are `fill`.  A reconstruction at a tap that is not `in` is never used.
+ *  10  stats[b] = { count of valid pixels, sum e, sum l1, sum ds } over the valid pixels of sample b: every fp32 value converted to
+ *      double and added in double, in a fixed order; the count is exact.
+ * Outputs of nnd_photometric_error: error (B,H,W) floats, required; optional: l1_out, dssim_out (B,H,W) floats, valid_out (B,H,W)
+ * bytes in the polarity of the mask (mask_valid_is_one), stats (B x 4 doubles on the device).  nnd_synthesize_view: recon
+ * (B,C,H,W), required; valid_out optional.  `workspace` (needed only with stats) = nnd_photometric_workspace_bytes(B,H,W) device
+ * bytes, 8-byte aligned, the caller's: four doubles per workgroup.
+ * nnd_synthesize_view is ONE launch without a workspace.  nnd_photometric_error is ONE launch that writes the maps and a partial
+ * per workgroup into that workgroup's own slot, and with stats a second small one that adds the partials in a fixed order.  No
+ * atomics, no host synchronisation, the same bytes on every run; nothing depends on what the outputs or the workspace held.
+ * Refused before any HIP call: a null required pointer, error / recon aliasing an input, B, H, W out of range (1 <= B <= 65535,
+ * H, W >= 2, H*W < 2^31), a batch stride below H*W, C outside 1 .. nnd_photometric_limit(0), ssim_weight outside [0, 1] or NaN,
+ * c1, c2 or inv_range not finite or <= 0, stats without a workspace of the right size and alignment.
+ * nnd_photometric_limit: the largest channel count (which = 0; >= 4), the height (1) and width (2) of the output tile of one
+ * workgroup; anything else: < 0.  nnd_photometric_workspace_bytes: < 0 for a shape that is refused.
+ * Not here: the edge-aware smoothness term, Monodepth2's identity auto-mask (a zero disparity gives the unwarped error), other
+ * window sizes, gradients, 16-bit pictures.                                                                                     */
+int nnd_photometric_limit(int which);
+int64_t nnd_photometric_workspace_bytes(int B, int H, int W);
+int nnd_synthesize_view(const float* other, const float* disp, int64_t disp_bstride, const unsigned char* mask, int mask_valid_is_one,
+                        int negative, int target_is_left, float fill, float* recon, unsigned char* valid_out, int B, int C, int H,
+                        int W, void* stream);
+int nnd_photometric_error(const float* target, const float* other, const float* disp, int64_t disp_bstride, const unsigned char* mask,
+                          int mask_valid_is_one, int negative, int target_is_left, float ssim_weight, float c1, float c2,
+                          float inv_range, float fill, float* error, float* l1_out, float* dssim_out, unsigned char* valid_out,
+                          double* stats, void* workspace, int64_t workspace_bytes, int B, int C, int H, int W, void* stream);
+
 /* ------------------------------------------------------------- LoFTR layer with linear attention (CREStereo)
  * Replaces LoFTREncoderLayer.forward  nndepth/blocks/transformer.py:39-66 with LinearAttention  nndepth/blocks/attn_block.py:23-58
  * (no masks).  The reference's (N, H*W, C) tokens are the (N,C,H,W) maps transposed, so every nn.Linear is a 1x1 conv of

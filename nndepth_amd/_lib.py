@@ -240,6 +240,11 @@ SIGNATURES = {
     "nnd_fill_holes": (_I, [_P, C.c_int64, _P, _I, _I, _I, C.c_float, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P]),
     "nnd_median_filter_limit": (_I, [_I]),
     "nnd_median_filter": (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, C.c_float, _P, _I, C.c_float, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "nnd_photometric_limit": (_I, [_I]),
+    "nnd_photometric_workspace_bytes": (C.c_int64, [_I, _I, _I]),
+    "nnd_synthesize_view": (_I, [_P, _P, C.c_int64, _P, _I, _I, _I, C.c_float, _P, _P, _I, _I, _I, _I, _P]),
+    "nnd_photometric_error": (_I, [_P, _P, _P, C.c_int64, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P,
+                                   _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P]),
     "nnd_loftr_packed_floats": (C.c_int64, [_I, _I]),
     "nnd_loftr_workspace_floats": (C.c_int64, [_I, _I, _I, _I, _I]),
     "nnd_loftr_pack": (_I, [_I, _I, C.POINTER(_P), _P]),

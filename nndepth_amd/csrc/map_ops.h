@@ -1,4 +1,5 @@
-// The input contract of the disparity / depth map operations (geometry.hip, speckle.hip, warp.hip, median.hip), stated once.
+// The input contract of the disparity / depth map operations (geometry.hip, speckle.hip, warp.hip, median.hip, photometric.hip),
+// stated once.
 //   map     (B,1,H,W) fp32 with dense rows; sample b starts bstride >= H*W floats after sample b-1 (a channel slice of a 2-channel
 //           output, half of a stacked batch).  1 <= B <= 65535 (a grid dimension), H, W > 0.
 //   mask    optional, B*H*W dense bytes; any non-zero byte is "set".  valid_is_one != 0: set = valid (a valid mask); == 0: set =

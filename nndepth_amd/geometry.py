@@ -13,6 +13,9 @@ Here:
                                                         Depth.fill_holes): the other view and an occlusion mask from ONE map
     median_filter, range_weights                       (csrc/median.hip; Disparity.median_filter, Depth.median_filter): a masked
                                                         k x k median, or a weighted median guided by a picture
+    synthesize_view, photometric_error, photometric_score    (csrc/photometric.hip; Disparity.synthesize,
+                                                        Disparity.photometric_error): the other PICTURE seen from this view, and the
+                                                        L1 + SSIM error of that reconstruction with its per-sample sums
 
 Maps are (B,1,H,W) fp32 on the HIP device; a batch stride is read where it lies (a channel slice of CREStereo's 2-channel
 output, half of a stacked batch).  Masks are torch.bool or torch.uint8, (B,1,H,W) or (B,H,W).  Camera values come from
@@ -504,6 +507,131 @@ def median_filter(map: torch.Tensor, radius: int = 1, valid_mask: Optional[torch
                                     float(fill), _p(guide), C, inv_step, None if table is None else table.ctypes.data, _p(filtered),
                                     _p(mask_out), _p(changed), B, H, W, _stream(d.device)), what)
     return (filtered, mask_out, changed) if return_changed else (filtered, mask_out)
+
+
+# ------------------------------------------------------------------ view synthesis and photometric error (csrc/photometric.hip)
+def photometric_max_channels() -> int:
+    """The largest channel count of a picture that `synthesize_view` and `photometric_error` accept."""
+    return int(lib.nnd_photometric_limit(0))
+
+
+def photometric_tile() -> Tuple[int, int]:
+    """(height, width) of the output tile of one `photometric_error` workgroup."""
+    return int(lib.nnd_photometric_limit(1)), int(lib.nnd_photometric_limit(2))
+
+
+def photometric_workspace_bytes(B: int, H: int, W: int) -> int:
+    """Device bytes `photometric_error` needs for its statistics at (B,C,H,W): four doubles per workgroup."""
+    return _nbytes("nnd_photometric_workspace_bytes", B, H, W, "photometric_workspace_bytes")
+
+
+def _pictures(what: str, disp, valid_mask, pictures):
+    """The (B,1,H,W) map and its mask through `_map4`, and each (name, picture) as a contiguous (B,C,H,W) fp32 tensor beside it;
+    what does not fit is refused by name, whatever the device."""
+    if torch.is_tensor(disp) and disp.dtype == torch.float32 and _is_map(disp):
+        B, _, H, W = disp.shape
+        cmax = photometric_max_channels()
+        for name, p in pictures:
+            if not torch.is_tensor(p) or p.dtype != torch.float32:
+                raise NndError(f"{what}: {name} is torch.float32; got {p.dtype if torch.is_tensor(p) else type(p).__name__}")
+            if p.ndim != 4 or p.shape[0] != B or tuple(p.shape[2:]) != (H, W) or not 1 <= p.shape[1] <= cmax:
+                raise NndError(f"{what}: {name} is (B,C,H,W) = ({B},1..{cmax},{H},{W}); got {tuple(p.shape)}")
+        if len({p.shape[1] for _, p in pictures}) > 1:
+            raise NndError(f"{what}: the pictures have {' and '.join(str(p.shape[1]) for _, p in pictures)} channels")
+    d, m = _map4(disp, what, valid_mask, shape_first=True)
+    out = []
+    for name, p in pictures:
+        if p.device != d.device:
+            raise NndError(f"{what}: {name} is on {p.device}, the map on {d.device} (no CPU fallback exists)")
+        out.append(p.contiguous())
+    if d.shape[2] < 2 or d.shape[3] < 2:
+        raise NndError(f"{what}: a map of {tuple(d.shape)}: H and W must be at least 2 (the reflected border)")
+    return d, m, out
+
+
+def _view(view: str, what: str) -> int:
+    if view not in _VIEWS:
+        raise NndError(f"{what}: target_view must be one of {_VIEWS}; got {view!r}")
+    return int(view == "left")
+
+
+def synthesize_view(other: torch.Tensor, disp: torch.Tensor, disp_sign: str = "negative", target_view: str = "left",
+                    valid_mask: Optional[torch.Tensor] = None, mask_is_valid: bool = True, fill: float = 0.0):
+    """(recon (B,C,H,W) fp32, valid (B,1,H,W) uint8 in the polarity of the mask): the OTHER picture seen from the view `disp`
+    belongs to, a backward warp along the row in one launch (csrc/photometric.hip).  Per pixel, each step one rounded fp32
+    operation:
+
+        m = (+-d) + 0.0f ;  src_ok = mask-valid && isfinite(m) && m >= 0
+        xr = float(x) - m for target_view "left" (other = the right picture), float(x) + m for "right"
+        in = src_ok && 0 <= xr <= W-1 ;  i0 = floor(xr), i1 = min(i0+1, W-1), f = xr - i0
+        recon_c = in ? other_c[y,i0] * (1-f) + other_c[y,i1] * f : fill          (mul, mul, add)
+
+    valid = in; with mask_is_valid False the returned mask is 1 where NOT in, like the occlusion mask that was read.  No CPU
+    fallback."""
+    what = "synthesize_view"
+    neg, left = _sign(disp_sign, what), _view(target_view, what)
+    d, m, (o,) = _pictures(what, disp, valid_mask, (("the other picture", other),))
+    B, C, H, W = o.shape
+    recon = torch.empty((B, C, H, W), dtype=torch.float32, device=d.device)
+    valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib.nnd_synthesize_view(_p(o), _p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), neg, left, float(fill), _p(recon),
+                                      _p(valid), B, C, H, W, _stream(d.device)), what)
+    return recon, valid
+
+
+def photometric_error(target: torch.Tensor, other: torch.Tensor, disp: torch.Tensor, disp_sign: str = "negative",
+                      target_view: str = "left", valid_mask: Optional[torch.Tensor] = None, mask_is_valid: bool = True,
+                      ssim_weight: float = 0.85, data_range: float = 2.0, fill: float = 0.0, return_parts: bool = False,
+                      stats: bool = True, workspace: Optional[torch.Tensor] = None):
+    """(error (B,1,H,W) fp32, valid (B,1,H,W) uint8 in the polarity of the mask, stats[, l1, dssim]): how well `disp` explains
+    `target` from `other`, the Monodepth photometric error ssim_weight * (1 - SSIM) / 2 + (1 - ssim_weight) * |target - recon| /
+    data_range with a 3 x 3 reflected window, fused with the backward warp of `synthesize_view` in one launch
+    (csrc/photometric.hip; the numbered contract is in include/nndepth_amd.h).  c1 = (0.01 data_range)^2, c2 = (0.03
+    data_range)^2 and 1 / data_range are formed as float32 here, once; the default 2.0 fits the models' [-1, 1] frames.
+
+    valid: every one of the nine reflected taps was reconstructed (ssim_weight 0: the pixel itself) and the error is finite; the
+    other pixels hold `fill` in every map.  stats: a (B,4) float64 DEVICE tensor {count of valid pixels, sum error, sum l1, sum
+    dssim} per sample (None with stats=False), added in double in a fixed order by a second small launch: stats[:, 1] / stats[:, 0]
+    is the mean error, and nothing here synchronises with the host.  `workspace`: `photometric_workspace_bytes(B,H,W)` device
+    bytes of the caller's (a fresh tensor otherwise).  With ssim_weight 0 the error is l1, dssim is `fill` and its sum 0.
+    Not here: the edge-aware smoothness term, Monodepth2's identity auto-mask (pass a zero disparity for the unwarped error), other
+    windows, gradients, 16-bit pictures.  No CPU fallback."""
+    import numpy as np
+    what = "photometric_error"
+    neg, left = _sign(disp_sign, what), _view(target_view, what)
+    w, r = float(ssim_weight), float(data_range)
+    if not 0.0 <= w <= 1.0:
+        raise NndError(f"{what}: ssim_weight must be in [0, 1]; got {ssim_weight}")
+    if not (r > 0.0 and r < float("inf")):
+        raise NndError(f"{what}: data_range must be finite and > 0; got {data_range}")
+    c1, c2, inv_range = (float(np.float32(v)) for v in ((0.01 * r) ** 2, (0.03 * r) ** 2, 1.0 / r))
+    d, m, (t, o) = _pictures(what, disp, valid_mask, (("the target picture", target), ("the other picture", other)))
+    B, C, H, W = t.shape
+    dev = d.device
+    error = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=dev)
+    l1 = torch.empty_like(error) if return_parts else None
+    dssim = torch.empty_like(error) if return_parts else None
+    st, ws, ws_bytes = None, None, 0
+    if stats:
+        st = torch.empty((B, 4), dtype=torch.float64, device=dev)
+        ws = _workspace(photometric_workspace_bytes(B, H, W), workspace, torch.float64, dev, what, "photometric_workspace_bytes")
+        ws_bytes = ws.numel() * ws.element_size()
+    with torch.cuda.device(dev):
+        check(lib.nnd_photometric_error(_p(t), _p(o), _p(d), _bstride(d), _p(m), int(bool(mask_is_valid)), neg, left, w, c1, c2, inv_range,
+                                        float(fill), _p(error), _p(l1), _p(dssim), _p(valid), _p(st), _p(ws), ws_bytes, B, C, H, W,
+                                        _stream(dev)), what)
+    return (error, valid, st, l1, dssim) if return_parts else (error, valid, st)
+
+
+def photometric_score(forward: Callable, left: torch.Tensor, right: torch.Tensor, threshold: float = 1.0, **kw):
+    """(scene.Disparity, error, stats): `occlusion_from_warp(forward, left, right, threshold)`, then `photometric_error(left,
+    right, disp.data, valid_mask=disp.occlusion, mask_is_valid=False, **kw)`: one forward, and whether its map explains the right
+    picture from the left where the warp does not call it occluded."""
+    disp = occlusion_from_warp(forward, left, right, threshold)
+    out = photometric_error(left, right, disp.data, valid_mask=disp.occlusion, mask_is_valid=False, **kw)
+    return disp, out[0], out[2]
 
 
 def occlusion_from_warp(forward: Callable, left: torch.Tensor, right: torch.Tensor, threshold: float = 1.0):

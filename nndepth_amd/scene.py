@@ -308,6 +308,27 @@ class Disparity:
                                            min_count=min_count, fill_invalid=fill_invalid, **weights_kw)
         return Disparity(data=data, disp_sign=self.disp_sign, occlusion=_mask_like(occ, self.occlusion), baseline=self.baseline)
 
+    def synthesize(self, other, view: str = "left"):
+        """(recon, invalid): the OTHER picture (a Frame or a (B,C,H,W) fp32 tensor, C <= 4) seen from this map's view
+        (geometry.synthesize_view, csrc/photometric.hip): `view` says which view this map belongs to, "left" samples the right
+        picture at x - |d|.  Occluded pixels (self.occlusion == 1) are not reconstructed and hold 0.  `invalid` is in the polarity
+        of the occlusion, 1 = not reconstructed (occluded, not finite, of the wrong sign or sampled from outside the frame), in the
+        dtype of self.occlusion, uint8 if there was none.  (B,1,H,W) maps; not a method of the reference."""
+        from . import geometry
+        recon, inv = geometry.synthesize_view(_guide_tensor(other), self.data, self.disp_sign, view, self.occlusion, False)
+        return recon, _mask_like(inv, self.occlusion)
+
+    def photometric_error(self, frame, other, view: str = "left", **kw):
+        """(error, invalid, stats[, l1, dssim]): how well this map explains `frame` (the picture of its own view) from `other`
+        (the other view's), the Monodepth L1 + SSIM error per pixel and its per-sample sums on the device
+        (geometry.photometric_error; `kw`: ssim_weight, data_range, fill, return_parts, stats, workspace).  Both pictures are
+        Frames or (B,C,H,W) fp32 tensors.  Occluded pixels (self.occlusion == 1) are not sampled; `invalid` is in the polarity of the
+        occlusion, 1 = no trusted error at this pixel, in the dtype of self.occlusion, uint8 if there was none."""
+        from . import geometry
+        out = geometry.photometric_error(_guide_tensor(frame), _guide_tensor(other), self.data, self.disp_sign, view, self.occlusion,
+                                         False, **kw)
+        return (out[0], _mask_like(out[1], self.occlusion)) + tuple(out[2:])
+
 
 def _guide_tensor(guide):
     """A Frame's picture, (C,H,W) or (B,C,H,W), or a tensor, as the (B,C,H,W) guide of geometry.median_filter."""
